@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: queries/sec + recall@10 of the nlsh query-time hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a torchrun child
@@ -21,11 +21,17 @@ pipeline that consumes device tensors sees) is timed in a second K-step region a
 stream, which is where `roofline` comes from.  At N=1 the kernels of a device-resident step run back to back on one
 stream (each kernel alone on the chip: ONE `nlsh_query_batch` call, five launches); at N>1 they go through the graph slots of
 nlsh_amd/pipeline.py with the all-gather behind each batch on its slot's stream (`--pipeline on|off` forces either), and the scan
-kernel is timed alone in a short sequential region of its own.  The default N=1 run also carries `workloads`: configs[2]
+kernel is timed alone in a short sequential region of its own.  The `--full` N=1 run also carries `workloads`: configs[2]
 (GloVe-1.2M-shaped) and configs[1] on SURVEY 8(d)'s own generator, 3 + 20 device-resident steps each (`--no-side-workloads` skips).
 N>1: corpus buckets sharded over the ranks (whole buckets per rank, one build-time all-to-all; `--shard rows` keeps
 contiguous row ranges), every rank answers all queries over its shard, one all-gather (RCCL) of the per-rank top-k +
 merge per step ("strong" scaling: total work fixed).
+
+A plain run measures the headline alone: set up, build the index, warm up, time the K protocol steps, write the last step's lists
+if `--dump-outputs DIR` is given (DIR/ids.npy, n_candidates.npy, query_rows.npy; fixed probe seeds, so the same arguments give the
+same arrays), compute recall@10 with one more call and print the line.  Everything else described here -- index rebuild time,
+`protocol_qps_opt_in`, `own_slice_qps`, the device-resident region and `roofline`, the folded-L2 and pipelined regions, `encoder`,
+`cpu_baseline`, `workloads` -- is measured with `--full` only.
 
 `value` is measured with the facade's DEFAULT settings (what an unmodified Trainer.fit gets); `protocol_qps_opt_in` is the
 same region with the two host-side opt-ins.  `--l2-form folded` prints the complete line on the opt-in
@@ -129,7 +135,35 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of each baseline sample")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launch check only (no GPU needed): start the ranks, rendezvous over gloo, print {n_gpus} and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: index rebuild time, the opt-in and own-slice protocol regions, the device-resident "
+                         "region with its roofline, the folded-L2 and pipelined regions, encoder / HBM copy figures, cpu_baseline and the "
+                         "`workloads` object.  Off: set up, warm up, time --steps protocol steps, recall@10, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step returned to its caller as DIR/*.npy (float64): "
+                         "ids.npy [Q, k] (-1 past a short list), n_candidates.npy [Q], query_rows.npy [Q] (rows of the step's batch; a fixed, "
+                         "seeded sample of them when the whole would exceed 64 MB)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ids, ncand, k):
+    """The lists `Indexer.query` returned in the last timed step, as float64 arrays: the step's batch and probe seed are fixed, so two
+    builds given the same arguments can be compared array for array."""
+    Q = len(ids)
+    rows = np.arange(Q)
+    per_row = 8 * (k + 2)                                   # ids, n_candidates and query_rows
+    if Q * per_row > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(Q, DUMP_LIMIT_BYTES // per_row, replace=False))
+    out = np.full((len(rows), k), -1.0)
+    for j, r in enumerate(rows.tolist()):
+        out[j, :len(ids[r])] = ids[r]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ids.npy"), out)
+    np.save(os.path.join(out_dir, "n_candidates.npy"), np.asarray(ncand, dtype=np.float64)[rows])
+    np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
 
 
 def _free_port():
@@ -426,7 +460,7 @@ def main():
     torch.cuda.synchronize()
     build_s = time.time() - t0
     rebuild_s = None
-    if world == 1:      # the build that recurs (the reference rebuilds every 300 training steps, main.py:402): allocator warm
+    if world == 1 and args.full:      # the build that recurs (the reference rebuilds every 300 training steps, main.py:402): allocator warm
         t0 = time.time()
         Indexer(hashing, shard, distance, compat=H <= 16, seg_rows=args.seg_rows, algo=args.algo, l2_form=args.l2_form, window_rows=args.window)
         torch.cuda.synchronize()
@@ -459,9 +493,10 @@ def main():
         Indexer.defer_result_release = Indexer.untracked_results = bool(opt_in)
         try:
             def query_lists(i):
-                if sharded is not None:   # same seed on every rank
+                # the step's probe seed is fixed (the same on every rank): the last step's lists are the same from run to run
+                if sharded is not None:
                     return sharded.query(qb[i % B], k=k, hash_times=P, seed=5000 + i, own_slice=own)
-                return indexer.query(qb[i % B], k=k, hash_times=P)
+                return indexer.query(qb[i % B], k=k, hash_times=P, seed=5000 + i)
 
             held = None
             for i in range(max(warmup, 1)):        # at least one: sizes the task table (may retry once); untimed
@@ -481,180 +516,185 @@ def main():
 
     elapsed, call_s, (ids_api, nc_api) = protocol_region(own=False, opt_in=False)
     assert isinstance(ids_api, list) and len(ids_api) == Q and isinstance(nc_api, list)
-    elapsed_opt_in, _, _ = protocol_region(own=False, opt_in=True)
-    elapsed_own = None
-    if sharded is not None:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ids_api, nc_api, k)
+    elapsed_opt_in, elapsed_own = None, None
+    if args.full:
+        elapsed_opt_in, _, _ = protocol_region(own=False, opt_in=True)
+    if args.full and sharded is not None:
         elapsed_own, _, (ids_own, _) = protocol_region(own=True, opt_in=False)
         q_lo, q_hi = shard_range(Q, rank, world)
         assert len(ids_own) == q_hi - q_lo
 
-    # ------------------------------------------------------------------ region B: same path, results left in HBM
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-    ev_x = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-    for a, b in ev + ev_x:  # instantiate the hipEvent handles
-        a.record(); b.record()
-    xchg = TopkExchange(k) if world > 1 else None
-    cur = [None]
-
-    def exchange(k64, nc):   # tail stage on a sharded index: all-gather of per-shard top-k + merge
-        i = cur[0]
-        if i is not None:
-            ev_x[i][0].record()
-        out_ = xchg(k64, nc)
-        if i is not None:
-            ev_x[i][1].record()
-        return out_
-
-    use_pipeline = args.pipeline == "on" or (args.pipeline == "auto" and world > 1)
-    pipe = None
-    if use_pipeline:
-        from nlsh_amd.pipeline import QueryPipeline
-        pipe = QueryPipeline(indexer, qb[0], k=k, hash_times=P, depth=3, exchange=exchange if world > 1 else None)
-
-    def device_step(i, events=None, mark=False):
-        q = qb[i % B]
-        seed = 1000 + i  # identical on every rank -> identical multi-probe keys
-        if pipe is not None:
-            cur[0] = i if (events is not None or mark) else None     # timed steps bracket their exchange with ev_x[i]
-            return pipe.submit(q, seed=seed, events=events)[:3]
-        dist_, idx_, nc_, k64 = indexer.query_tensors(q, k=k, hash_times=P, seed=seed, want_keys=world > 1, check=False, events=events)
-        if world > 1:
-            if events is not None:
-                ev_x[i][0].record()
-            dist_, idx_, nc_ = gather_and_merge(k64, nc_, k)
-            if events is not None:
-                ev_x[i][1].record()
-        return dist_, idx_, nc_
-
-    # graph slots (r06) run whole batches concurrently on the slots' own streams: two scan kernels may share the chip, so events around one
-    # of them no longer time it alone -- and a batch with scan events is launched eagerly instead of replayed.  The timed pipelined region
-    # then runs WITHOUT scan events and the kernel is timed in a short sequential region of its own below (same batches, same seeds).
-    graph_slots = pipe is not None and getattr(pipe, "graph", False)
-    for i in range(warmup):
-        device_step(i % B)
-    fence()
-    t0 = time.perf_counter()
-    for i in range(steps):
-        device_step(i, events=None if graph_slots else ev[i], mark=True)
-    if pipe is not None:
-        pipe.synchronize()
-    fence()
-    elapsed_dev = max_over_ranks(time.perf_counter() - t0)
-    last_status = pipe.last_slot.status if pipe is not None else indexer.last_status
-    n_tasks, overflow = (int(v) for v in last_status.cpu())
-    assert overflow == 0 and not (pipe is not None and pipe.overflowed()), "segment table overflow inside the timed region"
-    if graph_slots:
-        for i in range(steps):     # the scan kernel alone on the chip: sequential steps on one stream, no exchange
-            indexer.query_tensors(qb[i % B], k=k, hash_times=P, seed=1000 + i, want_keys=world > 1, check=False, events=ev[i])
-        fence()
-    scan_avg_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-
-    # N=1, L2: the same K sequential device-resident steps with the OPT-IN folded L2 form (NLSH_METRIC_L2_EPS_FOLDED: (q + eps) - c, two
-    # vector operations per element instead of three, one rounding per element away from the reference's order; never the default,
-    # never `value` or `roofline`) -- reported beside the shipped bit-exact form
-    folded = None
-    if world == 1 and pipe is None and metric == "l2" and args.l2_form == "exact":
-        ev_f = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-        for a, b in ev_f:
+    # ------------------------------------------------------------------ --full: everything beside the headline
+    if args.full:
+        # ------------------------------------------------------------------ region B: same path, results left in HBM
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+        ev_x = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+        for a, b in ev + ev_x:  # instantiate the hipEvent handles
             a.record(); b.record()
-        indexer.l2_form = "folded"
-        try:
-            for i in range(max(warmup, 1)):
-                device_step(i % B)
-            fence()
-            t0 = time.perf_counter()
-            for i in range(steps):
-                device_step(i, events=ev_f[i])
-            fence()
-            el_f = time.perf_counter() - t0
-            folded = {"scan_avg_ms": float(np.mean([a.elapsed_time(b) for a, b in ev_f])), "device_resident_ms_per_step": 1e3 * el_f / steps,
-                      "device_resident_qps": Q * steps / el_f, "algo": int(indexer.last_algo)}
-            d_f, i_f, _, _ = indexer.query_tensors(qb[0], k=k, hash_times=P, seed=5000)
-        finally:
-            indexer.l2_form = "exact"
-        # how far apart the two forms are on this batch: id lists that differ at all, and the largest relative distance difference
-        # (tests/test_gpu_fullsize.py holds every difference to a k-th-distance tie within 1e-4 and recall@10 to equality)
-        d_e, i_e, _, _ = indexer.query_tensors(qb[0], k=k, hash_times=P, seed=5000)
-        both = (i_e >= 0) & (i_f >= 0)
-        folded["id_lists_differing"] = int((i_e != i_f).any(1).sum().item())
-        folded["max_rel_distance_diff"] = float(((d_e - d_f).abs() / d_e.abs().clamp(min=1.0))[both].max().item()) if bool(both.any()) else 0.0
+        xchg = TopkExchange(k) if world > 1 else None
+        cur = [None]
 
-    # N=1: the same K device-resident steps through the three-stage pipeline as well (what a serving loop would run; the
-    # sequential region above is the one whose scan kernel is timed alone on the chip for the roofline)
-    piped_qps = None
-    if world == 1 and pipe is None:
-        from nlsh_amd.pipeline import QueryPipeline
-        alt = QueryPipeline(indexer, qb[0], k=k, hash_times=P, depth=3)
+        def exchange(k64, nc):   # tail stage on a sharded index: all-gather of per-shard top-k + merge
+            i = cur[0]
+            if i is not None:
+                ev_x[i][0].record()
+            out_ = xchg(k64, nc)
+            if i is not None:
+                ev_x[i][1].record()
+            return out_
+
+        use_pipeline = args.pipeline == "on" or (args.pipeline == "auto" and world > 1)
+        pipe = None
+        if use_pipeline:
+            from nlsh_amd.pipeline import QueryPipeline
+            pipe = QueryPipeline(indexer, qb[0], k=k, hash_times=P, depth=3, exchange=exchange if world > 1 else None)
+
+        def device_step(i, events=None, mark=False):
+            q = qb[i % B]
+            seed = 1000 + i  # identical on every rank -> identical multi-probe keys
+            if pipe is not None:
+                cur[0] = i if (events is not None or mark) else None     # timed steps bracket their exchange with ev_x[i]
+                return pipe.submit(q, seed=seed, events=events)[:3]
+            dist_, idx_, nc_, k64 = indexer.query_tensors(q, k=k, hash_times=P, seed=seed, want_keys=world > 1, check=False, events=events)
+            if world > 1:
+                if events is not None:
+                    ev_x[i][0].record()
+                dist_, idx_, nc_ = gather_and_merge(k64, nc_, k)
+                if events is not None:
+                    ev_x[i][1].record()
+            return dist_, idx_, nc_
+
+        # graph slots (r06) run whole batches concurrently on the slots' own streams: two scan kernels may share the chip, so events around one
+        # of them no longer time it alone -- and a batch with scan events is launched eagerly instead of replayed.  The timed pipelined region
+        # then runs WITHOUT scan events and the kernel is timed in a short sequential region of its own below (same batches, same seeds).
+        graph_slots = pipe is not None and getattr(pipe, "graph", False)
         for i in range(warmup):
-            alt.submit(qb[i % B], seed=1000 + i)
-        alt.synchronize()
+            device_step(i % B)
         fence()
         t0 = time.perf_counter()
         for i in range(steps):
-            alt.submit(qb[i % B], seed=1000 + i)
-        alt.synchronize()
+            device_step(i, events=None if graph_slots else ev[i], mark=True)
+        if pipe is not None:
+            pipe.synchronize()
         fence()
-        piped_qps = Q * steps / (time.perf_counter() - t0)
-        assert not alt.overflowed()
-        del alt
+        elapsed_dev = max_over_ranks(time.perf_counter() - t0)
+        last_status = pipe.last_slot.status if pipe is not None else indexer.last_status
+        n_tasks, overflow = (int(v) for v in last_status.cpu())
+        assert overflow == 0 and not (pipe is not None and pipe.overflowed()), "segment table overflow inside the timed region"
+        if graph_slots:
+            for i in range(steps):     # the scan kernel alone on the chip: sequential steps on one stream, no exchange
+                indexer.query_tensors(qb[i % B], k=k, hash_times=P, seed=1000 + i, want_keys=world > 1, check=False, events=ev[i])
+            fence()
+        scan_avg_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
-    # candidates per launch of the timed device steps (untimed recomputation with the same batches and probe seeds)
-    sum_c, uniq_rows = [], []
-    tables = dict(indexer._max_tasks)          # task tables as the timed steps saw them
-    bucket_rows = (indexer.offsets[1:] - indexer.offsets[:-1]).long() if indexer.n_buckets else None
-    for i in range(steps):
-        sum_c.append(int(indexer.query_tensors(qb[i % B], k=k, hash_times=P, seed=1000 + i)[2].long().sum().item()))
-        # rows of the buckets the batch probes at all, each counted ONCE: what a schedule that shares a fetched row between the
-        # queries probing its bucket has to read at least (the bucket-major schedules' algorithmic bytes)
-        if bucket_rows is not None:
-            kk, nn = indexer.hash_device(qb[i % B], hash_times=P, seed=1000 + i)
-            pos = torch.searchsorted(indexer.uniq_keys, kk.clamp(min=int(indexer.uniq_keys[0]), max=int(indexer.uniq_keys[-1]))).clamp(max=indexer.n_buckets - 1)
-            hit = (indexer.uniq_keys[pos] == kk) & (torch.arange(kk.shape[1], device=dev)[None, :] < nn[:, None])
-            uniq_rows.append(int(bucket_rows[torch.unique(pos[hit])].sum().item()))
-        # every timed step (not only the last, whose status word was read above) fitted its task table
-        needed, tkey = int(indexer.last_status.cpu()[0]), indexer._last_tkey
-        assert tkey not in tables or needed <= tables[tkey], f"step {i}: {needed} tasks > table {tables[tkey]} inside the timed region"
-    sum_c_local = float(np.mean(sum_c))
-    unique_bytes = 4.0 * d * float(np.mean(uniq_rows)) if uniq_rows else 0.0
-    algo_bytes = 4.0 * d * sum_c_local
-    flops_per_pair = 3.0 * d if metric == "l2" else 2.0 * d      # (q-c), +eps, fma per element | one fma
-    algo_flops = flops_per_pair * sum_c_local
-    t_scan = scan_avg_ms * 1e-3
+        # N=1, L2: the same K sequential device-resident steps with the OPT-IN folded L2 form (NLSH_METRIC_L2_EPS_FOLDED: (q + eps) - c, two
+        # vector operations per element instead of three, one rounding per element away from the reference's order; never the default,
+        # never `value` or `roofline`) -- reported beside the shipped bit-exact form
+        folded = None
+        if world == 1 and pipe is None and metric == "l2" and args.l2_form == "exact":
+            ev_f = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+            for a, b in ev_f:
+                a.record(); b.record()
+            indexer.l2_form = "folded"
+            try:
+                for i in range(max(warmup, 1)):
+                    device_step(i % B)
+                fence()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    device_step(i, events=ev_f[i])
+                fence()
+                el_f = time.perf_counter() - t0
+                folded = {"scan_avg_ms": float(np.mean([a.elapsed_time(b) for a, b in ev_f])), "device_resident_ms_per_step": 1e3 * el_f / steps,
+                          "device_resident_qps": Q * steps / el_f, "algo": int(indexer.last_algo)}
+                d_f, i_f, _, _ = indexer.query_tensors(qb[0], k=k, hash_times=P, seed=5000)
+            finally:
+                indexer.l2_form = "exact"
+            # how far apart the two forms are on this batch: id lists that differ at all, and the largest relative distance difference
+            # (tests/test_gpu_fullsize.py holds every difference to a k-th-distance tie within 1e-4 and recall@10 to equality)
+            d_e, i_e, _, _ = indexer.query_tensors(qb[0], k=k, hash_times=P, seed=5000)
+            both = (i_e >= 0) & (i_f >= 0)
+            folded["id_lists_differing"] = int((i_e != i_f).any(1).sum().item())
+            folded["max_rel_distance_diff"] = float(((d_e - d_f).abs() / d_e.abs().clamp(min=1.0))[both].max().item()) if bool(both.any()) else 0.0
 
-    # encoder (MFMA) utilisation on this rank's corpus rows, and the box's measured HBM copy rate next to the spec peak
-    enc, copy_gbps = None, None
-    if world == 1:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        hashing.hash_device(shard, n=1)
-        e0.record()
-        for _ in range(5):
+        # N=1: the same K device-resident steps through the three-stage pipeline as well (what a serving loop would run; the
+        # sequential region above is the one whose scan kernel is timed alone on the chip for the roofline)
+        piped_qps = None
+        if world == 1 and pipe is None:
+            from nlsh_amd.pipeline import QueryPipeline
+            alt = QueryPipeline(indexer, qb[0], k=k, hash_times=P, depth=3)
+            for i in range(warmup):
+                alt.submit(qb[i % B], seed=1000 + i)
+            alt.synchronize()
+            fence()
+            t0 = time.perf_counter()
+            for i in range(steps):
+                alt.submit(qb[i % B], seed=1000 + i)
+            alt.synchronize()
+            fence()
+            piped_qps = Q * steps / (time.perf_counter() - t0)
+            assert not alt.overflowed()
+            del alt
+
+        # candidates per launch of the timed device steps (untimed recomputation with the same batches and probe seeds)
+        sum_c, uniq_rows = [], []
+        tables = dict(indexer._max_tasks)          # task tables as the timed steps saw them
+        bucket_rows = (indexer.offsets[1:] - indexer.offsets[:-1]).long() if indexer.n_buckets else None
+        for i in range(steps):
+            sum_c.append(int(indexer.query_tensors(qb[i % B], k=k, hash_times=P, seed=1000 + i)[2].long().sum().item()))
+            # rows of the buckets the batch probes at all, each counted ONCE: what a schedule that shares a fetched row between the
+            # queries probing its bucket has to read at least (the bucket-major schedules' algorithmic bytes)
+            if bucket_rows is not None:
+                kk, nn = indexer.hash_device(qb[i % B], hash_times=P, seed=1000 + i)
+                pos = torch.searchsorted(indexer.uniq_keys, kk.clamp(min=int(indexer.uniq_keys[0]), max=int(indexer.uniq_keys[-1]))).clamp(max=indexer.n_buckets - 1)
+                hit = (indexer.uniq_keys[pos] == kk) & (torch.arange(kk.shape[1], device=dev)[None, :] < nn[:, None])
+                uniq_rows.append(int(bucket_rows[torch.unique(pos[hit])].sum().item()))
+            # every timed step (not only the last, whose status word was read above) fitted its task table
+            needed, tkey = int(indexer.last_status.cpu()[0]), indexer._last_tkey
+            assert tkey not in tables or needed <= tables[tkey], f"step {i}: {needed} tasks > table {tables[tkey]} inside the timed region"
+        sum_c_local = float(np.mean(sum_c))
+        unique_bytes = 4.0 * d * float(np.mean(uniq_rows)) if uniq_rows else 0.0
+        algo_bytes = 4.0 * d * sum_c_local
+        flops_per_pair = 3.0 * d if metric == "l2" else 2.0 * d      # (q-c), +eps, fma per element | one fma
+        algo_flops = flops_per_pair * sum_c_local
+        t_scan = scan_avg_ms * 1e-3
+
+        # encoder (MFMA) utilisation on this rank's corpus rows, and the device's measured HBM copy rate next to the spec peak
+        enc, copy_gbps = None, None
+        if world == 1:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             hashing.hash_device(shard, n=1)
-        e1.record()
-        torch.cuda.synchronize()
-        enc_ms = e0.elapsed_time(e1) / 5
-        dims_ = [d] + list(hidden) + [H]
-        flops = 2.0 * sum(a_ * b_ for a_, b_ in zip(dims_[:-1], dims_[1:])) * shard.shape[0]
-        enc = {"kernel": "encode_hash_kernel (fp32 MFMA 32x32x2, fused bits + keys)", "rows": int(shard.shape[0]), "ms": enc_ms,
-               "tflops": flops / (enc_ms * 1e-3) / 1e12, "peak_tflops": MFMA_F32_PEAK_TFLOPS,
-               "mfma_util": flops / (enc_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS}
-        src = torch.empty((1 << 28,), dtype=torch.float32, device=dev)      # 1 GiB read + 1 GiB written per copy
-        dst = torch.empty_like(src)
-        dst.copy_(src)
-        e0.record()
-        for _ in range(5):
+            e0.record()
+            for _ in range(5):
+                hashing.hash_device(shard, n=1)
+            e1.record()
+            torch.cuda.synchronize()
+            enc_ms = e0.elapsed_time(e1) / 5
+            dims_ = [d] + list(hidden) + [H]
+            flops = 2.0 * sum(a_ * b_ for a_, b_ in zip(dims_[:-1], dims_[1:])) * shard.shape[0]
+            enc = {"kernel": "encode_hash_kernel (fp32 MFMA 32x32x2, fused bits + keys)", "rows": int(shard.shape[0]), "ms": enc_ms,
+                   "tflops": flops / (enc_ms * 1e-3) / 1e12, "peak_tflops": MFMA_F32_PEAK_TFLOPS,
+                   "mfma_util": flops / (enc_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS}
+            src = torch.empty((1 << 28,), dtype=torch.float32, device=dev)      # 1 GiB read + 1 GiB written per copy
+            dst = torch.empty_like(src)
             dst.copy_(src)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbps = 2.0 * src.numel() * 4 * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del src, dst
+            e0.record()
+            for _ in range(5):
+                dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_gbps = 2.0 * src.numel() * 4 * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del src, dst
 
-    # HBM traffic / VALU instruction counts per launch: PMC numbers cannot be collected from inside the process; they
-    # come from the committed rocprofv3 --pmc passes of this round (taken on the PROFILE box, same workload) when the
-    # workload matches, and are labelled as such.
-    traffic, valu_insts, clock_held, traffic_src, dram_bytes = (None,) * 5
-    if world == 1:
-        traffic, valu_insts, clock_held, traffic_src, dram_bytes = traffic_entry(
-            f"{args.workload}:{args.data}:{args.l2_form}", (N, d, Q, H, P, int(indexer.last_algo), int(indexer.last_window)), "learned" in hash_desc)
+        # HBM traffic / VALU instruction counts per launch: PMC numbers cannot be collected from inside the process; they
+        # come from the committed rocprofv3 --pmc passes (a profiling run of its own, same workload) when the
+        # workload matches, and are labelled as such.
+        traffic, valu_insts, clock_held, traffic_src, dram_bytes = (None,) * 5
+        if world == 1:
+            traffic, valu_insts, clock_held, traffic_src, dram_bytes = traffic_entry(
+                f"{args.workload}:{args.data}:{args.l2_form}", (N, d, Q, H, P, int(indexer.last_algo), int(indexer.last_window)), "learned" in hash_desc)
 
     result = None
     if rank == 0:
@@ -676,44 +716,6 @@ def main():
         mean_c = float(np.mean(nc0))
         value = Q * steps / elapsed
         algo = indexer.last_algo
-        kernel = {0: "scan_kernel (query-major)", 1: "bscan2_kernel (bucket-major, 8 queries in registers)",
-                  2: "bscan3_kernel (bucket-major, LDS-tiled)"}[algo] + " " + metric
-        if algo == _capi.SCAN_QUERY_MAJOR:
-            roof = {"bound": "hbm", "kernel": kernel, "achieved": algo_bytes / t_scan / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s"}
-            roof["frac"] = roof["achieved"] / roof["peak"]
-        else:
-            # The bucket-major schedules fetch a corpus row once per query GROUP, so SURVEY 8(d)'s per-pair bytes (4 d sum C_q) are not what
-            # they move (that rate is `algorithmic_GBps`, above the HBM peak on the headline).  Two roofs can bind them, both priced on
-            # ALGORITHMIC quantities measured live: fp32 vector issue on the 3 d (L2) / 2 d (cosine) flops per (query, candidate) pair, and
-            # HBM on the bytes of the DISTINCT candidate rows of the batch (each has to be read at least once).  `bound` is the one with
-            # the one with the clearly larger fraction (HBM needs 1.5x the VALU fraction to be named: where the two are close -- the skewed
-            # headline, 0.23 vs 0.25 -- the ablations of DESIGN.md appendix A show that arithmetic issue binds, the traffic is 0.7 GB per
-            # launch); the balanced hashes with tiny buckets stream (nearly) the whole corpus once per batch and are HBM-side.
-            valu_frac = algo_flops / t_scan / 1e12 / VALU_F32_PEAK_TFLOPS
-            hbm_frac = unique_bytes / t_scan / 1e9 / HBM_PEAK_GBPS
-            if 1.5 * valu_frac >= hbm_frac:
-                roof = {"bound": "valu", "kernel": kernel, "achieved": algo_flops / t_scan / 1e12, "peak": VALU_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": valu_frac}
-            else:
-                roof = {"bound": "hbm", "kernel": kernel, "achieved": unique_bytes / t_scan / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": hbm_frac}
-            roof.update({"valu_frac": valu_frac, "hbm_frac_of_distinct_candidate_rows": hbm_frac, "distinct_candidate_row_bytes_per_launch": unique_bytes,
-                         "note": "bucket-major schedules share a fetched row between the queries of a group: bound = (pair flops / fp32 vector peak) unless (bytes of the "
-                                 "batch's distinct candidate rows / HBM peak) is more than 1.5x that fraction; both algorithmic and measured live, both reported; the contract's "
-                                 "'mfma' slot does not apply (the distance math is VALU by design, north_star keeps MFMA for the encoder)"})
-        roof.update({"traffic": traffic, "traffic_source": traffic_src, "avg_launch_ms": scan_avg_ms,
-                     "algorithmic_bytes_per_launch": algo_bytes, "algorithmic_GBps": algo_bytes / t_scan / 1e9,
-                     "algorithmic_flops_per_launch": algo_flops, "sum_candidates_per_launch": sum_c_local, "tasks_per_launch": n_tasks})
-        if traffic:
-            roof["hbm_frac_of_measured_traffic"] = traffic / t_scan / 1e9 / HBM_PEAK_GBPS
-        if dram_bytes is not None:     # where the bytes come from, as far as the pool's counters go (profiles/traffic_r06.json: `origin`)
-            roof["traffic_origin"] = dram_bytes
-        if valu_insts:
-            roof["valu_wave_instructions_per_launch"] = valu_insts
-            roof["valu_issue_frac"] = valu_insts * 2.0 / (1024 * t_scan * 2.4e9)
-            if clock_held:   # the chip holds less than 2.4 GHz in this kernel: the same fraction at that clock
-                roof["clock_held_GHz"] = clock_held
-                roof["valu_issue_frac_at_clock_held"] = valu_insts * 2.0 / (1024 * t_scan * clock_held * 1e9)
-        if copy_gbps is not None:
-            roof["hbm_copy_measured_GBps"] = copy_gbps
         result = {
             "metric": "queries/sec + recall@10, SIFT1M 128-d 16-bit hash, 1/2/4/8 GPU" if args.workload == "sift1m" else
                       "queries/sec + recall@10 (GloVe-1.2M 100-d cosine 24-bit: BASELINE.json configs[2], not the headline)",
@@ -722,25 +724,15 @@ def main():
             "dtype": "f32", "data": "real" if args.dataset else "synthetic",
             "recall_at_10": recall,
             "value_protocol": "Indexer.query(batch, k, hash_times) -> Python lists of ALL Q queries on the calling rank, K synchronous calls "
-                              "(nlsh/trainers/base.py:93-96), the facade's DEFAULT settings: what an unmodified Trainer.fit gets.  protocol_qps_opt_in is the same "
+                              "(nlsh/trainers/base.py:93-96), the facade's DEFAULT settings: what an unmodified Trainer.fit gets.  protocol_qps_opt_in (--full) is the same "
                               "region with Indexer.defer_result_release = Indexer.untracked_results = True (host-side opt-ins, INTEGRATION.md)" +
                               ("" if world == 1 else f"; sharded x{world}: every rank scans all queries over its shard, one all-gather + merge, every rank builds all Q "
                                "lists -- the call is host-bound (Python list construction, ~0.9 ms per 10^4 queries at N=1), so `value` is ~flat in N BY CONSTRUCTION; "
-                               "the figure that scales is named by scaling_value_key"),
-            "protocol_qps_opt_in": Q * steps / elapsed_opt_in,
-            # the field of THIS line a scaling study should read: device-resident steps (results left in HBM, incl. the all-gather + merge at N>1);
-            # predicted ceiling from the one-GPU emulation of the per-rank pipelined local step (profiles/r06_shard_step_profile_pipelined.jsonl:
-            # 0.302 / 0.169 / 0.106 / 0.076 ms at 1 / 2 / 4 / 8 bucket shards, host enqueue 0.02 ms per batch through graph slots):
-            # encode + lookup, the task layout and the merge are replicated on every rank
-            "scaling_value_key": "device_resident_qps",
-            "scaling_ceiling_note": "per-rank pipelined local step emulated on one GPU (graph slots, profiles/r06_shard_step_profile_pipelined.jsonl): 0.302 / 0.169 / 0.106 / 0.076 ms = x1.8 / x2.85 / x4.0 at N = 2 / 4 / 8 before the all-gather (the ~70 us of encode + lookup, task layout and merge every rank repeats; host enqueue 0.02 ms per batch)",
-            "own_slice_qps": None if elapsed_own is None else Q * steps / elapsed_own,
+                               "the figure that scales is named by scaling_value_key (--full)"),
             # N>1 only: the exchange as the data backend itself saw it (ranks counted by an all-reduce of ones, devices by an all-gather of PCI ids)
             "collective": collective,
             "protocol_median_qps": Q / float(np.median(call_s)),
             "protocol_call_ms": [round(1e3 * c, 3) for c in call_s],
-            "device_resident_qps": Q * steps / elapsed_dev, "device_resident_ms_per_step": 1e3 * elapsed_dev / steps,
-            "device_resident_pipelined_qps": piped_qps,
             # the five quantities the reference's validation logs (nlsh/trainers/base.py:87-90,105-108), same names
             "test_metrics": {"test/n_indexes": stats["n_indexes"], "test/std_index_rows": stats["std_index_rows"], "test/recall": recall,
                              "test/query_size": mean_c, "test/qps": Q * steps / elapsed},
@@ -748,37 +740,90 @@ def main():
                        "hash": hash_desc, "l2_form": args.l2_form if metric == "l2" else None, "window_rows": int(indexer.last_window),
                        "shape": {"N": N, "d": d, "Q": Q, "H": H, "hash_times": P, "algo": int(algo), "window_rows": int(indexer.last_window)},
                        "traffic_key": f"{args.workload}:{args.data}:{args.l2_form}",
-                       "parallelism": (f"corpus {args.shard} sharded x{world} ({indexer._candidate_vectors_gpu.shape[0]} rows on rank 0), "
-                                       f"all-gather of per-shard top-k + merge: {float(np.mean([a.elapsed_time(b) for a, b in ev_x])):.4f} ms/step"
+                       "parallelism": (f"corpus {args.shard} sharded x{world} ({indexer._candidate_vectors_gpu.shape[0]} rows on rank 0)"
                                        ) if world > 1 else "single GPU",
                        "n_buckets": stats["n_indexes"], "bucket_mean": stats["mean"], "bucket_median": stats["median"],
-                       "bucket_max": stats["max"], "mean_candidates_per_query": mean_c, "index_build_s": build_s, "index_rebuild_s": rebuild_s,
-                       "device_step_driver": (("graph slots: every batch one captured hipGraph on its slot's own stream (nlsh_amd/pipeline.py)" if graph_slots else
-                                               "three-stage pipeline over three HIP streams (nlsh_amd/pipeline.py)") if pipe is not None
-                                              else "sequential: every kernel of a step back to back on one stream")},
-            "roofline": roof,
+                       "bucket_max": stats["max"], "mean_candidates_per_query": mean_c, "index_build_s": build_s, "index_rebuild_s": rebuild_s},
         }
-        if folded is not None and folded["algo"] == _capi.SCAN_BUCKET_TILED:
-            result["l2_folded_opt_in"] = {
-                "form": "sqrt(sum(((q + 1e-6) - c)^2)): Indexer(l2_form='folded') / NLSH_METRIC_L2_EPS_FOLDED; |d - d_exact| <= 1e-4 * max(1, d), not "
-                        "bit-identical to the oracle, NOT what value / roofline above measure",
-                "avg_launch_ms": folded["scan_avg_ms"], "achieved": algo_flops / (folded["scan_avg_ms"] * 1e-3) / 1e12, "unit": "TFLOP/s",
-                "frac_of_valu_peak_on_the_same_algorithmic_flops": algo_flops / (folded["scan_avg_ms"] * 1e-3) / 1e12 / VALU_F32_PEAK_TFLOPS,
-                "device_resident_ms_per_step": folded["device_resident_ms_per_step"], "device_resident_qps": folded["device_resident_qps"],
-                "id_lists_differing_from_exact": folded["id_lists_differing"], "of_queries": Q, "max_rel_distance_diff_vs_exact": folded["max_rel_distance_diff"],
-                "full_line": "python bench.py --l2-form folded prints the complete line (value, roofline, recall) measured on this form"}
-        if enc is not None:
-            result["encoder"] = enc
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(args, corpus_h, batches_h[0], Ws, bs, indexer, qb[0], metric)
-        side_ok = (world == 1 and not args.no_side_workloads and args.workload == "sift1m" and args.data == "manifold" and not args.dataset
-                   and not args.n and not args.dim and not args.hash_size and args.l2_form == "exact" and args.algo is None and args.window is None)
-        if side_ok:
-            # the other two workloads the round's numbers are quoted on, driver-run like the headline; `folded` is
-            # `l2_folded_opt_in` above (the headline's own index with the 2-op L2 form)
-            del indexer, shard
-            torch.cuda.empty_cache()
-            result["workloads"] = {tag: side_workload(tag, args, dev) for tag in ("glove", "clusters")}
+        if args.full:
+            kernel = {0: "scan_kernel (query-major)", 1: "bscan2_kernel (bucket-major, 8 queries in registers)",
+                      2: "bscan3_kernel (bucket-major, LDS-tiled)"}[algo] + " " + metric
+            if algo == _capi.SCAN_QUERY_MAJOR:
+                roof = {"bound": "hbm", "kernel": kernel, "achieved": algo_bytes / t_scan / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s"}
+                roof["frac"] = roof["achieved"] / roof["peak"]
+            else:
+                # The bucket-major schedules fetch a corpus row once per query GROUP, so SURVEY 8(d)'s per-pair bytes (4 d sum C_q) are not what
+                # they move (that rate is `algorithmic_GBps`, above the HBM peak on the headline).  Two roofs can bind them, both priced on
+                # ALGORITHMIC quantities measured live: fp32 vector issue on the 3 d (L2) / 2 d (cosine) flops per (query, candidate) pair, and
+                # HBM on the bytes of the DISTINCT candidate rows of the batch (each has to be read at least once).  `bound` is the one with
+                # the one with the clearly larger fraction (HBM needs 1.5x the VALU fraction to be named: where the two are close -- the skewed
+                # headline, 0.23 vs 0.25 -- the ablations of DESIGN.md appendix A show that arithmetic issue binds, the traffic is 0.7 GB per
+                # launch); the balanced hashes with tiny buckets stream (nearly) the whole corpus once per batch and are HBM-side.
+                valu_frac = algo_flops / t_scan / 1e12 / VALU_F32_PEAK_TFLOPS
+                hbm_frac = unique_bytes / t_scan / 1e9 / HBM_PEAK_GBPS
+                if 1.5 * valu_frac >= hbm_frac:
+                    roof = {"bound": "valu", "kernel": kernel, "achieved": algo_flops / t_scan / 1e12, "peak": VALU_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": valu_frac}
+                else:
+                    roof = {"bound": "hbm", "kernel": kernel, "achieved": unique_bytes / t_scan / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": hbm_frac}
+                roof.update({"valu_frac": valu_frac, "hbm_frac_of_distinct_candidate_rows": hbm_frac, "distinct_candidate_row_bytes_per_launch": unique_bytes,
+                             "note": "bucket-major schedules share a fetched row between the queries of a group: bound = (pair flops / fp32 vector peak) unless (bytes of the "
+                                     "batch's distinct candidate rows / HBM peak) is more than 1.5x that fraction; both algorithmic and measured live, both reported; the contract's "
+                                     "'mfma' slot does not apply (the distance math is VALU by design, north_star keeps MFMA for the encoder)"})
+            roof.update({"traffic": traffic, "traffic_source": traffic_src, "avg_launch_ms": scan_avg_ms,
+                         "algorithmic_bytes_per_launch": algo_bytes, "algorithmic_GBps": algo_bytes / t_scan / 1e9,
+                         "algorithmic_flops_per_launch": algo_flops, "sum_candidates_per_launch": sum_c_local, "tasks_per_launch": n_tasks})
+            if traffic:
+                roof["hbm_frac_of_measured_traffic"] = traffic / t_scan / 1e9 / HBM_PEAK_GBPS
+            if dram_bytes is not None:     # where the bytes come from, as far as the hardware counters go (profiles/traffic_r06.json: `origin`)
+                roof["traffic_origin"] = dram_bytes
+            if valu_insts:
+                roof["valu_wave_instructions_per_launch"] = valu_insts
+                roof["valu_issue_frac"] = valu_insts * 2.0 / (1024 * t_scan * 2.4e9)
+                if clock_held:   # the chip holds less than 2.4 GHz in this kernel: the same fraction at that clock
+                    roof["clock_held_GHz"] = clock_held
+                    roof["valu_issue_frac_at_clock_held"] = valu_insts * 2.0 / (1024 * t_scan * clock_held * 1e9)
+            if copy_gbps is not None:
+                roof["hbm_copy_measured_GBps"] = copy_gbps
+            result.update({
+                "protocol_qps_opt_in": Q * steps / elapsed_opt_in,
+                # the field of THIS line a scaling study should read: device-resident steps (results left in HBM, incl. the all-gather + merge at N>1);
+                # predicted ceiling from the one-GPU emulation of the per-rank pipelined local step (profiles/r06_shard_step_profile_pipelined.jsonl:
+                # 0.302 / 0.169 / 0.106 / 0.076 ms at 1 / 2 / 4 / 8 bucket shards, host enqueue 0.02 ms per batch through graph slots):
+                # encode + lookup, the task layout and the merge are replicated on every rank
+                "scaling_value_key": "device_resident_qps",
+                "scaling_ceiling_note": "per-rank pipelined local step emulated on one GPU (graph slots, profiles/r06_shard_step_profile_pipelined.jsonl): 0.302 / 0.169 / 0.106 / 0.076 ms = x1.8 / x2.85 / x4.0 at N = 2 / 4 / 8 before the all-gather (the ~70 us of encode + lookup, task layout and merge every rank repeats; host enqueue 0.02 ms per batch)",
+                "own_slice_qps": None if elapsed_own is None else Q * steps / elapsed_own,
+                "device_resident_qps": Q * steps / elapsed_dev, "device_resident_ms_per_step": 1e3 * elapsed_dev / steps,
+                "device_resident_pipelined_qps": piped_qps,
+                "roofline": roof,
+            })
+            if world > 1:
+                result["config"]["parallelism"] += (f", all-gather of per-shard top-k + merge: "
+                                                    f"{float(np.mean([a.elapsed_time(b) for a, b in ev_x])):.4f} ms/step")
+            result["config"]["device_step_driver"] = (("graph slots: every batch one captured hipGraph on its slot's own stream (nlsh_amd/pipeline.py)"
+                                                       if graph_slots else "three-stage pipeline over three HIP streams (nlsh_amd/pipeline.py)")
+                                                      if pipe is not None else "sequential: every kernel of a step back to back on one stream")
+            if folded is not None and folded["algo"] == _capi.SCAN_BUCKET_TILED:
+                result["l2_folded_opt_in"] = {
+                    "form": "sqrt(sum(((q + 1e-6) - c)^2)): Indexer(l2_form='folded') / NLSH_METRIC_L2_EPS_FOLDED; |d - d_exact| <= 1e-4 * max(1, d), not "
+                            "bit-identical to the oracle, NOT what value / roofline above measure",
+                    "avg_launch_ms": folded["scan_avg_ms"], "achieved": algo_flops / (folded["scan_avg_ms"] * 1e-3) / 1e12, "unit": "TFLOP/s",
+                    "frac_of_valu_peak_on_the_same_algorithmic_flops": algo_flops / (folded["scan_avg_ms"] * 1e-3) / 1e12 / VALU_F32_PEAK_TFLOPS,
+                    "device_resident_ms_per_step": folded["device_resident_ms_per_step"], "device_resident_qps": folded["device_resident_qps"],
+                    "id_lists_differing_from_exact": folded["id_lists_differing"], "of_queries": Q, "max_rel_distance_diff_vs_exact": folded["max_rel_distance_diff"],
+                    "full_line": "python bench.py --l2-form folded prints the complete line (value, roofline, recall) measured on this form"}
+            if enc is not None:
+                result["encoder"] = enc
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(args, corpus_h, batches_h[0], Ws, bs, indexer, qb[0], metric)
+            side_ok = (world == 1 and not args.no_side_workloads and args.workload == "sift1m" and args.data == "manifold" and not args.dataset
+                       and not args.n and not args.dim and not args.hash_size and args.l2_form == "exact" and args.algo is None and args.window is None)
+            if side_ok:
+                # the other two workloads the round's numbers are quoted on, driver-run like the headline; `folded` is
+                # `l2_folded_opt_in` above (the headline's own index with the 2-op L2 form)
+                del indexer, shard
+                torch.cuda.empty_cache()
+                result["workloads"] = {tag: side_workload(tag, args, dev) for tag in ("glove", "clusters")}
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

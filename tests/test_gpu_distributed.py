@@ -108,14 +108,14 @@ def test_two_rank_sharded_pipeline_equals_single_index(tmp_path, shard):
 
 
 def test_bench_gpus_2_self_launch_reports_two_ranks():
-    """`python bench.py --gpus 2` with no launcher around it: bench.py starts the two ranks itself (rehearsal mode: gloo
+    """`python bench.py --gpus 2 --full` with no launcher around it: bench.py starts the two ranks itself (rehearsal mode: gloo
     rendezvous, both ranks on cuda:0 since the box has one GPU) and rank 0 prints ONE JSON line with n_gpus == 2."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NLSH_BENCH_SAME_DEVICE="1", NLSH_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "60000", "--q", "1000", "--steps", "3", "--warmup", "1",
-           "--batches", "2", "--no-cpu-baseline"]
+           "--batches", "2", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -203,12 +203,12 @@ def _bench_env():
 # without the GPU below, and the 8-rank collectives of the build-time exchange and the merge run on gloo/CPU in tests/test_distributed_cpu.py.
 @pytest.mark.parametrize("exchange", ["auto", "allgather"])
 def test_bench_gpus_4_same_device_rehearsal(exchange):
-    """`python bench.py --gpus 4 --steps 2 --no-cpu-baseline` self-launched (gloo rendezvous, all ranks on cuda:0): the whole N>1 driver
+    """`python bench.py --gpus 4 --steps 2 --no-cpu-baseline --full` self-launched (gloo rendezvous, all ranks on cuda:0): the whole N>1 driver
     path -- bucket-sharded build with either exchange mode, protocol regions incl. own_slice, pipelined device-resident region with the
     all-gather + merge in its tail, rank 0's line -- with recall and candidate counts equal to the N=1 line's."""
     import json
     import subprocess
-    common = ["--n", "80000", "--q", "1200", "--steps", "2", "--warmup", "1", "--batches", "2", "--no-cpu-baseline"]
+    common = ["--n", "80000", "--q", "1200", "--steps", "2", "--warmup", "1", "--batches", "2", "--no-cpu-baseline", "--full"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--exchange", exchange] + common,
                          env=_bench_env(), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -420,6 +420,35 @@ def test_bench_runs_on_real_files_given_as_a_texmex_directory(tmp_path):
     assert abs(rec["recall_at_10"] - float(np.mean(calculate_recall(list(gt[:, :10]), ids)))) < 1e-12
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times --steps protocol steps and prints the headline line without the --full fields;
+    `--dump-outputs DIR` writes the lists of the last timed step, and two runs with the same arguments write the same arrays."""
+    N, Q, k = 50000, 800, 10
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(N), "--q", str(Q), "--steps", "3", "--warmup", "1", "--batches", "2"]
+    recs = []
+    for run in ("a", "b"):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        recs.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and len(rec["protocol_call_ms"]) == 3
+    assert rec["unit"] == "queries/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32" and rec["value"] > 0
+    assert abs(rec["ms_per_step"] - 1e3 * Q / rec["value"]) <= 1e-9 * rec["ms_per_step"]
+    assert 0.0 <= rec["recall_at_10"] <= 1.0 and rec["recall_at_10"] == recs[1]["recall_at_10"]
+    assert not {"roofline", "device_resident_qps", "protocol_qps_opt_in", "encoder", "cpu_baseline", "workloads"} & set(rec)
+    arrs = {}
+    for name in ("ids", "n_candidates", "query_rows"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+        arrs[name] = a
+    ids, nc = arrs["ids"], arrs["n_candidates"]
+    assert ids.shape == (Q, k) and nc.shape == (Q,) and np.array_equal(arrs["query_rows"], np.arange(Q))
+    assert ((ids >= -1) & (ids < N) & (ids == np.round(ids))).all() and (nc >= 0).all()
+    n_ids = (ids >= 0).sum(1)
+    assert (ids[np.arange(k)[None, :] >= n_ids[:, None]] == -1).all()          # -1 only past the end of a list
+    assert ((n_ids == k) | (nc < k)).all() and (n_ids > 0).any()               # short lists only where C_q < k
+
+
 def test_train_hash_tool_on_a_texmex_directory(tmp_path):
     """tools/train_hash.py --dataset: the minimal triplet trainer (N2) on files read through the dataset classes (N4); the checkpoint it
     writes loads back through io.load_hasher_weights and its validation history went through the HIP Indexer."""

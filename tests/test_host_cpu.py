@@ -215,6 +215,28 @@ def test_bench_gpus_n_launches_n_ranks_or_fails(tmp_path):
     assert one.returncode == 0 and json.loads(one.stdout.splitlines()[-1])["n_gpus"] == 1
 
 
+def test_bench_dump_outputs_pads_short_lists_and_samples_above_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's lists as float64 arrays, -1 past a short list; above the size limit a fixed, seeded
+    sample of the queries, the same one every time, with the rows it took."""
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))   # restored after the test
+    import bench
+    assert bench.parse([]).full is False and bench.parse([]).dump_outputs is None
+    ids, nc = [[5, 3, 9], [], [1, 2, 3, 4], [7]], [3, 0, 12, 1]
+    bench.dump_outputs(str(tmp_path / "all"), ids, nc, 4)
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("ids", "n_candidates", "query_rows")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["ids"].tolist() == [[5, 3, 9, -1], [-1] * 4, [1, 2, 3, 4], [7, -1, -1, -1]]
+    assert got["n_candidates"].tolist() == nc and got["query_rows"].tolist() == [0, 1, 2, 3]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 8 * (4 + 2))                # room for two of the four queries
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), ids, nc, 4)
+    rows = np.load(tmp_path / "s1" / "query_rows.npy")
+    assert len(rows) == 2 and np.array_equal(rows, np.load(tmp_path / "s2" / "query_rows.npy")) and np.all(np.diff(rows) > 0)
+    sampled = np.load(tmp_path / "s1" / "ids.npy")
+    assert sampled.tolist() == [got["ids"][int(r)].tolist() for r in rows]
+    assert np.load(tmp_path / "s1" / "n_candidates.npy").tolist() == [nc[int(r)] for r in rows]
+
+
 def test_result_lists_skip_the_young_generation_and_full_collections_still_happen():
     """`Indexer._plain_lists` with the OPT-IN promotion on: the fresh lists are promoted past the collector's young
     generations (no collection is triggered by them), the application's own frozen objects are respected, and cyclic

@@ -14,16 +14,16 @@ PMC="FETCH_SIZE SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_C
 pmc_bench() {   # $1 = tag, rest = bench.py flags: counters of the bench command in their own pass (no tracing domains beside --pmc)
   tag=$1; shift
   rm -rf /tmp/pm_$tag
-  (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc $PMC --output-format csv -d /tmp/pm_$tag -- python3 $R/bench.py --no-cpu-baseline --no-side-workloads --steps 3 --warmup 1 --query-chunks 1 "$@" > $O/pmc_${tag}_line.json 2> /tmp/pm_$tag.err)
+  (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc $PMC --output-format csv -d /tmp/pm_$tag -- python3 $R/bench.py --full --no-cpu-baseline --no-side-workloads --steps 3 --warmup 1 --query-chunks 1 "$@" > $O/pmc_${tag}_line.json 2> /tmp/pm_$tag.err)
   python3 $R/tools/pmc_summary.py /tmp/pm_$tag > $O/pmc_$tag.json
 }
 if [ "${1:-main}" = "main" ] || [ "$1" = "lines" ]; then
   python -m pytest tests -m gpu -q -x 2>&1 | tail -2 > $O/tests.txt
-  python bench.py > $O/bench.json 2> $O/bench.err
-  python bench.py --l2-form folded --no-cpu-baseline > $O/bench_folded.json 2>/dev/null
-  python bench.py --data clusters --no-cpu-baseline > $O/bench_clusters.json 2>/dev/null
-  python bench.py --workload glove --no-cpu-baseline > $O/bench_glove.json 2>/dev/null
-  python bench.py --workload glove --no-cpu-baseline --algo query > $O/bench_glove_query_major.json 2>/dev/null
+  python bench.py --full > $O/bench.json 2> $O/bench.err
+  python bench.py --full --l2-form folded --no-cpu-baseline > $O/bench_folded.json 2>/dev/null
+  python bench.py --full --data clusters --no-cpu-baseline > $O/bench_clusters.json 2>/dev/null
+  python bench.py --full --workload glove --no-cpu-baseline > $O/bench_glove.json 2>/dev/null
+  python bench.py --full --workload glove --no-cpu-baseline --algo query > $O/bench_glove_query_major.json 2>/dev/null
   for w in 1 2 4 8; do python tools/shard_step_profile.py --world $w --rank 0 --steps 50; done 2>/dev/null > $O/shard_step_profile_sequential.jsonl
   for g in on off; do for w in 1 2 4 8; do python tools/shard_step_profile.py --world $w --rank 0 --steps 100 --pipeline --graph $g; done; done 2>/dev/null > $O/shard_step_profile_pipelined.jsonl
   python tools/graph_enqueue_probe.py 2>/dev/null > $O/graph_enqueue_probe.json
@@ -37,7 +37,7 @@ if [ "${1:-main}" = "main" ] || [ "$1" = "counters" ]; then
     CLK=$(grep -oE 'clock median [0-9.]+' $O/scan_clock.txt | head -1 | awk '{print $3}')
   fi
   # per-kernel statistics of the bench command (one row range per query() call: every scan launch has the full-batch grid)
-  rm -rf /tmp/kt && (cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python3 $R/bench.py --no-cpu-baseline --no-side-workloads --query-chunks 1 > $O/bench_under_rocprof.json 2> /tmp/kt.err)
+  rm -rf /tmp/kt && (cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python3 $R/bench.py --full --no-cpu-baseline --no-side-workloads --query-chunks 1 > $O/bench_under_rocprof.json 2> /tmp/kt.err)
   cp $(find /tmp/kt -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
   python3 $R/tools/kernel_trace_regions.py /tmp/kt > $O/kernel_trace_regions.txt
   : > $O/step_timeline.txt
@@ -48,7 +48,7 @@ if [ "${1:-main}" = "main" ] || [ "$1" = "counters" ]; then
   done
   for wl in glove clusters; do
     flags="--workload glove"; [ $wl = clusters ] && flags="--data clusters"
-    rm -rf /tmp/kt_$wl && (cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$wl -- python3 $R/bench.py --no-cpu-baseline --query-chunks 1 $flags > $O/bench_${wl}_under_rocprof.json 2> /tmp/kt_$wl.err)
+    rm -rf /tmp/kt_$wl && (cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$wl -- python3 $R/bench.py --full --no-cpu-baseline --query-chunks 1 $flags > $O/bench_${wl}_under_rocprof.json 2> /tmp/kt_$wl.err)
     cp $(find /tmp/kt_$wl -name '*kernel_stats.csv' | head -1) $O/${wl}_kernel_stats.csv
   done
   pmc_bench sift1m
@@ -57,7 +57,7 @@ if [ "${1:-main}" = "main" ] || [ "$1" = "counters" ]; then
   pmc_bench glove --workload glove
   # what the L2's fabric-side read requests of the GloVe launch are made of: all of them, those routed to local DRAM (as opposed to
   # GMI / IO -- NOT "missed the Infinity Cache": no counter of this rocprofv3 sits behind the MALL), the 32-byte ones
-  rm -rf /tmp/pm_ea && (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d /tmp/pm_ea -- python3 $R/bench.py --no-cpu-baseline --no-side-workloads --steps 3 --warmup 1 --query-chunks 1 --workload glove > /dev/null 2> /tmp/pm_ea.err) || true
+  rm -rf /tmp/pm_ea && (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d /tmp/pm_ea -- python3 $R/bench.py --full --no-cpu-baseline --no-side-workloads --steps 3 --warmup 1 --query-chunks 1 --workload glove > /dev/null 2> /tmp/pm_ea.err) || true
   python3 $R/tools/pmc_summary.py /tmp/pm_ea bscan3 > $O/pmc_glove_ea_requests.json || true
   python3 tools/make_traffic.py --entry $O/pmc_sift1m.json:$O/pmc_sift1m_line.json${CLK:+:$CLK} --entry $O/pmc_sift1m_folded.json:$O/pmc_sift1m_folded_line.json \
       --entry $O/pmc_clusters.json:$O/pmc_clusters_line.json --entry $O/pmc_glove.json:$O/pmc_glove_line.json \

@@ -5,10 +5,10 @@ R=$PWD; O=$R/gpurun_out/r06c; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/tests.txt 2>&1 || { tail -30 $O/tests.txt; exit 1; }
 tail -2 $O/tests.txt
 t0=$(date +%s)
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "default bench.py wall seconds: $(( $(date +%s) - t0 ))" | tee $O/bench_wall.txt
-timeout -k 10 300 python bench.py --workload glove --no-cpu-baseline > $O/bench_glove.json 2>/dev/null
-timeout -k 10 300 python bench.py --data clusters --no-cpu-baseline > $O/bench_clusters.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --workload glove --no-cpu-baseline > $O/bench_glove.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --data clusters --no-cpu-baseline > $O/bench_clusters.json 2>/dev/null
 (cd /tmp && TMPDIR=/tmp timeout -k 10 120 rocprofv3 --list-avail > $O/rocprof_list_avail.txt 2>&1) || true
 python - <<'PY'
 import json
