@@ -60,6 +60,7 @@ enum { NLSH_SCAN_QUERY_MAJOR = 0, NLSH_SCAN_BUCKET_MAJOR = 1, NLSH_SCAN_BUCKET_T
 #define NLSH_MAX_K 64
 #define NLSH_MAX_DIM 1024   /* vector dimension of corpus / queries for the scan */
 #define NLSH_MAX_WIDTH 632  /* widest HIDDEN encoder layer the LDS-resident MLP supports (the input may be NLSH_MAX_DIM wide) */
+#define NLSH_MAX_STREAM_WIDTH 4096  /* widest HIDDEN encoder layer of the streamed form (nlsh_encode_hash_stream) */
 
 int nlsh_abi_version(void);
 const char *nlsh_last_error(void);
@@ -93,11 +94,39 @@ int nlsh_encoder_pack(int n_layers, const int *dims, const float *const *W, cons
  * Probes 1..n_probes-1 are Bernoulli(p) draws from a Philox4x32-10 stream keyed by `seed`,
  * counter (row0 + row, probe, word): reproducible across devices and ranks.  Rows with index
  * >= n_multi_rows are single-probe (Indexer.hash's trailing-batch rule, nlsh/indexer.py:51-53).
- * Limits: H <= 32, n_probes <= NLSH_MAX_ENCODE_PROBES, dims[0] <= NLSH_MAX_DIM, hidden dims[l] <= NLSH_MAX_WIDTH. */
+ * Limits: H <= 32, n_probes <= NLSH_MAX_ENCODE_PROBES, dims[0] <= NLSH_MAX_DIM, hidden dims[l] <= NLSH_MAX_WIDTH
+ * (wider hidden layers: nlsh_encode_hash_stream below). */
 int nlsh_encode_hash(const float *x, int64_t n, int64_t x_stride, int n_layers, const int *dims,
                      const float *packed, int act, int key_mode, int n_probes, int64_t n_multi_rows,
                      uint64_t seed, int64_t row0, float *z_out, float *probs_out, uint32_t *code_out,
                      int32_t *keys_out, int32_t *nkeys_out, nlsh_stream_t stream);
+
+/* The streamed form: the same function for encoders with hidden layers up to NLSH_MAX_STREAM_WIDTH wide (narrow ones too).
+ * The LDS-resident form above keeps a row's whole activation on chip, which bounds a hidden layer at NLSH_MAX_WIDTH; here the
+ * activations of a block of rows live in `workspace` between layers: one fp32-MFMA GEMM launch per Linear layer (one k-ascending
+ * chain per output element from 0, bias, then ReLU: z is the same bits as nlsh_encode_hash's and the oracle's), then the epilogue
+ * of nlsh_encode_hash (sigmoid / tanh, bits, packing, Philox probes, de-duplication) on z.  Pipelined batch slots
+ * (nlsh_step_*, nlsh_query_batch) take LDS-resident encoders only.
+ * Limits: H <= 32, n_probes <= NLSH_MAX_ENCODE_PROBES, dims[0] <= NLSH_MAX_DIM, hidden dims[l] <= NLSH_MAX_STREAM_WIDTH. */
+
+/* Floats of the streamed form's blob (its own layout; -1 if the shape is outside the limits above). */
+int64_t nlsh_encoder_stream_packed_floats(int n_layers, const int *dims);
+
+/* nlsh_encoder_pack for the streamed form: same arguments, `packed` sized by nlsh_encoder_stream_packed_floats. */
+int nlsh_encoder_stream_pack(int n_layers, const int *dims, const float *const *W, const float *const *b,
+                             float *packed, nlsh_stream_t stream);
+
+/* Workspace bytes of a pass of `rows_per_pass` rows (rounded up to the 128-row tile; 0 for a shape outside the limits). */
+size_t nlsh_encode_stream_workspace(int64_t rows_per_pass, int n_layers, const int *dims);
+
+/* nlsh_encode_hash's arguments and outputs, with the streamed blob, plus workspace [dev] (16-byte aligned) of workspace_bytes:
+ * the rows are processed in passes of as many 128-row tiles as the workspace holds (at least one: NLSH_E_WORKSPACE otherwise);
+ * the outputs do not depend on that size. */
+int nlsh_encode_hash_stream(const float *x, int64_t n, int64_t x_stride, int n_layers, const int *dims,
+                            const float *packed, int act, int key_mode, int n_probes, int64_t n_multi_rows,
+                            uint64_t seed, int64_t row0, float *z_out, float *probs_out, uint32_t *code_out,
+                            int32_t *keys_out, int32_t *nkeys_out, void *workspace, size_t workspace_bytes,
+                            nlsh_stream_t stream);
 
 /* Standalone bit packing: codes [dev] int32 [B, n, H] (0/1, C-contiguous) -> keys_out [dev] int32
  * [B, n].  Replaces binarr_to_int + the inner loop of hash_codes (nlsh/utils.pyx:6-15, 22-31);

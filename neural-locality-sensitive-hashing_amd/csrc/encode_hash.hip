@@ -23,6 +23,9 @@
 //     S = width+4 floats with S/4 odd makes those reads conflict-free;
 //   * bias + ReLU are fused into the accumulator write-back; sigmoid/tanh, the `> 0.5` bit rule,
 //     MSB-first packing, Philox Bernoulli probes and per-row de-duplication are the epilogue.
+//   * hidden layers wider than NLSH_MAX_WIDTH: the streamed form at the end of this file (a layer GEMM per Linear layer over a
+//     device workspace, then this epilogue on z).
+#include <algorithm>
 #include <atomic>
 
 #include "step_nodes.h"
@@ -103,7 +106,9 @@ extern "C" int nlsh_debug_enc_trace(float *host, int n_floats) { return (int)hip
 // the rows.  It IS the shorter critical path while there is at most one workgroup per CU: batches of <= 4096 rows (24.5 vs 27.2 us).
 // The workgroup body: rows [row_base, row_base + M) of the batch.  `blk` = the workgroup's index in the launch (its entry of the
 // lookup's `hits`; workgroup 0 does the batch's initialisation).
-template <int RT, int NW, bool SINGLE, int MT = 1, bool H16 = false>  // MT: column tiles a wave may own in SINGLE mode (1: width <= 32*NW)
+// ZIN (the streamed form's epilogue, encode_stream_epilogue_kernel): no staging and no layer loop -- z [rows][x_stride] is read from
+// a.x (the workspace the layer launches left it in) into the [M][33] image, and the epilogue below runs as it stands.
+template <int RT, int NW, bool SINGLE, int MT = 1, bool H16 = false, bool ZIN = false>  // MT: column tiles a wave may own in SINGLE mode (1: width <= 32*NW)
 __device__ __forceinline__ void encode_hash_body(const EncArgs &a, const PlanArgs &pa, float *smem, const long long row_base, const unsigned blk) {
     constexpr int M = H16 ? 16 * RT : 32 * RT;   // H16: RT row tiles of 16 sharing every B fragment (shipped: RT = 1; RT = 3 measured and dropped in r05)
     static_assert(!H16 || SINGLE, "the 16-row-tile form runs on a single LDS image");
@@ -127,7 +132,14 @@ __device__ __forceinline__ void encode_hash_body(const EncArgs &a, const PlanArg
 #endif
 
     // ---- stage the input rows (zero padded to Kp, zero rows past n) in the de-interleaved layout
-    {
+    if constexpr (ZIN) {
+        static_assert(SINGLE, "z is loaded into the single image");
+        for (int e = tid; e < M * a.H; e += NTH) {
+            const int r = e / a.H, h = e - r * a.H;
+            const long long grow = row_base + r;
+            out[r * 33 + h] = grow < a.n ? a.x[grow * a.x_stride + h] : 0.0f;
+        }
+    } else {
         const int K0 = a.L[0].K, Kp0 = a.L[0].Kp;
         const bool vec = ((K0 | (int)a.x_stride) & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
         if (vec) {
@@ -167,7 +179,7 @@ __device__ __forceinline__ void encode_hash_body(const EncArgs &a, const PlanArg
     __syncthreads();
     ENC_STAMP(1);
 
-    for (int l = 0; l < a.n_layers; ++l) {
+    for (int l = 0; l < (ZIN ? 0 : a.n_layers); ++l) {
         const LayerDesc L = a.L[l];
         const int nch = L.Kp >> 3;
         const float4 *Wp = reinterpret_cast<const float4 *>(a.packed + L.w_off);
@@ -961,4 +973,294 @@ extern "C" int nlsh_encode_hash(const float *x, int64_t n, int64_t x_stride, int
                               keys_out, nkeys_out);
     if (rc != NLSH_OK) return rc;
     return encode_plan_launch(p, x, x_stride, seed, (hipStream_t)stream);
+}
+
+// ================================================================================================================================
+// The streamed form (nlsh_encode_hash_stream): hidden layers up to NLSH_MAX_STREAM_WIDTH wide.  Every form above keeps a row's
+// whole activation in LDS, which bounds a hidden layer at NLSH_MAX_WIDTH; here activations live in a caller-owned workspace between
+// layers.  One pass over a block of rows = one launch of encode_layer_kernel per Linear layer + one of the shipped epilogue (ZIN).
+//   * encode_layer_kernel: out[r, j] = relu?(chain_k(in[r, k] * W[j, k]) + b[j]); a workgroup of 4 waves owns 128 rows x SL_BN
+//     columns, a wave RT x CT tiles of 32 x 32; v_mfma_f32_32x32x2_f32 over k ascending from 0, one chain per output element (no
+//     split-K), bias then ReLU after the chain: the arithmetic of the fused forms and of oracle_mlp_forward, so z is bit-exact;
+//   * A (rows x k) goes through LDS in slabs of SL_KS k, in the de-interleaved layout of pos() (one ds_read_b128 = the A operands
+//     of four k-steps), the next slab's global loads in flight under the current slab's MFMAs; B comes from the blob in the
+//     fragment order of pack_weights_kernel (one global_load_dwordx4 per lane per 8 k), three chunks ahead in a ring;
+//   * activations are stored [rows][WS] (WS = the widest hidden Np): the columns past a layer's width are exact zeros (zero weights,
+//     zero bias), so the next layer reads whole float4s; the output layer writes z [rows][32].
+namespace nlsh {
+
+constexpr int SL_KS = 64;            // k per LDS slab (8 chunks of 8)
+constexpr int SL_S = SL_KS + 4;      // LDS row stride: S / 4 odd -> conflict-free ds_read_b128
+constexpr int SL_BM = 128;           // rows per workgroup (a pass is a multiple of this)
+constexpr int SL_ZS = 32;            // row stride of the z buffer
+
+template <int RT, int CT, int WR, int WC, bool RELU>
+__global__ __launch_bounds__(WR * WC * 64) void encode_layer_kernel(const float *__restrict__ in, long long in_stride, int K, int Kp,
+                                                                    long long n, const float *__restrict__ Wp,
+                                                                    const float *__restrict__ bias, int Np, float *__restrict__ out,
+                                                                    long long out_stride) {
+    constexpr int NTH = WR * WC * 64, BM = WR * RT * 32, BN = WC * CT * 32;
+    static_assert(BM == SL_BM, "a pass is sized in SL_BM-row tiles");
+    constexpr int Q = SL_KS / 4, NV = BM * Q / NTH;   // float4 per slab row, float4 a thread stages per slab
+    __shared__ float4 As4[BM * SL_S / 4];
+    float *As = reinterpret_cast<float *>(As4);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int wr = wave % WR, wc = wave / WR;
+    const int ncb = (Np + BN - 1) / BN;
+    const long long rb = blockIdx.x / ncb;
+    const int cb = (int)(blockIdx.x - rb * ncb);
+    const long long row0 = rb * BM;
+    const int nch = Kp >> 3, nct = Np >> 5, nslab = (nch + SL_KS / 8 - 1) / (SL_KS / 8);
+
+    const float4 *w0[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int t = cb * (BN / 32) + wc * CT + ct;   // tiles past Np redo the last one (valid addresses), results dropped
+        w0[ct] = reinterpret_cast<const float4 *>(Wp) + (size_t)min(t, nct - 1) * nch * 64 + lane;
+    }
+    const bool vec = ((K | (int)in_stride) & 3) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    float4 v[NV];
+    auto load = [&](int s) {
+        const int k0 = s * SL_KS;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int e = i * NTH + tid, r = e / Q, k = k0 + 4 * (e % Q);
+            const long long grow = row0 + r;
+            const float *src = in + grow * in_stride + k;
+            if (vec) {
+                v[i] = (grow < n && k < K) ? *reinterpret_cast<const float4 *>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                const bool live = grow < n;
+                v[i].x = live && k < K ? src[0] : 0.0f;
+                v[i].y = live && k + 1 < K ? src[1] : 0.0f;
+                v[i].z = live && k + 2 < K ? src[2] : 0.0f;
+                v[i].w = live && k + 3 < K ? src[3] : 0.0f;
+            }
+        }
+    };
+
+    f32x16 acc[RT][CT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[rt][ct][i] = 0.0f;
+    float4 B[CT][4];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) B[ct][j] = w0[ct][(size_t)min(j, nch - 1) * 64];
+    const float *arow = As + (wr * RT * 32 + lr) * SL_S + 4 * lh;
+
+    load(0);
+    for (int s = 0; s < nslab; ++s) {
+        __syncthreads();   // every wave has finished reading the previous slab
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int e = i * NTH + tid, r = e / Q, q = e % Q;
+            float *dst = As + r * SL_S + ((4 * q) & ~7) + ((q & 1) << 1);   // pos(4q + j) = base + {0, 4, 1, 5}
+            dst[0] = v[i].x; dst[4] = v[i].y; dst[1] = v[i].z; dst[5] = v[i].w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SL_KS / 8; ++j) {
+            const int c = s * (SL_KS / 8) + j;
+            if (c < nch) {
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) B[ct][(j + 3) & 3] = w0[ct][(size_t)min(c + 3, nch - 1) * 64];
+                // the next slab's rows are requested behind the B fragment of chunk j + 3, so that the waits for chunks j + 1 .. j + 3
+                // (loads return in order) never wait for them
+                if (j == 4 && s + 1 < nslab) load(s + 1);
+                float4 av[RT];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) av[rt] = *reinterpret_cast<const float4 *>(arow + rt * 32 * SL_S + j * 8);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                        for (int ct = 0; ct < CT; ++ct) {
+                            const float aa = i == 0 ? av[rt].x : i == 1 ? av[rt].y : i == 2 ? av[rt].z : av[rt].w;
+                            const float bb = i == 0 ? B[ct][j & 3].x : i == 1 ? B[ct][j & 3].y : i == 2 ? B[ct][j & 3].z : B[ct][j & 3].w;
+                            acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(aa, bb, acc[rt][ct], 0, 0, 0);
+                        }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+
+    // bias (+ ReLU, encoders.py:19-20) after the chain; C/D map: col = lane & 31, row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5).
+    // One register of a tile is two 128-B row segments: plain vector stores at full rate.
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int col = cb * BN + (wc * CT + ct) * 32 + lr;
+        if (col < Np) {
+            const float bb = bias[col];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const long long row = row0 + (wr * RT + rt) * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh;
+                    if (row < n) {
+                        float val = acc[rt][ct][i] + bb;
+                        if (RELU) val = val > 0.0f ? val : 0.0f;
+                        out[row * out_stride + col] = val;
+                    }
+                }
+        }
+    }
+}
+
+// hidden layers: 2 x 2 waves of 2 x 2 tiles (128 rows x 128 columns); the output layer (Np = 32): four waves of one row tile each
+#define NLSH_LAYER_HIDDEN encode_layer_kernel<2, 2, 2, 2, true>
+#define NLSH_LAYER_OUT encode_layer_kernel<1, 1, 4, 1, false>
+constexpr int SL_BN_HIDDEN = 128, SL_BN_OUT = 32;
+
+// the shipped epilogue on z: 32-row workgroups of eight waves on one LDS image (the SINGLE form's geometry), no bucket lookup
+__global__ __launch_bounds__(512, 1) void encode_stream_epilogue_kernel(EncArgs a) {
+    extern __shared__ float4 smem4[];
+    PlanArgs pa{};
+    pa.enabled = 0; pa.prep_metric = -1;
+    encode_hash_body<1, 8, true, 1, false, true>(a, pa, reinterpret_cast<float *>(smem4), (long long)blockIdx.x * 32, blockIdx.x);
+}
+
+static int check_stream_dims(int n_layers, const int *dims) {
+    NLSH_REQUIRE(dims != nullptr && n_layers >= 1 && n_layers <= NLSH_MAX_LAYERS, NLSH_E_INVALID,
+                 "encoder (streamed): n_layers=%d out of range [1,%d]", n_layers, NLSH_MAX_LAYERS);
+    for (int l = 0; l <= n_layers; ++l) NLSH_REQUIRE(dims[l] >= 1, NLSH_E_INVALID, "encoder (streamed): dims[%d]=%d", l, dims[l]);
+    NLSH_REQUIRE(dims[0] <= NLSH_MAX_DIM, NLSH_E_UNSUPPORTED, "encoder (streamed): input width %d > %d", dims[0], NLSH_MAX_DIM);
+    for (int l = 1; l < n_layers; ++l)
+        NLSH_REQUIRE(dims[l] <= NLSH_MAX_STREAM_WIDTH, NLSH_E_UNSUPPORTED, "encoder (streamed): hidden width %d > %d", dims[l],
+                     NLSH_MAX_STREAM_WIDTH);
+    NLSH_REQUIRE(dims[n_layers] <= NLSH_MAX_HASH_BITS, NLSH_E_UNSUPPORTED, "encoder (streamed): hash_size %d > %d", dims[n_layers],
+                 NLSH_MAX_HASH_BITS);
+    return NLSH_OK;
+}
+
+// blob of the streamed form: every layer [Np/32 column tiles][Kp/8 chunks][64 lanes][4] (pack_weights_kernel), then its Np biases
+static long long fill_stream_layers(int n_layers, const int *dims, LayerDesc *L) {
+    long long off = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        L[l].K = dims[l]; L[l].N = dims[l + 1];
+        L[l].Kp = round_up(dims[l], 8); L[l].Np = round_up(dims[l + 1], 32);
+        L[l].w_off = off; off += (long long)L[l].Np * L[l].Kp;
+        L[l].b_off = off; off += L[l].Np;
+        L[l].w16_off = L[l].w_off;
+    }
+    return off;
+}
+
+// floats per row of a pass: `nbuf` activation images of WS floats, then z
+static void stream_row_floats(int n_layers, const int *dims, int *WS, int *nbuf, long long *per_row) {
+    int ws = 0;
+    for (int l = 1; l < n_layers; ++l) ws = std::max(ws, round_up(dims[l], 32));
+    *WS = ws;
+    *nbuf = std::min(2, n_layers - 1);
+    *per_row = (long long)*nbuf * ws + SL_ZS;
+}
+
+}  // namespace nlsh
+
+extern "C" int64_t nlsh_encoder_stream_packed_floats(int n_layers, const int *dims) {
+    if (check_stream_dims(n_layers, dims) != NLSH_OK) return -1;
+    LayerDesc L[NLSH_MAX_LAYERS];
+    return fill_stream_layers(n_layers, dims, L);
+}
+
+extern "C" int nlsh_encoder_stream_pack(int n_layers, const int *dims, const float *const *W, const float *const *b, float *packed,
+                                        nlsh_stream_t stream) {
+    int rc = check_stream_dims(n_layers, dims);
+    if (rc != NLSH_OK) return rc;
+    NLSH_REQUIRE(W != nullptr && b != nullptr && packed != nullptr, NLSH_E_INVALID, "encoder_stream_pack: null pointer");
+    LayerDesc L[NLSH_MAX_LAYERS];
+    fill_stream_layers(n_layers, dims, L);
+    for (int l = 0; l < n_layers; ++l) {
+        NLSH_REQUIRE(W[l] != nullptr, NLSH_E_INVALID, "encoder_stream_pack: W[%d] is null", l);
+        const long long tot = (long long)L[l].Np * L[l].Kp;
+        const int grid = (int)std::min((tot + 255) / 256, 4096ll);
+        hipLaunchKernelGGL(pack_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W[l], b[l], L[l].K, L[l].N, L[l].Kp,
+                           L[l].Np, packed + L[l].w_off, packed + L[l].b_off);
+        NLSH_CHECK_HIP(hipGetLastError());
+    }
+    return NLSH_OK;
+}
+
+extern "C" size_t nlsh_encode_stream_workspace(int64_t rows_per_pass, int n_layers, const int *dims) {
+    if (check_stream_dims(n_layers, dims) != NLSH_OK || rows_per_pass < 0) return 0;
+    int WS, nbuf;
+    long long per_row;
+    stream_row_floats(n_layers, dims, &WS, &nbuf, &per_row);
+    const long long rows = ((rows_per_pass < 1 ? 1 : rows_per_pass) + SL_BM - 1) / SL_BM * SL_BM;
+    return (size_t)(rows * per_row * 4);
+}
+
+extern "C" int nlsh_encode_hash_stream(const float *x, int64_t n, int64_t x_stride, int n_layers, const int *dims, const float *packed,
+                                       int act, int key_mode, int n_probes, int64_t n_multi_rows, uint64_t seed, int64_t row0,
+                                       float *z_out, float *probs_out, uint32_t *code_out, int32_t *keys_out, int32_t *nkeys_out,
+                                       void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+    int rc = check_stream_dims(n_layers, dims);
+    if (rc != NLSH_OK) return rc;
+    NLSH_REQUIRE(n >= 0, NLSH_E_INVALID, "encode_hash_stream: n=%lld", (long long)n);
+    NLSH_REQUIRE(act == NLSH_ACT_SIGMOID || act == NLSH_ACT_TANH, NLSH_E_INVALID, "encode_hash_stream: act=%d", act);
+    NLSH_REQUIRE(key_mode == NLSH_KEY_REF_INT16 || key_mode == NLSH_KEY_FULL, NLSH_E_INVALID, "encode_hash_stream: key_mode=%d", key_mode);
+    NLSH_REQUIRE(n_probes >= 1 && n_probes <= NLSH_MAX_ENCODE_PROBES, NLSH_E_INVALID, "encode_hash_stream: n_probes=%d not in [1,%d]",
+                 n_probes, NLSH_MAX_ENCODE_PROBES);
+    if (n == 0) return NLSH_OK;
+    NLSH_REQUIRE(x && packed && keys_out && nkeys_out && workspace, NLSH_E_INVALID, "encode_hash_stream: null pointer");
+    NLSH_REQUIRE(x_stride >= dims[0], NLSH_E_INVALID, "encode_hash_stream: x_stride %lld < d %d", (long long)x_stride, dims[0]);
+    NLSH_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, NLSH_E_INVALID, "encode_hash_stream: workspace not 16-byte aligned");
+    int WS, nbuf;
+    long long per_row;
+    stream_row_floats(n_layers, dims, &WS, &nbuf, &per_row);
+    const long long R = (long long)(workspace_bytes / ((size_t)per_row * 4)) / SL_BM * SL_BM;   // rows per pass
+    NLSH_REQUIRE(R >= SL_BM, NLSH_E_WORKSPACE, "encode_hash_stream: workspace %zu B < one %d-row tile (%lld B)", workspace_bytes, SL_BM,
+                 (long long)SL_BM * per_row * 4);
+    LayerDesc L[NLSH_MAX_LAYERS];
+    fill_stream_layers(n_layers, dims, L);
+    float *ws = static_cast<float *>(workspace);
+    float *buf[2] = {ws, ws + (nbuf > 1 ? R * WS : 0)};
+    float *zb = ws + (long long)nbuf * R * WS;
+    hipStream_t s = (hipStream_t)stream;
+
+    EncArgs a{};
+    a.x_stride = SL_ZS; a.n_layers = 0; a.packed = packed;
+    a.S = 72 + round_up(n_probes, 8) + 4;   // z, p and the key table side by side (the SINGLE form's epilogue image)
+    a.H = dims[n_layers]; a.act = act; a.key_mode = key_mode; a.n_probes = n_probes; a.seed = seed;
+    const size_t lds = (size_t)32 * a.S * 4;
+    for (long long p0 = 0; p0 < n; p0 += R) {
+        const long long np = std::min(R, (long long)n - p0), nrb = (np + SL_BM - 1) / SL_BM;
+        const float *src = x + p0 * x_stride;
+        long long src_stride = x_stride;
+        for (int l = 0; l < n_layers; ++l) {
+            const bool last = l + 1 == n_layers;
+            float *dst = last ? zb : buf[l & 1];
+            // layer 0 reads x as it is (K = d); later layers read whole padded rows of the previous image (exact zeros past K)
+            const int K = l == 0 ? L[l].K : L[l].Kp;
+            const float *Wl = packed + L[l].w_off, *bl = packed + L[l].b_off;
+            if (last) {
+                const long long grid = nrb * ((L[l].Np + SL_BN_OUT - 1) / SL_BN_OUT);
+                hipLaunchKernelGGL(NLSH_LAYER_OUT, dim3((unsigned)grid), dim3(256), 0, s, src, src_stride, K, L[l].Kp, np, Wl, bl, L[l].Np,
+                                   dst, (long long)SL_ZS);
+            } else {
+                const long long grid = nrb * ((L[l].Np + SL_BN_HIDDEN - 1) / SL_BN_HIDDEN);
+                hipLaunchKernelGGL(NLSH_LAYER_HIDDEN, dim3((unsigned)grid), dim3(256), 0, s, src, src_stride, K, L[l].Kp, np, Wl, bl,
+                                   L[l].Np, dst, (long long)WS);
+            }
+            NLSH_CHECK_HIP(hipGetLastError());
+            src = dst; src_stride = WS;
+        }
+        // the epilogue of the pass's rows: row indices (Philox counter, n_multi_rows rule, outputs) offset by p0
+        a.x = zb; a.n = np;
+        a.n_multi_rows = n_multi_rows - p0; a.row0 = row0 + p0;
+        a.z_out = z_out ? z_out + p0 * a.H : nullptr;
+        a.probs_out = probs_out ? probs_out + p0 * a.H : nullptr;
+        a.code_out = code_out ? code_out + p0 : nullptr;
+        a.keys_out = keys_out + p0 * n_probes;
+        a.nkeys_out = nkeys_out + p0;
+        hipLaunchKernelGGL(encode_stream_epilogue_kernel, dim3((unsigned)((np + 31) / 32)), dim3(512), lds, s, a);
+        NLSH_CHECK_HIP(hipGetLastError());
+    }
+    return NLSH_OK;
 }

@@ -20,11 +20,13 @@ MAX_LAYERS, MAX_HASH_BITS, MAX_PROBES, MAX_K, MAX_DIM, MAX_WIDTH = 8, 32, 64, 64
 PHASE_PLAN, PHASE_SCAN, PHASE_MERGE = 1, 2, 4
 PHASE_ALL = 7
 MAX_ENCODE_PROBES = 128  # nlsh_encode_hash generates up to this many keys per row; the scan takes them in slices of MAX_PROBES
+MAX_STREAM_WIDTH = 4096  # widest hidden layer of the streamed encoder form (nlsh_encode_hash_stream); MAX_WIDTH: the LDS-resident forms
 
 # every symbol include/nlsh_hip.h declares (tests/test_host_cpu.py::test_capi_library_exports_every_declared_symbol checks the header against this)
 SYMBOLS = (
     "nlsh_abi_version", "nlsh_last_error",
     "nlsh_encoder_packed_floats", "nlsh_encoder_pack", "nlsh_encode_hash", "nlsh_pack_codes",
+    "nlsh_encoder_stream_packed_floats", "nlsh_encoder_stream_pack", "nlsh_encode_stream_workspace", "nlsh_encode_hash_stream",
     "nlsh_build_csr_workspace", "nlsh_build_csr", "nlsh_bucket_order_workspace", "nlsh_bucket_order", "nlsh_build_cells_workspace", "nlsh_build_cells", "nlsh_gather_rows",
     "nlsh_scan_workspace", "nlsh_scan_workspace_layout", "nlsh_scan_topk", "nlsh_scan_topk_phase", "nlsh_scan_topk_cells_phase",
     "nlsh_merge_topk",
@@ -89,6 +91,14 @@ def lib():
     L.nlsh_encode_hash.argtypes = [vp, i64, i64, i32, vp, vp, i32, i32, i32, i64, u64, i64, vp, vp, vp, vp, vp, vp]
     L.nlsh_pack_codes.restype = i32
     L.nlsh_pack_codes.argtypes = [vp, i64, i32, i32, i32, vp, vp]
+    L.nlsh_encoder_stream_packed_floats.restype = i64
+    L.nlsh_encoder_stream_packed_floats.argtypes = [i32, vp]
+    L.nlsh_encoder_stream_pack.restype = i32
+    L.nlsh_encoder_stream_pack.argtypes = [i32, vp, vp, vp, vp, vp]
+    L.nlsh_encode_stream_workspace.restype = sz
+    L.nlsh_encode_stream_workspace.argtypes = [i64, i32, vp]
+    L.nlsh_encode_hash_stream.restype = i32
+    L.nlsh_encode_hash_stream.argtypes = list(L.nlsh_encode_hash.argtypes[:-1]) + [vp, sz, vp]
     L.nlsh_build_csr_workspace.restype = sz
     L.nlsh_build_csr_workspace.argtypes = [i64]
     L.nlsh_build_csr.restype = i32

@@ -4,6 +4,8 @@
 `hash()` / `predict()` (eval mode) run ONE HIP launch: MLP forward on fp32 MFMA, sigmoid/tanh,
 `> 0.5` bits, MSB-first packing, Philox multi-probe sampling and per-row de-duplication, with no
 device->host copy of codes.  `hash_device()` is the device-resident form `Indexer` uses.
+Encoders with a hidden layer wider than `_capi.MAX_WIDTH` (632) are "streamed": they hash through `nlsh_encode_hash_stream`
+(one GEMM launch per layer, activations in a workspace the hashing owns, then the same epilogue), up to `_capi.MAX_STREAM_WIDTH`.
 There is no CPU fallback: a missing library or a non-device tensor raises.
 """
 import itertools
@@ -32,6 +34,9 @@ class _Hasher(nn.Module):
 
 class MultivariateBernoulli:
     _Hasher = _Hasher
+    # bytes of device memory a streamed encoder's workspace may take per (device, stream): the C side makes as many passes over
+    # the rows as this needs (at 1024-wide layers, 8.3 KB per row: ~32k rows per pass)
+    stream_workspace_cap = 256 << 20
 
     def __init__(self, encoder, hash_size, distance_func, tanh_output=False, compat=True, seed=0):
         if not 1 <= hash_size <= _capi.MAX_HASH_BITS:
@@ -145,8 +150,19 @@ class MultivariateBernoulli:
                 sig.append((name, None) if t is None else (name, t.data_ptr(), t._version))
         return tuple(sig)
 
+    def streamed(self):
+        """True when a hidden layer is wider than the LDS-resident forms take (`_capi.MAX_WIDTH`): the encoder hashes through the
+        streamed form, which no pipelined batch slot or fused query call takes.  Asked on every hashing / query call: cached on the
+        weights' signature (a width changes only with a new parameter) instead of walking the layer stack each time."""
+        sig = self._weights_signature()
+        cached = self.__dict__.get("_streamed_for")
+        if cached is None or cached[0] != sig:
+            cached = self._streamed_for = (sig, max(self.dims()[1:-1], default=0) > _capi.MAX_WIDTH)
+        return cached[1]
+
     def packed_weights(self):
-        """MFMA-fragment-ordered weight blob on the device; repacked when a parameter changes."""
+        """MFMA-fragment-ordered weight blob on the device (the streamed form's own layout for a streamed encoder); repacked when a
+        parameter changes."""
         sig = self._weights_signature()
         if self._packed is not None and sig == self._packed_sig:
             return self._packed
@@ -156,21 +172,27 @@ class MultivariateBernoulli:
         if dev.type != "cuda":
             raise _capi.NlshHipError(_capi.E_INVALID, "hasher weights are not on the GPU; there is no CPU path")
         dims = self.dims()
-        n_floats = L.nlsh_encoder_packed_floats(len(stack), _capi.int_array(dims))
+        streamed = self.streamed()
+        count, pack = ((L.nlsh_encoder_stream_packed_floats, L.nlsh_encoder_stream_pack) if streamed
+                       else (L.nlsh_encoder_packed_floats, L.nlsh_encoder_pack))
+        n_floats = count(len(stack), _capi.int_array(dims))
         if n_floats < 0:
             _capi.check(_capi.E_UNSUPPORTED)
         packed = torch.empty((n_floats,), dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(L.nlsh_encoder_pack(len(stack), _capi.int_array(dims), _capi.ptr_array([w for w, _ in stack]),
-                                        _capi.ptr_array([b for _, b in stack]), _capi.ptr(packed), stream))
+        _capi.check(pack(len(stack), _capi.int_array(dims), _capi.ptr_array([w for w, _ in stack]),
+                         _capi.ptr_array([b for _, b in stack]), _capi.ptr(packed), stream))
         self._packed, self._packed_sig, self._keep = packed, sig, stack
         return packed
 
     def encode_args(self, n, keys, nkeys):
         """Fixed part of an `nlsh_encode_hash` call that fills a caller-owned key table (weights as they are NOW):
         (n_layers, dims array, packed weights ptr, act, key_mode, n_probes) and the output pointers, as plain values
-        for callers that launch many batches (nlsh_amd/pipeline.py)."""
+        for callers that launch many batches (nlsh_amd/pipeline.py).  A streamed encoder has no such call: NlshHipError(E_UNSUPPORTED)."""
         dims = self.dims()
+        if self.streamed():
+            raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"hidden width {max(dims[1:-1])} > {_capi.MAX_WIDTH}: the encoder hashes "
+                                                          "through the streamed form only (no fused / pipelined encode launch)")
         self._dims_arr = _capi.int_array(dims)
         packed = self.packed_weights()
         return ((len(dims) - 1, self._dims_arr, packed.data_ptr(), _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID,
@@ -248,12 +270,37 @@ class MultivariateBernoulli:
         if seed is None:
             seed = (self._seed + 0x9E3779B97F4A7C15 * (next(self._calls) + 1)) & 0xFFFFFFFFFFFFFFFF
         stream = torch.cuda.current_stream(x.device).cuda_stream
+        if self.streamed():
+            ws = self._stream_workspace(L, dims, B, x.device, stream)
+            _capi.check(L.nlsh_encode_hash_stream(
+                _capi.ptr(x), B, x.stride(0) if B else dims[0], len(dims) - 1, _capi.int_array(dims), _capi.ptr(packed),
+                _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID, self.key_mode, n,
+                B if n_multi_rows is None else int(n_multi_rows), seed, row0,
+                _capi.ptr(z_out), _capi.ptr(probs), _capi.ptr(code_out), _capi.ptr(keys), _capi.ptr(nkeys),
+                _capi.ptr(ws), ws.numel(), stream))
+            return keys, nkeys, probs
         _capi.check(L.nlsh_encode_hash(
             _capi.ptr(x), B, x.stride(0) if B else dims[0], len(dims) - 1, _capi.int_array(dims), _capi.ptr(packed),
             _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID, self.key_mode, n,
             B if n_multi_rows is None else int(n_multi_rows), seed, row0,
             _capi.ptr(z_out), _capi.ptr(probs), _capi.ptr(code_out), _capi.ptr(keys), _capi.ptr(nkeys), stream))
         return keys, nkeys, probs
+
+
+    def _stream_workspace(self, L, dims, rows, device, stream):
+        """The streamed form's workspace for `rows` rows on (device, stream), capped at `stream_workspace_cap` (at least one row tile):
+        one buffer per stream, so that calls on two streams never share one; grown, never shrunk."""
+        want = L.nlsh_encode_stream_workspace(max(rows, 1), len(dims) - 1, _capi.int_array(dims))
+        floor = L.nlsh_encode_stream_workspace(1, len(dims) - 1, _capi.int_array(dims))
+        if want == 0 or floor == 0:
+            raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"streamed encoder {dims}: outside the form's limits")
+        want = max(min(want, self.stream_workspace_cap), floor)
+        pool = self.__dict__.setdefault("_stream_ws", {})
+        key = (device.index, stream)
+        ws = pool.get(key)
+        if ws is None or ws.numel() < want:
+            ws = pool[key] = torch.empty((want,), dtype=torch.uint8, device=device)
+        return ws
 
 
 def host_key_set(row, count, key_mode=_capi.KEY_REF_INT16) -> Set[int]:

@@ -541,11 +541,13 @@ class Indexer:
     def _fuses(self, q, hash_times, algo):
         """One `nlsh_query_batch` call (ABI v4: five launches, the bucket lookup in the encode's epilogue) serves a batch when the
         fused kernel may hash it at all (not a BatchNorm encoder in train mode), the key table fits one scan call and the schedule
-        is a bucket-major one (the query-major stream's PLAN phase is a single kernel of its own)."""
+        is a bucket-major one (the query-major stream's PLAN phase is a single kernel of its own).  A streamed encoder (hidden layer
+        wider than `_capi.MAX_WIDTH`) has no fused encode launch: `hash_device` + `scan_tensors`, the same results by design."""
         needs_train = getattr(self._hashing, "_needs_train_forward", None)
+        streamed = getattr(self._hashing, "streamed", None)
         return (self.metric in ("l2", "cosine") and 1 <= hash_times <= _capi.MAX_PROBES and algo != _capi.SCAN_QUERY_MAJOR
                 and self.n_buckets > 0 and q.shape[0] > 0 and not (needs_train is not None and needs_train())
-                and hasattr(self._hashing, "encode_args"))
+                and hasattr(self._hashing, "encode_args") and not (streamed is not None and streamed()))
 
     def _batch_tensors(self, query_vectors, k, hash_times, seed, want_keys=False, check=True, events=None, algo=None, row0=0,
                        n_multi=None, out=None):

@@ -57,6 +57,10 @@ class QueryPipeline:
         (`nlsh_step_create_graph`): batches overlap because the slots' streams do, and a submit costs the host one graph launch + two
         node updates instead of the staged slots' five launches + eight to ten event calls.  False = the three / four stage streams of
         r03-r05.  None = graph slots whenever the schedule is a bucket-major one (`QueryPipeline.default_graph`)."""
+        streamed = getattr(indexer._hashing, "streamed", None)
+        if streamed is not None and streamed():
+            raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"pipelined batches take encoders with hidden layers <= {_capi.MAX_WIDTH} wide, "
+                                                          f"not {max(indexer._hashing.dims()[1:-1])} (the streamed form has no batch slot)")
         if hash_times > _capi.MAX_PROBES:
             raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"pipelined batches take hash_times <= {_capi.MAX_PROBES}")
         if depth < 2:
