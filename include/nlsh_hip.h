@@ -57,7 +57,10 @@ enum { NLSH_SCAN_QUERY_MAJOR = 0, NLSH_SCAN_BUCKET_MAJOR = 1, NLSH_SCAN_BUCKET_T
 #define NLSH_MAX_HASH_BITS 32
 #define NLSH_MAX_PROBES 64  /* keys per query one nlsh_scan_topk call takes */
 #define NLSH_MAX_ENCODE_PROBES 128  /* hash_times nlsh_encode_hash generates (eval.py:148 sweeps 1..100); scan in slices of 64 */
-#define NLSH_MAX_K 64
+#define NLSH_MAX_K 64       /* k every scan schedule takes */
+#define NLSH_MAX_K_TILED 256  /* k of the tiled schedule (NLSH_SCAN_BUCKET_TILED) and of nlsh_merge_topk: a tiled task scores at most 256 rows
+                               * per (task, query) list, so a list is still selected from what one wave holds.  The tiled workspace keeps
+                               * 16 lists of k keys per task, max_tasks * 16 * k * 8 bytes: 32 KB per task at k = 256 (17,277 tasks: 566 MB) */
 #define NLSH_MAX_DIM 1024   /* vector dimension of corpus / queries for the scan */
 #define NLSH_MAX_WIDTH 632  /* widest HIDDEN encoder layer the LDS-resident MLP supports (the input may be NLSH_MAX_DIM wide) */
 #define NLSH_MAX_STREAM_WIDTH 4096  /* widest HIDDEN encoder layer of the streamed form (nlsh_encode_hash_stream) */
@@ -214,7 +217,9 @@ size_t nlsh_scan_workspace(int64_t Q, int P, int k, int64_t max_tasks, int64_t n
  * empty and status[1] = 2 (the Python facade raises NLSH_E_WORKSPACE).  The counters are zero again after the refused call.
  * ev_scan_begin / ev_scan_end (nullable hipEvent_t): recorded on `stream` immediately before and
  * after the scan kernel, so a caller can time the HBM-bound kernel alone (bench.py roofline).
- * Limits: d <= NLSH_MAX_DIM, k <= NLSH_MAX_K, P <= NLSH_MAX_PROBES. */
+ * Limits: d <= NLSH_MAX_DIM, P <= NLSH_MAX_PROBES; k <= NLSH_MAX_K for algo NLSH_SCAN_QUERY_MAJOR and NLSH_SCAN_BUCKET_MAJOR,
+ * k <= NLSH_MAX_K_TILED for NLSH_SCAN_BUCKET_TILED (NLSH_E_UNSUPPORTED otherwise; the phase, cells, step and batch entry points
+ * below validate through the same rule).  The partial lists take max_tasks * 16 * k * 8 bytes of the tiled workspace. */
 int nlsh_scan_topk(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid,
                    const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
                    const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
@@ -348,7 +353,8 @@ int nlsh_step_busy(nlsh_step_t *step);
  * row as all-gathered from nlsh_scan_topk's out_keys) into the global top-k; same comparator, so the
  * result equals the single-GPU result.  Candidate counts are summed into out_ncand from ncand_in
  * (nullable) [G, Q], or, when ncand_in is NULL and row_stride > k, from element k of every row (so one
- * collective can carry keys and counts together). */
+ * collective can carry keys and counts together).
+ * Limits: k <= NLSH_MAX_K_TILED. */
 int nlsh_merge_topk(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,
                     float *out_dist, int32_t *out_idx, int32_t *out_ncand, nlsh_stream_t stream);
 

@@ -818,7 +818,10 @@ __device__ __forceinline__ void warm_query_lines_done(float &sink) {
 // The (NQ, NTL) pair is chosen ONCE per task, outside the k-block loop: chosen per k-block, the 16 accumulators crossed
 // a 16-way switch every k-block and the register allocator copied all of them in and out each time (466 v_mov in the
 // kernel, +67 % instructions on small shapes).  NTL also fixes the fat-stage geometry at compile time.
-template <int NW, int NQ, int NTL, int METRIC = NLSH_METRIC_L2_EPS>
+// (WIDEK changes nothing in here: it gives the wide-k kernels instantiations of their own.  The stage_load lambda below is an ordinary
+// function that the compiler inlines by its own judgement, and with a second kernel calling the SAME instantiation it judged differently:
+// the k <= 64 kernels' staging code changed and took three more VGPRs.)
+template <int NW, int NQ, int NTL, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false>
 __device__ __forceinline__ void l2_task(float4 *tile, const float4 *corpus4, long long stride4, int d4, int row0, int nrows,
                                         const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4],
                                         [[maybe_unused]] unsigned long long (&tr)[3]) {
@@ -932,15 +935,15 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const float4 *corpu
     }
 }
 
-template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS>
+template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false>
 __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const float4 *corpus4, long long stride4, int d4, int row0, int nrows,
                                            const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4], unsigned long long (&tr)[3]) {
     switch (ntile) {
         case 0: l2_task_single<NW, NQ, METRIC>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc); break;   // "0 tiles": the single-stage body
-        case 1: l2_task<NW, NQ, 1, METRIC>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
-        case 2: l2_task<NW, NQ, 2, METRIC>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
-        case 3: l2_task<NW, NQ, 3, METRIC>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
-        default: l2_task<NW, NQ, 4, METRIC>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
+        case 1: l2_task<NW, NQ, 1, METRIC, WIDEK>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
+        case 2: l2_task<NW, NQ, 2, METRIC, WIDEK>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
+        case 3: l2_task<NW, NQ, 3, METRIC, WIDEK>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
+        default: l2_task<NW, NQ, 4, METRIC, WIDEK>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
     }
 }
 
@@ -1024,6 +1027,73 @@ __device__ __forceinline__ void merge_query(const BArgs &a, long long q, int lan
     merge_finish(carry, a.k, lane, a.out_dist, a.out_idx, a.out_keys, q);
 }
 
+// merge_query for k in 65..NLSH_MAX_K_TILED (the tiled schedule only): the same records, the same list table and the same search for
+// queries that leave it; a list is k keys fetched KPL = ceil(k / 64) per lane (entry e in register e / 64 of lane e % 64) instead of 64 / k
+// lists per load, and a round takes NL lists beside the carry (merge_round_wide: (1 + NL) * KPL <= 8 keys per lane).  `sc` = NLSH_MAX_K_TILED
+// u64 of LDS scratch owned by the wave.
+template <int KPL>
+__device__ __forceinline__ void merge_query_wide(const BArgs &a, long long q, int lane, uint64_t *sc, int2 *ltab) {
+    int ns_l = 0, j_l = 0, ng_l = 0;
+    long long t0_l = 0;
+    int size_l = 0;
+    if (lane < a.P) {
+        const int4 rec = a.prec[q * a.P + lane];
+        t0_l = rec.x; j_l = rec.y; size_l = rec.z; ng_l = rec.w;
+        ns_l = (size_l + a.seg - 1) / a.seg;
+    }
+    {
+        const int c = __builtin_amdgcn_readlane(wave_incl_scan_i32(size_l), 63);
+        if (lane == 0) a.out_ncand[q] = c;
+    }
+    const int incl = wave_incl_scan_i32(ns_l);
+    const int L = __builtin_amdgcn_readlane(incl, 63);
+    constexpr int LIST_TAB = 128, LIST_TAB_MAX_SEG = 8;
+    const bool tabbed = L <= LIST_TAB && (int)wave_minmax_u32<true>((uint32_t)ns_l) <= LIST_TAB_MAX_SEG;   // wave-uniform
+    if (tabbed) {
+        const int first = incl - ns_l;
+        for (int si = 0; si < LIST_TAB_MAX_SEG; ++si)
+            if (si < ns_l) ltab[first + si] = make_int2((int)(t0_l + (long long)si * ng_l), j_l);
+    }
+    // the KPL registers of list `li` (wave-uniform; li >= L: absent)
+    auto fetch = [&](int li, uint64_t *dst) {
+        long long t;
+        int j;
+        if (tabbed) {
+            const int2 ent = ltab[li < L ? li : 0];   // same wave wrote it: LDS operations of a wave complete in order
+            t = ent.x; j = ent.y;
+        } else {
+            int lo = 0, hi = 63;  // probe of list li = first lane whose inclusive count exceeds li
+#pragma unroll
+            for (int step = 0; step < 6; ++step) {
+                const int mid = (lo + hi) >> 1;
+                if (__shfl(incl, mid) > li) hi = mid; else lo = mid + 1;
+            }
+            const int p = lo > 63 ? 63 : lo;
+            const int si = li - (__shfl(incl, p) - __shfl(ns_l, p));
+            t = (long long)(((unsigned long long)(unsigned)__shfl((int)(t0_l >> 32), p) << 32) | (unsigned)__shfl((int)t0_l, p)) + (long long)si * __shfl(ng_l, p);
+            j = __shfl(j_l, p);
+        }
+        // t >= max_tasks: table overflow, status[1] was set by the scan kernel and the caller repeats the call
+        const bool live = li < L && t < a.max_tasks;
+        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(a.partial) + ((live ? t : 0) * a.QB + j) * a.k;
+#pragma unroll
+        for (int i = 0; i < KPL; ++i) dst[i] = (live && i * 64 + lane < a.k) ? (uint64_t)src[i * 64 + lane] : KEY_NONE;
+    };
+    constexpr int NL = KPL == 2 ? 3 : 1;
+    uint64_t carry[KPL];
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) carry[i] = KEY_NONE;
+    for (int base = 0; base < L; base += NL) {
+        uint64_t key[KPL * (1 + NL)];
+#pragma unroll
+        for (int i = 0; i < KPL; ++i) key[i] = carry[i];
+#pragma unroll
+        for (int s = 0; s < NL; ++s) fetch(base + s, key + KPL * (1 + s));
+        merge_round_wide(key, carry, a.k, lane, sc);
+    }
+    merge_finish_wide(carry, sc, a.k, lane, a.out_dist, a.out_idx, a.out_keys, q);
+}
+
 // QW queries per wave, NW waves per workgroup (QW*NW queries per task), TPS 64-row tiles per task.
 // k-blocks of KB chunks are the OUTER loop: one stage holds the KB-chunk slice of ALL 64*TPS rows of
 // the segment in LDS, so every scalar-loaded query chunk is applied to TPS row tiles (TPS x fewer
@@ -1032,7 +1102,9 @@ __device__ __forceinline__ void merge_query(const BArgs &a, long long q, int lan
 // chunk c+1 are issued before chunk c is evaluated.
 // One task of the tiled schedule, start to finish (operands of the task already requested by the caller: descriptor and
 // the wave's query ids).  `tile` = the workgroup's LDS stage.
-template <int METRIC, int QW, int NW, int TPS>
+// WIDEK (compile time): k in 65..NLSH_MAX_K_TILED -- the epilogue's selection pads its k-key list with a lane-strided loop; everything in
+// front of the epilogue is the same code, so every distance keeps its bits.
+template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false>
 __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, long long t, const int4 desc, const int2 qr_all, int tid, int lane,
                                                 int wave, [[maybe_unused]] unsigned long long ts_entry) {
     constexpr int NT = 64 * NW;              // threads per workgroup
@@ -1124,11 +1196,11 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
     const int nt_sel = (NLSH_SINGLE_STAGE && nrows * d4 <= SINGLE_STAGE_SLOTS && nrows <= 64) ? 0 : ntile;   // wave-uniform (task shape)
     if (FAST) {   // hand-scheduled form, specialised per (queries of this wave, tiles of the task); same barrier count on every path
         switch (nqw) {
-            case 0: l2_task_nt<NW, 0, METRIC>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-            case 1: l2_task_nt<NW, 1, METRIC>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-            case 2: l2_task_nt<NW, 2, METRIC>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-            case 3: l2_task_nt<NW, 3, METRIC>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-            default: l2_task_nt<NW, 4, METRIC>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+            case 0: l2_task_nt<NW, 0, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+            case 1: l2_task_nt<NW, 1, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+            case 2: l2_task_nt<NW, 2, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+            case 3: l2_task_nt<NW, 3, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+            default: l2_task_nt<NW, 4, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
         }
     }
     if (!FAST) stage_load(0);
@@ -1248,7 +1320,7 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
             if (NLSH_ABLATE != 3) {
                 // (r04: one-tile tasks selecting from ONE key per lane instead of TPS with three absent -- a quarter of the ballots per
                 // bisection step -- measured equal on all three workloads, profiles/r04_select_nk1_ab.txt; not kept)
-                const uint64_t bound = select_k_smallest<TPS>(key, a.k, lane, out);
+                const uint64_t bound = select_k_smallest<TPS, false, WIDEK>(key, a.k, lane, out);
                 if (bound != KEY_NONE && lane == 0) atomicMin(a.tauq + qid[jq], (unsigned long long)bound);
             } else if (lane < a.k) out[lane] = key[0];
         }
@@ -1315,6 +1387,32 @@ __global__ __launch_bounds__(64 * NW, NLSH_TILED_MIN_WAVES) void bscan3_kernel(B
     tiled_task_body<METRIC, QW, NW, TPS>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry);
 }
 
+// The tiled scan for k in 65..NLSH_MAX_K_TILED: bscan3_kernel with the wide epilogue.  A kernel of its own name, so that the three
+// bscan3_kernel instantiations -- what every k <= 64 call runs -- keep their code and their register / occupancy budget.  The task pick
+// is bscan3_kernel's, line for line (see the comments there), and written out again: with the LDS stage handed to a shared function, or
+// declared in one, its address stops being a compile-time constant of the staging code and the narrow kernels' instructions change.
+template <int METRIC, int QW, int NW, int TPS>
+__global__ __launch_bounds__(64 * NW, NLSH_TILED_MIN_WAVES) void bscanw_kernel(BArgs a) {
+    constexpr int RS = NLSH_TILED_KB + 1;
+    __shared__ float4 tile[64 * TPS * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
+    if (NLSH_PRIO_OUT >= 0) __builtin_amdgcn_s_setprio(NLSH_PRIO_OUT);
+    long long ntasks = a.status[0];
+    if (ntasks > a.max_tasks) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
+        ntasks = a.max_tasks;
+    }
+    constexpr int XC = 16;
+    const long long j = blockIdx.x >> 3;
+    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
+    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
+    const int4 desc = a.task[tc];
+    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
+    if (t >= ntasks) return;
+    tiled_task_body<METRIC, QW, NW, TPS, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry);
+}
+
 // (r01-r05 re-checked here that every pair counter was back at zero; since r06 bscan_kernel resets the counters itself and its
 // verdict covers every way a stale count can enter a batch -- positive ones through the sum, negative ones directly.)
 __global__ __launch_bounds__(256) void bmerge_kernel(BArgs a) {
@@ -1323,6 +1421,16 @@ __global__ __launch_bounds__(256) void bmerge_kernel(BArgs a) {
     __shared__ uint64_t scratch[4][64];
     __shared__ int2 list_tab[4][128];    // merge_query's LIST_TAB entries per wave
     if (q < a.Q) merge_query(a, q, lane, scratch[threadIdx.x >> 6], list_tab[threadIdx.x >> 6]);
+}
+
+// Wide-k merge (k in 65..NLSH_MAX_K_TILED): KPL = ceil(k / 64) keys per lane, one list = KPL coalesced loads of the wave.
+template <int KPL>
+__global__ __launch_bounds__(256) void bmergew_kernel(BArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    __shared__ uint64_t scratch[4][NLSH_MAX_K_TILED];
+    __shared__ int2 list_tab[4][128];
+    if (q < a.Q) merge_query_wide<KPL>(a, q, lane, scratch[threadIdx.x >> 6], list_tab[threadIdx.x >> 6]);
 }
 
 #ifndef NLSH_TILED_QB
@@ -1407,7 +1515,12 @@ static void scan_kernel_of(const BucketScanCall &c, int metric, int d4, const vo
         // profiles/r04_tasks_per_workgroup_ab.txt, DESIGN.md appendix A.)
         *grid = dim3((unsigned)((c.max_tasks + 127) / 128 * 128));
         *block = dim3(64 * (TILED_QB / 4));
-        if (metric == NLSH_METRIC_L2_EPS) *fn = (const void *)bscan3_kernel<NLSH_METRIC_L2_EPS, 4, TILED_QB / 4, TILED_TPS>;
+        if (c.k > NLSH_MAX_K) {   // wide k: the same task body, its epilogue selecting up to 64 * TPS keys per list
+            static_assert(NLSH_MAX_K_TILED <= 64 * TILED_TPS, "a (task, query) list is selected from the 64 * TPS candidates the wave holds");
+            if (metric == NLSH_METRIC_L2_EPS) *fn = (const void *)bscanw_kernel<NLSH_METRIC_L2_EPS, 4, TILED_QB / 4, TILED_TPS>;
+            else if (metric == NLSH_METRIC_L2_EPS_FOLDED) *fn = (const void *)bscanw_kernel<NLSH_METRIC_L2_EPS_FOLDED, 4, TILED_QB / 4, TILED_TPS>;
+            else *fn = (const void *)bscanw_kernel<NLSH_METRIC_COSINE, 4, TILED_QB / 4, TILED_TPS>;
+        } else if (metric == NLSH_METRIC_L2_EPS) *fn = (const void *)bscan3_kernel<NLSH_METRIC_L2_EPS, 4, TILED_QB / 4, TILED_TPS>;
         else if (metric == NLSH_METRIC_L2_EPS_FOLDED) *fn = (const void *)bscan3_kernel<NLSH_METRIC_L2_EPS_FOLDED, 4, TILED_QB / 4, TILED_TPS>;
         else *fn = (const void *)bscan3_kernel<NLSH_METRIC_COSINE, 4, TILED_QB / 4, TILED_TPS>;
     } else {
@@ -1522,7 +1635,13 @@ int bucket_scan_run(const BucketScanCall &c) {
         NLSH_CHECK_HIP(hipLaunchKernel(fn, grid, block, argv, 0, s));
         if (c.ev_end) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)c.ev_end, s));
     }
-    if (c.phases & NLSH_PHASE_MERGE) hipLaunchKernelGGL(bmerge_kernel, dim3((unsigned)((c.Q + 3) / 4)), dim3(256), 0, s, a);
+    if (c.phases & NLSH_PHASE_MERGE) {
+        const dim3 gm((unsigned)((c.Q + 3) / 4));
+        if (c.k <= NLSH_MAX_K) hipLaunchKernelGGL(bmerge_kernel, gm, dim3(256), 0, s, a);
+        else if (c.k <= 128) hipLaunchKernelGGL(bmergew_kernel<2>, gm, dim3(256), 0, s, a);
+        else if (c.k <= 192) hipLaunchKernelGGL(bmergew_kernel<3>, gm, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(bmergew_kernel<4>, gm, dim3(256), 0, s, a);
+    }
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
 }

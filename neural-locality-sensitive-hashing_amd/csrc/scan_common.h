@@ -152,7 +152,14 @@ __device__ __forceinline__ int wave_incl_scan_i32(int x) {
 // CLAMP (the merges): keys that reach a merge are distinct when every (query, bucket) pair was scanned once -- the plan
 // kernels de-duplicate a query's probe keys, corpus shards are disjoint -- but nlsh_merge_topk takes whatever lists a C
 // caller hands it: with repeated keys the tie search can select more than k, so the compaction never writes past out[k).
-template <int NK, bool CLAMP = false>
+// WIDE (k up to NLSH_MAX_K_TILED, compile time): the search and the compaction are generic in k; what assumes one output slot per lane is
+// the KEY_NONE padding behind the survivors, which the wide form writes with a lane-strided loop.  The narrow form's code is unchanged.
+__device__ __forceinline__ void select_pad_wide(uint64_t *out, int from, int k, int lane) {
+    for (int i = lane; i < k; i += 64)
+        if (i >= from) out[i] = KEY_NONE;
+}
+
+template <int NK, bool CLAMP = false, bool WIDE = false>
 __device__ __forceinline__ uint64_t select_k_smallest(const uint64_t (&key)[NK], int k, int lane, uint64_t *out) {
     uint32_t hi[NK], lo[NK];
     int n = 0;
@@ -166,7 +173,8 @@ __device__ __forceinline__ uint64_t select_k_smallest(const uint64_t (&key)[NK],
     // 23-41 % with fewer than k (profiles/r05_epilogue_counters_and_ablations.txt): neither needs a cut, and the general compaction below
     // spends six compares per key slot re-deriving "present" from a cut that takes everything.
     if (NLSH_SELECT_SHORT_PATHS && n == 0) {
-        if (lane < k) out[lane] = KEY_NONE;
+        if constexpr (WIDE) select_pad_wide(out, 0, k, lane);
+        else if (lane < k) out[lane] = KEY_NONE;
         return KEY_NONE;
     }
     if (NLSH_SELECT_SHORT_PATHS && n < k) {
@@ -181,7 +189,8 @@ __device__ __forceinline__ uint64_t select_k_smallest(const uint64_t (&key)[NK],
                 base0 += __popcll(m);
             }
         }
-        if (lane >= base0 && lane < k) out[lane] = KEY_NONE;
+        if constexpr (WIDE) select_pad_wide(out, base0, k, lane);
+        else if (lane >= base0 && lane < k) out[lane] = KEY_NONE;
         return KEY_NONE;
     }
     uint32_t dk = 0xFFFFFFFFu, idk = 0xFFFFFFFFu;  // take everything present (hi of a present key < 0xFFFFFFFF)
@@ -245,7 +254,8 @@ __device__ __forceinline__ uint64_t select_k_smallest(const uint64_t (&key)[NK],
         }
         base += __popcll(m);
     }
-    if (lane >= base && lane < k) out[lane] = KEY_NONE;
+    if constexpr (WIDE) select_pad_wide(out, base, k, lane);
+    else if (lane >= base && lane < k) out[lane] = KEY_NONE;
     return n >= k ? ((uint64_t)dk + 1ull) << 32 : KEY_NONE;
 }
 
@@ -272,6 +282,46 @@ __device__ __forceinline__ void merge_finish(uint64_t carry, int k, int lane, fl
         out_dist[q * k + pos] = none ? __builtin_inff() : float_from_mono((uint32_t)(carry >> 32));
         out_idx[q * k + pos] = none ? -1 : (int32_t)(uint32_t)carry;
         if (out_keys) out_keys[q * k + pos] = carry;
+    }
+}
+
+// Wide k (65..NLSH_MAX_K_TILED = 256): the same merge by selection with KPL = ceil(k / 64) keys per lane -- entry e of a k-key list sits in
+// register e / 64 of lane e % 64.  A round selects the k best of the carry and of NL new lists (NK = KPL * (1 + NL) <= 8 keys per lane) into
+// the wave's LDS scratch (k keys; NLSH_MAX_K_TILED of them per wave are reserved) and reads the carry back from it.
+template <int NK, int KPL>
+__device__ __forceinline__ void merge_round_wide(const uint64_t (&key)[NK], uint64_t (&carry)[KPL], int k, int lane, uint64_t *scratch) {
+    select_k_smallest<NK, true, true>(key, k, lane, scratch);
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) carry[i] = i * 64 + lane < k ? scratch[i * 64 + lane] : KEY_NONE;   // same wave wrote it (see merge_round)
+}
+
+// Final ordering of the wide carry: every lane ranks its KPL keys against the survivors in the scratch copy (one broadcast LDS read per
+// survivor, KPL compares each).  `scratch` is what the LAST round left: real keys in [0, n_real), KEY_NONE behind -- with no round at all the
+// carry is all KEY_NONE, n_real = 0 and the scratch is never read.  Same order and padding as merge_finish.
+template <int KPL>
+__device__ __forceinline__ void merge_finish_wide(const uint64_t (&carry)[KPL], const uint64_t *scratch, int k, int lane, float *out_dist,
+                                                  int32_t *out_idx, uint64_t *out_keys, long long q) {
+    int n_real = 0, rank[KPL];
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) {
+        n_real += __popcll(__ballot(carry[i] != KEY_NONE));
+        rank[i] = 0;
+    }
+    for (int j = 0; j < n_real; ++j) {   // equal keys (a C caller's repeated lists) are ordered by slot: every slot is written
+        const uint64_t kj = scratch[j];
+#pragma unroll
+        for (int i = 0; i < KPL; ++i) rank[i] += (kj < carry[i] || (kj == carry[i] && j < i * 64 + lane)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) {
+        const int slot = i * 64 + lane;
+        if (slot < k) {
+            const bool none = carry[i] == KEY_NONE;
+            const int pos = none ? slot : rank[i];
+            out_dist[q * k + pos] = none ? __builtin_inff() : float_from_mono((uint32_t)(carry[i] >> 32));
+            out_idx[q * k + pos] = none ? -1 : (int32_t)(uint32_t)carry[i];
+            if (out_keys) out_keys[q * k + pos] = carry[i];
+        }
     }
 }
 

@@ -250,6 +250,43 @@ __global__ __launch_bounds__(256) void merge_shards_kernel(const uint64_t *keys_
     }
 }
 
+// merge_shards_kernel for k in 65..NLSH_MAX_K_TILED: KPL = ceil(k / 64) keys per lane, NL shard lists per round beside the carry
+template <int KPL>
+__global__ __launch_bounds__(256) void merge_shards_wide_kernel(const uint64_t *keys_in, long long row_stride, int G, long long Q, int k,
+                                                                 const int32_t *ncand_in, float *out_dist, int32_t *out_idx,
+                                                                 int32_t *out_ncand) {
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= Q) return;
+    constexpr int NL = KPL == 2 ? 3 : 1;
+    __shared__ uint64_t scratch[4][NLSH_MAX_K_TILED];
+    uint64_t *sc = scratch[threadIdx.x >> 6];
+    uint64_t carry[KPL];
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) carry[i] = KEY_NONE;
+    for (int base = 0; base < G; base += NL) {
+        uint64_t key[KPL * (1 + NL)];
+#pragma unroll
+        for (int i = 0; i < KPL; ++i) key[i] = carry[i];
+#pragma unroll
+        for (int s = 0; s < NL; ++s) {
+            const int g = base + s;
+#pragma unroll
+            for (int i = 0; i < KPL; ++i)
+                key[KPL * (1 + s) + i] = (g < G && i * 64 + lane < k) ? keys_in[((long long)g * Q + q) * row_stride + i * 64 + lane] : KEY_NONE;
+        }
+        merge_round_wide(key, carry, k, lane, sc);
+    }
+    merge_finish_wide(carry, sc, k, lane, out_dist, out_idx, nullptr, q);
+    if (out_ncand && (ncand_in || row_stride > k)) {
+        int32_t nc = 0;
+        for (int g = lane; g < G; g += 64) nc += ncand_in ? ncand_in[(long long)g * Q + q] : (int32_t)keys_in[((long long)g * Q + q) * row_stride + k];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) nc += __shfl_xor(nc, m);
+        if (lane == 0) out_ncand[q] = nc;
+    }
+}
+
 struct ScanWs {
     size_t pstart, pcum, nseg, tbase, task_q, task_s, partial, total;
 };
@@ -311,7 +348,11 @@ int nlsh::scan_topk_cells_phase_checked(const float *corpus_sorted, int64_t row_
     NLSH_REQUIRE(!(phases & NLSH_PHASE_PLAN_REST) || algo != NLSH_SCAN_QUERY_MAJOR, NLSH_E_INVALID, "scan_topk: the query-major schedule has no fused lookup");
     NLSH_REQUIRE(Q >= 0 && Q < (1ll << 31), NLSH_E_INVALID, "scan_topk: Q=%lld", (long long)Q);
     NLSH_REQUIRE(d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_UNSUPPORTED, "scan_topk: d=%d not in [1,%d]", d, NLSH_MAX_DIM);
-    NLSH_REQUIRE(k >= 1 && k <= NLSH_MAX_K, NLSH_E_UNSUPPORTED, "scan_topk: k=%d not in [1,%d]", k, NLSH_MAX_K);
+    // one key per lane is built into the running top-k of the query-major and the wave-level bucket-major schedules; the tiled schedule
+    // selects a list from the 64 * TPS = 256 candidates a wave holds
+    NLSH_REQUIRE(k >= 1 && k <= (algo == NLSH_SCAN_BUCKET_TILED ? NLSH_MAX_K_TILED : NLSH_MAX_K), NLSH_E_UNSUPPORTED,
+                 "scan_topk: k=%d not supported by algo=%d: every schedule takes k in [1,%d], only the tiled schedule (NLSH_SCAN_BUCKET_TILED, "
+                 "algo=\"tiled\" in the Python facade) takes k in [1,%d]", k, algo, NLSH_MAX_K, NLSH_MAX_K_TILED);
     NLSH_REQUIRE(P >= 1 && P <= NLSH_MAX_PROBES, NLSH_E_UNSUPPORTED, "scan_topk: P=%d not in [1,%d]", P, NLSH_MAX_PROBES);
     NLSH_REQUIRE(metric == NLSH_METRIC_L2_EPS || metric == NLSH_METRIC_COSINE || metric == NLSH_METRIC_L2_EPS_FOLDED, NLSH_E_INVALID, "scan_topk: metric=%d", metric);
     NLSH_REQUIRE(algo == NLSH_SCAN_QUERY_MAJOR || algo == NLSH_SCAN_BUCKET_MAJOR || algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_INVALID,
@@ -401,12 +442,18 @@ extern "C" int nlsh_scan_topk(const float *corpus_sorted, int64_t row_stride, in
 
 extern "C" int nlsh_merge_topk(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,
                                float *out_dist, int32_t *out_idx, int32_t *out_ncand, nlsh_stream_t stream) {
-    NLSH_REQUIRE(G >= 1 && Q >= 0 && k >= 1 && k <= NLSH_MAX_K && row_stride >= k, NLSH_E_INVALID,
-                 "merge_topk: G=%d Q=%lld k=%d row_stride=%lld", G, (long long)Q, k, (long long)row_stride);
+    NLSH_REQUIRE(G >= 1 && Q >= 0 && k >= 1 && k <= NLSH_MAX_K_TILED && row_stride >= k, NLSH_E_INVALID,
+                 "merge_topk: G=%d Q=%lld k=%d (at most %d) row_stride=%lld", G, (long long)Q, k, NLSH_MAX_K_TILED, (long long)row_stride);
     if (Q == 0) return NLSH_OK;
     NLSH_REQUIRE(keys_in && out_dist && out_idx, NLSH_E_INVALID, "merge_topk: null pointer");
-    hipLaunchKernelGGL(merge_shards_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, (hipStream_t)stream, keys_in, (long long)row_stride, G,
-                       (long long)Q, k, ncand_in, out_dist, out_idx, out_ncand);
+    const dim3 grid((unsigned)((Q + 3) / 4));
+    const void *fn = (const void *)merge_shards_kernel;
+    if (k > 192) fn = (const void *)merge_shards_wide_kernel<4>;
+    else if (k > 128) fn = (const void *)merge_shards_wide_kernel<3>;
+    else if (k > NLSH_MAX_K) fn = (const void *)merge_shards_wide_kernel<2>;
+    long long rs = row_stride, q64 = Q;
+    void *argv[] = {&keys_in, &rs, &G, &q64, &k, &ncand_in, &out_dist, &out_idx, &out_ncand};
+    NLSH_CHECK_HIP(hipLaunchKernel(fn, grid, dim3(256), argv, 0, (hipStream_t)stream));
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
 }

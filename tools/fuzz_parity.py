@@ -38,6 +38,8 @@ def one_case(rng, case_id):
     k = int(rng.choice([1, 3, 10, 10, 10, 37, 64]))
     P = int(rng.choice([1, 2, 6, 10, 10, 33, 64, 100]))
     algo = rng.choice(["query", "bucket", "tiled", None])
+    if algo == "tiled" and rng.integers(0, 3) == 0:                   # the tiled schedule (named: it then serves every batch size) takes k <= 256
+        k = int(rng.choice([65, 100, 128, 129, 200, 255, 256]))
     window = [None, 0, 64, 128, 256][int(rng.integers(0, 5))]         # row window of the tiled schedule's small-bucket packing (never changes a bit)
     hidden = tuple(int(v) for v in rng.choice([32, 64, 96, 320], size=int(rng.integers(1, 3))))
     gen = synth.sift_like if metric == "l2" else synth.glove_like

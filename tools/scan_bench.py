@@ -3,7 +3,7 @@
 then times the scan phase alone (HIP events around the scan kernel, as bench.py does) and the whole device-resident
 step, and checks the result against the query-major schedule (ids equal up to fp32 near-ties, candidate counts exact).
 
-    python tools/scan_bench.py [--algo tiled] [--iters 30] [--workload sift1m|clusters|glove] [--window 0,64,128,256]
+    python tools/scan_bench.py [--algo tiled] [--iters 30] [--workload sift1m|clusters|glove] [--window 0,64,128,256] [--k 10,64,100,256]
     NLSH_HIP_LIB=/path/to/other/build.so python tools/scan_bench.py --tag other      # A/B against another build
 """
 import argparse
@@ -23,6 +23,26 @@ from nlsh_amd.data import Glove, SIFT  # noqa: E402
 from nlsh_amd.indexer import Indexer  # noqa: E402
 
 
+def merge_phase_ms(ix, qg, keys, nkeys, k, iters, out):
+    """Mean device time of the MERGE phase alone: re-run (it only reads the partial lists the last scan left in the workspace) between
+    two events, into buffers of its own; the result must be the scan call's."""
+    from nlsh_amd import _capi
+    if ix.last_algo == _capi.SCAN_QUERY_MAJOR:
+        return None
+    Q = qg.shape[0]
+    ws = next(v for (_, bucket_major), v in ix._ws.items() if bucket_major)
+    od, oi = torch.empty((Q, k), dtype=torch.float32, device=qg.device), torch.empty((Q, k), dtype=torch.int32, device=qg.device)
+    ncand, status = torch.empty((Q,), dtype=torch.int32, device=qg.device), torch.zeros((2,), dtype=torch.int32, device=qg.device)
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for a, b in evs:
+        a.record()
+        ix._scan_launch(qg, keys, nkeys, k, ix.last_algo, ix._last_max_tasks, od, oi, None, ncand, status, ws, _capi.PHASE_MERGE, None, ix.last_window)
+        b.record()
+    torch.cuda.synchronize()
+    assert torch.equal(od.view(torch.int32), out[0].view(torch.int32)) and torch.equal(oi, out[1]) and torch.equal(ncand, out[2])
+    return float(np.mean([a.elapsed_time(b) for a, b in evs[1:]] or [evs[0][0].elapsed_time(evs[0][1])]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--algo", default="tiled")
@@ -33,6 +53,7 @@ def main():
     ap.add_argument("--tag", default="")
     ap.add_argument("--window", default="", help="comma-separated row windows of the small-bucket packing to time one after the other on the same index and keys (0 = one task list per bucket; empty = the facade's choice); one JSON line each")
     ap.add_argument("--rounds", type=int, default=1, help="repeat the --window list this many times, interleaved (A B C A B C ...), and end with a summary line: per window the median and the minimum of the rounds' mean scan times -- same-process A/B that clock drift cannot order")
+    ap.add_argument("--k", default="10", help="comma-separated k values timed one after the other on the same index and keys (k > 64: the tiled schedule only; the check against the query-major schedule, k <= 64 there, is skipped); with --rounds they are interleaved like the windows.  Each line also carries merge_kernel_ms: the MERGE phase alone, re-run on the partial lists the scan left")
     ap.add_argument("--metric", default="", choices=["", "l2", "cosine"], help="override the workload's metric (sift1m with cosine = the same buckets and candidates through the cosine bodies)")
     ap.add_argument("--l2-form", default="exact", choices=["exact", "folded"], help="folded: the opt-in 2-op L2 block (NLSH_METRIC_L2_EPS_FOLDED)")
     ap.add_argument("--stress", type=int, default=0, help="repeat the scan N more times and count results that differ from the first one in any bit (the tiled schedule's results do not depend on timing: any difference is a race)")
@@ -103,8 +124,9 @@ def main():
             ix._cells[w] = (cell_of, cell_offsets, new_t, nc)
         else:
             ix.bucket_order = new_t
-    windows = ([None] if not args.window else [int(w) for w in args.window.split(",")]) * max(1, args.rounds)
-    ref_out, first, by_window = None, None, {}
+    ks = [int(x) for x in args.k.split(",")]
+    configs = [(w, k) for w in ([None] if not args.window else [int(w) for w in args.window.split(",")]) for k in ks] * max(1, args.rounds)
+    ref_out, first, by_window = {}, {}, {}
     # rows of the buckets this batch probes at all (each counted once): what a schedule that fetches every needed row exactly once reads
     uk_ = ix.uniq_keys.cpu().numpy().astype(np.int64)
     kh_, nh_ = keys.cpu().numpy().astype(np.int64), nkeys.cpu().numpy()
@@ -112,9 +134,9 @@ def main():
     pos_ = np.searchsorted(uk_, flat_); pos_[pos_ >= len(uk_)] = 0
     probed_ = np.unique(pos_[uk_[pos_] == flat_])
     unique_rows, n_pairs = int(ix.bucket_sizes[probed_].sum()), int((uk_[pos_] == flat_).sum())
-    for window in windows:
+    for window, k in configs:
         ix.window_rows = window
-        ix.scan_tensors(qg, keys, nkeys, k=10)                      # sizes the task table
+        ix.scan_tensors(qg, keys, nkeys, k=k)                       # sizes the task table
         if args.tight:
             ix._max_tasks[ix._last_tkey] = int(args.tight * int(ix.last_status.cpu()[0])) + 1
         if args.zeros:
@@ -123,22 +145,24 @@ def main():
         for a, b in evs:
             a.record(); b.record()
         for _ in range(3):
-            ix.scan_tensors(qg, keys, nkeys, k=10, check=False)
+            ix.scan_tensors(qg, keys, nkeys, k=k, check=False)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.iters):
-            out = ix.scan_tensors(qg, keys, nkeys, k=10, check=False, events=evs[i])
+            out = ix.scan_tensors(qg, keys, nkeys, k=k, check=False, events=evs[i])
         torch.cuda.synchronize()
         scan_call_ms = 1e3 * (time.perf_counter() - t0) / args.iters
         kern = np.array([a.elapsed_time(b) for a, b in evs])
+        merge_ms = merge_phase_ms(ix, qg, keys, nkeys, k, args.iters, out)   # right behind the scan calls: their partial lists, their task table
         t0 = time.perf_counter()
         for i in range(args.iters):
-            ix.query_tensors(qg, k=10, hash_times=10, seed=7, check=False)
+            ix.query_tensors(qg, k=k, hash_times=10, seed=7, check=False)
         torch.cuda.synchronize()
         step_ms = 1e3 * (time.perf_counter() - t0) / args.iters
         dist, idx, nc, _ = out
         rec = {"tag": args.tag, "workload": args.workload, "l2_form": args.l2_form, "lib": os.path.basename(os.environ.get("NLSH_HIP_LIB", "default")), "algo": args.algo,
-               "scan_kernel_ms": float(kern.mean()), "scan_kernel_ms_min": float(kern.min()), "scan_phases_ms": scan_call_ms,
+               "k": k,
+               "scan_kernel_ms": float(kern.mean()), "scan_kernel_ms_min": float(kern.min()), "merge_kernel_ms": merge_ms, "scan_phases_ms": scan_call_ms,
                "step_ms": step_ms, "tasks": int(ix.last_status.cpu()[0]), "max_tasks": ix._last_max_tasks, "sum_candidates": int(nc.long().sum())}
         if os.environ.get("SCAN_BENCH_GROUPS"):   # pairs by the size of the query group they sit in (host recomputation from the keys)
             uk = ix.uniq_keys.cpu().numpy().astype(np.int64)
@@ -155,28 +179,29 @@ def main():
         if args.stress:
             bad = 0
             for i in range(args.stress):
-                o = ix.scan_tensors(qg, keys, nkeys, k=10, check=False)
+                o = ix.scan_tensors(qg, keys, nkeys, k=k, check=False)
                 bad += int(not (torch.equal(o[0], dist) and torch.equal(o[1], idx) and torch.equal(o[2], nc)))
             rec["stress_runs"], rec["stress_mismatches"] = args.stress, bad
-        if not args.no_check:
-            if ref_out is None:
+        if not args.no_check and k <= 64:                           # the query-major schedule takes k <= 64
+            if k not in ref_out:
                 ref = Indexer(hashing, cg, dist_fn, compat=compat, algo="query")
-                ref_out = ref.scan_tensors(qg, keys, nkeys, k=10)[:3]
+                ref_out[k] = ref.scan_tensors(qg, keys, nkeys, k=k)[:3]
                 del ref
-            d0, i0, n0 = ref_out
+            d0, i0, n0 = ref_out[k]
             rec["ncand_equal"] = bool(torch.equal(n0, nc))
             rec["ids_equal_frac"] = float((i0 == idx).all(1).float().mean())
             both = (i0 >= 0) & (idx >= 0)
             rec["max_abs_dist_diff"] = float((d0 - dist).abs()[both].max())
         rec["window_rows"], rec["workload"], rec["row_stride"] = ix.last_window, args.workload, ix.row_stride
         rec["pairs"], rec["probed_buckets"], rec["unique_probed_rows"], rec["unique_probed_bytes"] = n_pairs, int(len(probed_)), unique_rows, unique_rows * 4 * ix.dim
-        by_window.setdefault(ix.last_window, []).append(rec["scan_kernel_ms"])
+        by_window.setdefault(ix.last_window if len(ks) == 1 else f"{ix.last_window}/k={k}", []).append(rec["scan_kernel_ms"])
         if window:
             rec["n_cells"], rec["n_buckets"] = ix.cells(window)[3], ix.n_buckets
-        if first is None:
-            first = (dist, idx, nc)
+        if k not in first:
+            first[k] = (dist, idx, nc)
         else:   # every window size must give the first one's bits
-            rec["bits_equal_first_window"] = bool(torch.equal(dist.view(torch.int32), first[0].view(torch.int32)) and torch.equal(idx, first[1]) and torch.equal(nc, first[2]))
+            f = first[k]
+            rec["bits_equal_first_window"] = bool(torch.equal(dist.view(torch.int32), f[0].view(torch.int32)) and torch.equal(idx, f[1]) and torch.equal(nc, f[2]))
         print(json.dumps(rec), flush=True)
     if args.rounds > 1:
         print(json.dumps({"summary": args.workload, "rounds": args.rounds, "scan_kernel_ms_median_by_window": {str(w): float(np.median(v)) for w, v in by_window.items()},
