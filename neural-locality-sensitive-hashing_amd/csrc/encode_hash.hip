@@ -58,20 +58,11 @@ __device__ __forceinline__ void philox4x32_10(unsigned long long seed, uint32_t 
 // dynamic LDS a workgroup may ask for: the CU's 160 KB less the kernel's static variables (the lookup's two block counters, r06)
 constexpr size_t ENC_LDS_LIMIT = 160 * 1024 - 256;
 // Batches up to this many rows take the single-image 32-row form (2 x 256 CUs x 32 rows: every workgroup resident at once)
-#ifndef NLSH_ENC_BUILD_128
-#define NLSH_ENC_BUILD_128 1  // index-build launches: 1 = 128-row workgroups on one LDS image, 0 = 64-row workgroups on a ping-pong pair
-#endif
 #ifndef NLSH_ENC_SINGLE_MAX_ROWS
 #define NLSH_ENC_SINGLE_MAX_ROWS 16384
 #endif
 // Batches of at most this many rows take the 16-row form (H16): as long as its workgroups are at most one per CU (256 x 16 rows) it is
 // the shorter critical path (24.5 us against 27.2 for the 32-row form, 64 ... 4096 rows); beyond that it loses -- see the kernel.
-#ifndef NLSH_ENC_HET_PRIO
-#define NLSH_ENC_HET_PRIO 3   // wave priority of the 16-row workgroups of the balanced query-batch launch (-1: leave it alone)
-#endif
-#ifndef NLSH_ENC_HET
-#define NLSH_ENC_HET 1   // 0: every query batch of more than 4096 rows as 32-row workgroups (r02-r05), for A/B
-#endif
 #ifndef NLSH_ENC_H16_MAX_ROWS
 #define NLSH_ENC_H16_MAX_ROWS 4096
 #endif
@@ -638,10 +629,9 @@ __global__ __launch_bounds__(512, 1) void encode_hash_het_kernel(EncArgs a, Plan
         // A 16-row workgroup shares its CU with a 32-row one whose waves are older: at equal priority they keep the MFMA pipes, the
         // 16-row workgroup's first layer ends when the other's SECOND does (traced: 19 us for 1.9 us of pipe time) and its serial
         // tail -- output layer, key pass, lookup: 11 us -- then runs alone at the end of the launch.  With the higher issue priority
-        // the short workgroup goes first and the long one's layers absorb the delay (tools/enc_step_trace.py).
-#if NLSH_ENC_HET_PRIO >= 0
-        __builtin_amdgcn_s_setprio(NLSH_ENC_HET_PRIO);
-#endif
+        // the short workgroup goes first and the long one's layers absorb the delay (tools/enc_step_trace.py; 44.5 us at equal priority
+        // against 42.9, and 46.8 for 32-row workgroups only: DESIGN.md appendix A, r06).
+        __builtin_amdgcn_s_setprio(3);
         encode_hash_body<1, 8, true, 2, true>(a, pa, reinterpret_cast<float *>(smem4), (long long)n32 * 32 + (long long)(blockIdx.x - n32) * 16, blockIdx.x);
     }
 }
@@ -840,7 +830,7 @@ int encode_plan_fill(EncPlan &p, int64_t n, int n_layers, const int *dims, const
             // the rows behind the last FULL round of 32-row workgroups (one per CU), when they are at most half a round, as 16-row
             // workgroups of the same launch (encode_hash_het_kernel): 10^4 rows on 256 CUs = 256 x 32 + 113 x 16
             const long long round_rows = 32ll * device_cus(), rem = n % round_rows;
-            if (NLSH_ENC_HET && h16_ok && n > round_rows && rem > 0 && rem <= round_rows / 2) {
+            if (h16_ok && n > round_rows && rem > 0 && rem <= round_rows / 2) {
                 p.form = ENC_FORM_HET;
                 p.n32 = (unsigned)((n - rem) / 32);
                 p.grid = p.n32 + (unsigned)((rem + 15) / 16);
@@ -856,7 +846,7 @@ int encode_plan_fill(EncPlan &p, int64_t n, int n_layers, const int *dims, const
         // per 1M rows; of four waves owning two column tiles each (201 VGPRs): 1.92 ms at an in-kernel clock of 2.23 GHz -- against
         // 1.895 ms at 2.16 GHz for the form below.  The phases did overlap (tools/enc_trace.py) and the chip gave the gain back as
         // clock: clock x MFMA duty stayed put.
-        if (NLSH_ENC_BUILD_128 && max_np <= 32 * 8 && lds128 <= lds_limit) {
+        if (max_np <= 32 * 8 && lds128 <= lds_limit) {
             // index builds: 128 rows per workgroup on ONE image (accumulators of the four row tiles held in registers across the
             // layer barrier): a B fragment feeds 16 MFMAs instead of 8 and the per-layer fixed cost (write-back, barriers, ring
             // prologue: ~2.5-3.8 us) is paid once per 128 rows instead of once per 64

@@ -5,8 +5,8 @@
 // Diagnostic timing builds (`make VARIANT=diag EXTRA="-DNLSH_DIAG -DNLSH_ABLATE=n"`, tools/scan_bench.py): every switch below
 // produces WRONG results by design (it removes a piece of the kernel to time the rest) and exists only under NLSH_DIAG, so that a
 // stray -D on the shipped build cannot turn one on.  NLSH_ABLATE: 1 no distance math, 2 no global loads, 3 no top-k selection,
-// 4 no scalar loads (generic loop), 5 no epilogue, 6 neither math nor epilogue (staging skeleton), 7 tasks of <= 64 rows vanish,
-// 8 tasks of <= NLSH_ABLATE_NQ queries vanish, 9 every workgroup leaves after its descriptor loads, 11 no bisection in the
+// 5 no epilogue, 6 neither math nor epilogue (staging skeleton), 7 tasks of <= 64 rows vanish,
+// 8 tasks of <= 4 queries vanish, 9 every workgroup leaves after its descriptor loads, 11 no bisection in the
 // selection, 12 = 2 + 5 (no global loads, no epilogue), 13 = 2 + 6 (barriers and LDS writes only).  NLSH_NO_STAGE_BARRIER=1: the stage barriers of the hand-scheduled task body are removed (the four waves of a
 // workgroup race on the tile): what the barriers' straggler coupling costs (r03: 3-5 %).
 // (Two r03 experiments lived here behind switches and were deleted in r04, measured slower and never shipped: LDS-DMA staging of the
@@ -25,10 +25,6 @@
 #endif
 #define NLSH_ABLATE 0
 #define NLSH_NO_STAGE_BARRIER 0
-#endif
-
-#ifndef NLSH_SELECT_SHORT_PATHS
-#define NLSH_SELECT_SHORT_PATHS 1   // select_k_smallest: lists with no / fewer than k present keys skip the cut search and its compaction (0: r04's single path, for A/B; same results)
 #endif
 
 namespace nlsh {
@@ -171,13 +167,13 @@ __device__ __forceinline__ uint64_t select_k_smallest(const uint64_t (&key)[NK],
     }
     // r05: the two short cases first.  18-36 % of the tiled scan's lists reach this point with NO key below the query's published bound and
     // 23-41 % with fewer than k (profiles/r05_epilogue_counters_and_ablations.txt): neither needs a cut, and the general compaction below
-    // spends six compares per key slot re-deriving "present" from a cut that takes everything.
-    if (NLSH_SELECT_SHORT_PATHS && n == 0) {
+    // spends six compares per key slot re-deriving "present" from a cut that takes everything (r04's single path: same results, slower).
+    if (n == 0) {
         if constexpr (WIDE) select_pad_wide(out, 0, k, lane);
         else if (lane < k) out[lane] = KEY_NONE;
         return KEY_NONE;
     }
-    if (NLSH_SELECT_SHORT_PATHS && n < k) {
+    if (n < k) {
         int base0 = 0;
 #pragma unroll
         for (int i = 0; i < NK; ++i) {

@@ -1,4 +1,4 @@
-// The bucket lookup of the bucket-major PLAN phase, shared by its two homes (r06): `bplan_kernel` (scan_bucket.hip; caller-supplied key
+// The bucket lookup of the bucket-major PLAN phase, shared by its two homes (r06): `bplan_kernel` (scan_bucket_plan.h; caller-supplied key
 // tables) and the epilogue of `encode_hash_kernel` (encode_hash.hip; the keys are in the workgroup's LDS there, so the lookup rides in
 // the launch that made them and the batch has one dependent launch less).  Replaces, per (query, probe) pair, the reference's
 // `self.index2row.get(key, empty)` (nlsh/indexer.py:68) and the bookkeeping of its `for key in index_keys` loop (:66-83).

@@ -1,4 +1,4 @@
-"""Every hand-scheduled task body of the LDS-tiled scan (csrc/scan_bucket.hip: l2_task<NW, NQ, NTL, METRIC>, NQ = queries
+"""Every hand-scheduled task body of the LDS-tiled scan (csrc/scan_bucket_tiled.h: l2_task<NW, NQ, NTL, METRIC>, NQ = queries
 a wave holds 0..4, NTL = 64-row tiles of the task 1..4, L2 and cosine = 40 bodies, plus the odd-chunk tail of l2_kblock and
 the fat-stage geometry of short segments) on a deterministic index: buckets of chosen sizes, each probed by a chosen
 number of queries, so that the task table provably holds every (queries, tiles) shape -- asserted from the table the PLAN

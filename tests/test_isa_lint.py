@@ -100,3 +100,21 @@ def test_diagnostic_switches_exist_only_under_nlsh_diag():
     assert stray.returncode != 0 and "diagnostic builds only" in stray.stderr
     diag = subprocess.run(base + ["-DNLSH_DIAG", "-DNLSH_ABLATE=13", "-DNLSH_NO_STAGE_BARRIER=1"], capture_output=True, text=True)
     assert diag.returncode == 0, diag.stderr[-2000:]
+
+
+def test_compare_classes_two_builds_of_a_kernel():
+    old = ["s_load_dword s4, s[0:1], 0x0", "s_waitcnt lgkmcnt(0)", "v_mov_b32 v3, s4", ".LBB0_1:", "v_sub_f32 v1, s4, v2", "v_fmac_f32 v0, v1, v1",
+           "s_cbranch_scc1 .LBB0_1", "global_store_dword v3, v0, s[2:3]", "s_endpgm"]
+    res = {"VGPRs": 4, "Occupancy": 8}
+    assert isa_lint.compare(old, list(old), res, dict(res)) == "a"
+    # other register numbers and another label, the same program
+    renamed = [s.replace("s4", "s9").replace("v3", "v7").replace(".LBB0_1", ".LBB3_2") for s in old]
+    assert isa_lint.compare(old, renamed, res, dict(res)) == "b"
+    # the prologue in another order and with another register: first appearances no longer line up
+    moved = [old[2].replace("v3", "v5"), old[0], old[1]] + old[3:7] + [old[7].replace("v3", "v5"), old[8]]
+    assert isa_lint.compare(old, moved, res, dict(res)) == "c"
+    assert isa_lint.compare(old, moved, res, {"VGPRs": 5, "Occupancy": 8}) == "d"       # ... at another register budget
+    # the same opcodes, but the arithmetic loop's order differs
+    hot = old[:4] + [old[5], old[4]] + old[6:]
+    assert isa_lint.compare(old, hot, res, dict(res)) == "d"
+    assert isa_lint.compare(old, old + ["s_nop 0"], res, dict(res)) == "d"              # another instruction count

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ISA lint of the hand-scheduled scan kernels (CPU only: hipcc cross-compiles gfx950 without a GPU).
 
-The tiled scan issues `s_load_dword*` from inline asm (`load_qset`, `warm_query_lines` in csrc/scan_bucket.hip).  The
+The tiled scan issues `s_load_dword*` from inline asm (`load_qset`, `warm_query_lines` in csrc/scan_bucket_tiled.h, part of the translation unit scan_bucket.hip).  The
 compiler believes their outputs are written when the asm statement ends; the data lands later, at a hand-placed
 `s_waitcnt lgkmcnt(0)`.  That is correct only while nothing reads, copies or reassigns those SGPRs in between -- r02 hit
 exactly this (a throw-away destination was reused, the late write corrupted a live value, the kernel faulted).  This
@@ -16,7 +16,12 @@ into the same destination (the scalar-cache warm-up: the value is never read), i
 landing on one) is a violation.  Resource figures come from `-Rpass-analysis=kernel-resource-usage` of the same compile.
 
     python tools/isa_lint.py [--extra=-DNLSH_TILED_KB=8 ...] [--match bscan3_kernel] [--src scan_bucket.hip]
+
+`--compare OLD.s` classes every kernel of the source against an earlier build of it instead (a refactor's proof that the shipped code
+did not move): OLD.s is what `hipcc <BASE_FLAGS> -S --cuda-device-only -Rpass-analysis=kernel-resource-usage` wrote for the old
+source, OLD.remarks beside it that command's stderr.  See `compare`.
 """
+import collections
 import argparse
 import os
 import re
@@ -187,25 +192,61 @@ def spills_in_hot_loops(lines, hot="v_fmac_f32"):
     """SGPR spill traffic (v_writelane_b32, or a v_readlane_b32 of a constant lane into an SGPR: the compiler's spill / reload
     forms) inside any loop whose body holds the distance arithmetic.  Loop = a backward branch to a label; body = the lines between.
     Spills elsewhere (kernel arguments parked in a VGPR at the prologue, reloaded in the epilogue) cost nothing that matters."""
-    pos = {}
-    for i, s_ in enumerate(lines):
-        m = _LABEL.match(s_)
-        if m:
-            pos[m.group(1)] = i
     # the VGPRs the compiler spills SGPRs into = the destinations of the function's v_writelane_b32 (a v_readlane of a constant
     # lane from any other VGPR is ordinary code: wave reductions read lane 63)
     spill_vgprs = {x.split()[1].rstrip(",") for x in lines if x.startswith("v_writelane_b32")}
     bad = []
+    for body in _hot_loops(lines, hot):
+        for x in body:
+            r = re.match(r"^v_readlane_b32 s\d+, (v\d+), \d+$", x)
+            if x.startswith("v_writelane_b32") or (r and r.group(1) in spill_vgprs):
+                bad.append(x)
+    return bad
+
+
+def _hot_loops(lines, hot="v_fmac_f32"):
+    """Bodies of the loops (a backward branch to a label; body = the lines between) that hold the distance arithmetic."""
+    pos = {m.group(1): i for i, s_ in enumerate(lines) for m in [_LABEL.match(s_)] if m}
     for i, s_ in enumerate(lines):
         m = _BRANCH.match(s_)
-        if m and m.group(2) in pos and pos[m.group(2)] < i:
+        if m and pos.get(m.group(2), i) < i:
             body = lines[pos[m.group(2)]:i]
             if any(x.startswith(hot) for x in body):
-                for x in body:
-                    r = re.match(r"^v_readlane_b32 s\d+, (v\d+), \d+$", x)
-                    if x.startswith("v_writelane_b32") or (r and r.group(1) in spill_vgprs):
-                        bad.append(x)
-    return bad
+                yield body
+
+
+_RENUMBER = re.compile(r"\b[sva]\d+\b|\b[sva]\[\d+:\d+\]|\.L\w+")
+
+
+def _renumbered(lines):
+    """The lines with every register (range) and local label named by the order of its first appearance."""
+    names = {}
+    return [_RENUMBER.sub(lambda m: names.setdefault(m.group(0), "%s#%d" % (m.group(0)[0], len(names))), s) for s in lines]
+
+
+def _opcodes(lines):
+    return [s.split()[0] for s in lines if not _LABEL.match(s)]
+
+
+def compare(old, new, old_res=None, new_res=None):
+    """Class of one kernel's new instruction list against its old one: "a" identical; "b" identical after renumbering branch labels
+    and registers; "c" the same opcode multiset, the same resource figures and the same opcode sequence in every loop that holds
+    v_fmac_f32 (what spills_in_hot_loops calls a hot loop): the compiler ordered or allocated the code around the arithmetic
+    differently, the arithmetic loops and the occupancy are what they were; "d" anything else."""
+    if old == new:
+        return "a"
+    if _renumbered(old) == _renumbered(new):
+        return "b"
+    if (collections.Counter(_opcodes(old)) == collections.Counter(_opcodes(new)) and old_res == new_res
+            and [_opcodes(b) for b in _hot_loops(old)] == [_opcodes(b) for b in _hot_loops(new)]):
+        return "c"
+    return "d"
+
+
+def compare_builds(old_asm, old_remarks, new_asm, new_remarks):
+    """{kernel: class} over the kernels of either build (one that exists in only one of them is "d")."""
+    fo, fn, ro, rn = functions(old_asm), functions(new_asm), resources(old_remarks), resources(new_remarks)
+    return {k: compare(fo[k], fn[k], ro.get(k), rn.get(k)) if k in fo and k in fn else "d" for k in sorted(set(fo) | set(fn))}
 
 
 def lint(src="scan_bucket.hip", match="bscan3_kernel", extra=()):
@@ -228,7 +269,16 @@ def main():
     ap.add_argument("--src", default="scan_bucket.hip")
     ap.add_argument("--match", default="bscan3_kernel")
     ap.add_argument("--extra", action="append", default=[])
+    ap.add_argument("--compare", metavar="OLD.s", help="class every kernel of --src against this earlier build (see compare)")
     args = ap.parse_args()
+    if args.compare:
+        remarks = os.path.splitext(args.compare)[0] + ".remarks"
+        asm, new_remarks = compile_asm(args.src, tuple(args.extra))
+        rep = compare_builds(open(args.compare).read(), open(remarks).read() if os.path.exists(remarks) else "", asm, new_remarks)
+        res = resources(new_remarks)
+        for name, cls in rep.items():
+            print(cls, name, len(functions(asm).get(name, ())), "lines", res.get(name, {}))
+        sys.exit(int("d" in rep.values()))
     rep = lint(args.src, args.match, tuple(args.extra))
     rc = 0
     for name, r in rep.items():

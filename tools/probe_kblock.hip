@@ -1,4 +1,4 @@
-// Hardware probe: the tiled scan's hand-scheduled k-block (nlsh::l2_kblock<NQ, NT> from csrc/scan_bucket.hip, the very code the
+// Hardware probe: the tiled scan's hand-scheduled k-block (nlsh::l2_kblock<NQ, NT> from csrc/scan_bucket_tiled.h, which scan_bucket.hip includes: the very code the
 // kernel runs) in isolation -- LDS tile resident, no staging, no barriers, no epilogue -- at the kernel's occupancy.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/probe_kblock.hip neural-locality-sensitive-hashing_amd/csrc/capi.hip -o /tmp/probe_kblock
 #include "../neural-locality-sensitive-hashing_amd/csrc/scan_bucket.hip"
