@@ -32,6 +32,38 @@ def dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
+def task_table(indexer, Qn, P, k, d, full=False):
+    """(nq, nrows) of every task the last tiled scan laid out, read from the workspace through the diagnostic layout call;
+    full=True: the whole table [tasks, 4] plus the tasks' query ids and packed row ranges, each [tasks, 16]."""
+    import ctypes
+    from nlsh_amd import _capi
+    L = _capi.lib()
+    max_tasks = indexer._last_max_tasks                              # the table the LAST launch ran with (it may be trimmed afterwards)
+    off_task, off_q, off_r = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _capi.check(L.nlsh_scan_workspace_layout(Qn, P, k, max_tasks, indexer.n_buckets, d, _capi.SCAN_BUCKET_TILED,
+                                             ctypes.byref(off_task), ctypes.byref(off_q), ctypes.byref(off_r)))
+    ws = next(w for (stream, bm), w in indexer._ws.items() if bm)
+    n_tasks = int(indexer.last_status.cpu()[0])
+    tab = ws[off_task.value:off_task.value + 16 * n_tasks].view(torch.int32).view(-1, 4).cpu().numpy()
+    if not full:
+        return tab[:, 1], tab[:, 3]
+    assert off_r.value == off_q.value + 4                            # one interleaved table of {query id, row range} records
+    qr = ws[off_q.value:off_q.value + 128 * n_tasks].view(torch.int32).view(-1, 16, 2).cpu().numpy()
+    return tab, qr[:, :, 0], qr[:, :, 1]
+
+
+def fp64_distances(query, rows, metric):
+    """Plain fp64 numpy evaluation of the project's two distances on fp32 inputs (nlsh/data.py:201: sqrt(sum(((q - c) + 1e-6)^2));
+    nlsh/data.py:109: 1 - q.c / (max(|q|, 1e-8) * max(|c|, 1e-8))), the eps constants being the fp32 ones the kernels hold."""
+    q = np.asarray(query, dtype=np.float64)
+    c = np.asarray(rows, dtype=np.float64)
+    if metric == "l2":
+        return np.sqrt((((q - c) + np.float64(np.float32(1e-6))) ** 2).sum(1))
+    eps = np.float64(np.float32(1e-8))
+    qn = q / max(np.sqrt((q * q).sum()), eps)
+    return 1.0 - (c @ qn) / np.maximum(np.sqrt((c * c).sum(1)), eps)
+
+
 def check_topk_against_candidates(idx_row, dist_row, cand_rows, cand_d64, k, rtol=2e-5):
     """One query: returned (ids, distances) vs exact fp64 distances of ITS candidate set.
 

@@ -3,13 +3,12 @@ a wave holds 0..4, NTL = 64-row tiles of the task 1..4, L2 and cosine = 40 bodie
 the fat-stage geometry of short segments) on a deterministic index: buckets of chosen sizes, each probed by a chosen
 number of queries, so that the task table provably holds every (queries, tiles) shape -- asserted from the table the PLAN
 phase left in the workspace -- and the results are held to the oracle (L2: bit-identical; cosine: <= 2e-5)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from helpers import assert_lists_differ_only_at_ties, dev, make_hashing
+from helpers import task_table as _task_table
 from nlsh_amd import _capi, synth
 from oracle import oracle
 
@@ -41,24 +40,6 @@ def _build(d, metric, seed):
     key_lists[5].insert(2, 999999)                                  # an unknown key in the middle of a list
     assert max(len(ks) for ks in key_lists) <= _capi.MAX_PROBES
     return corpus, queries, corpus_keys, key_lists, buckets
-
-
-def _task_table(indexer, Qn, P, k, d, full=False):
-    """(nq, nrows) of every task the last tiled scan laid out, read from the workspace through the diagnostic layout call;
-    full=True: the whole table [tasks, 4] plus the tasks' query ids and packed row ranges, each [tasks, 16]."""
-    L = _capi.lib()
-    max_tasks = indexer._last_max_tasks                              # the table the LAST launch ran with (it may be trimmed afterwards)
-    off_task, off_q, off_r = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _capi.check(L.nlsh_scan_workspace_layout(Qn, P, k, max_tasks, indexer.n_buckets, d, _capi.SCAN_BUCKET_TILED,
-                                             ctypes.byref(off_task), ctypes.byref(off_q), ctypes.byref(off_r)))
-    ws = next(w for (stream, bm), w in indexer._ws.items() if bm)
-    n_tasks = int(indexer.last_status.cpu()[0])
-    tab = ws[off_task.value:off_task.value + 16 * n_tasks].view(torch.int32).view(-1, 4).cpu().numpy()
-    if not full:
-        return tab[:, 1], tab[:, 3]
-    assert off_r.value == off_q.value + 4                            # one interleaved table of {query id, row range} records
-    qr = ws[off_q.value:off_q.value + 128 * n_tasks].view(torch.int32).view(-1, 16, 2).cpu().numpy()
-    return tab, qr[:, :, 0], qr[:, :, 1]
 
 
 @pytest.mark.parametrize("d", [128, 100, 96, 72])
