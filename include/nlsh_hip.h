@@ -346,6 +346,19 @@ int nlsh_step_release(nlsh_step_t *step);   /* hold_done steps only: the batch e
  * the retry after status[1] = 1 (task table too small), with a larger max_tasks / workspace. */
 int nlsh_query_batch(const nlsh_step_desc_t *desc, size_t desc_bytes, const float *queries, int64_t q_stride, uint64_t seed,
                      int64_t row0, int lookup_done, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream);
+/* nlsh_query_batch for a caller that wants the results on the HOST: the same five launches with the host-writing form of the merge last
+ * (k <= NLSH_MAX_K, bucket-major schedules).  host_out [host memory mapped for the device: hipHostMalloc / hipHostRegister] receives,
+ * in int32 words,
+ *     ids [Q * k] (-1 past a short list, as out_idx) | candidate counts [Q] | status [2] | key rows [Q * (n_probes + 1)]
+ * where the key row of query q -- nkeys[q] followed by its n_probes keys of desc->qkeys -- is stored ONLY if the query has fewer than k
+ * candidates (the caller's special case, nlsh/indexer.py:89-93); the rows of the other queries are not touched.  The block is complete
+ * for the host once the stream has passed the call (an event or a stream synchronisation); no copy command is involved.
+ * desc->out_dist / out_idx / out_ncand are NOT written by this form; desc->status is, as by nlsh_query_batch (and copied into the block).
+ * host_words: words available at host_out, at least Q * (k + n_probes + 2) + 2.  Refused with NLSH_E_INVALID before anything is
+ * enqueued: a NULL or too small host_out, k > NLSH_MAX_K, the query-major schedule, a host_out the runtime does not report as host
+ * memory mapped for the device (hipPointerGetAttributes). */
+int nlsh_query_batch_host(const nlsh_step_desc_t *desc, size_t desc_bytes, const float *queries, int64_t q_stride, uint64_t seed,
+                          int64_t row0, int lookup_done, int32_t *host_out, size_t host_words, nlsh_stream_t stream);
 /* 1 while the slot's last batch has not left the tail stream, 0 once it has, < 0 on error.  Never blocks. */
 int nlsh_step_busy(nlsh_step_t *step);
 

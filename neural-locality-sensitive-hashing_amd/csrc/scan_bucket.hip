@@ -282,7 +282,10 @@ int bucket_scan_run(const BucketScanCall &c) {
     }
     if (c.phases & NLSH_PHASE_MERGE) {
         const dim3 gm((unsigned)((c.Q + 3) / 4));
-        if (c.k <= NLSH_MAX_K) hipLaunchKernelGGL(bmerge_kernel, gm, dim3(256), 0, s, a);
+        if (c.host_out) {
+            NLSH_REQUIRE(c.k <= NLSH_MAX_K, NLSH_E_UNSUPPORTED, "scan_topk(bucket-major): the host-writing merge takes k <= %d", NLSH_MAX_K);
+            hipLaunchKernelGGL(bmerge_host_kernel, gm, dim3(256), 0, s, a, c.host_out);
+        } else if (c.k <= NLSH_MAX_K) hipLaunchKernelGGL(bmerge_kernel, gm, dim3(256), 0, s, a);
         else if (c.k <= 128) hipLaunchKernelGGL(bmergew_kernel<2>, gm, dim3(256), 0, s, a);
         else if (c.k <= 192) hipLaunchKernelGGL(bmergew_kernel<3>, gm, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(bmergew_kernel<4>, gm, dim3(256), 0, s, a);

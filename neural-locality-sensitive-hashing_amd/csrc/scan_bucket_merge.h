@@ -1,12 +1,17 @@
 // Bucket-major scan, MERGE phase (part of the translation unit scan_bucket.hip, which defines BArgs in front of this file): one
 // wavefront merges the partial lists of a query's (probe, segment) pairs into its final top-k; bmerge_kernel for k <= 64,
-// bmergew_kernel<KPL> for k up to NLSH_MAX_K_TILED.
+// bmergew_kernel<KPL> for k up to NLSH_MAX_K_TILED.  bmerge_host_kernel is bmerge_kernel for a caller that wants the results on the
+// HOST (nlsh_query_batch_host): same merge, the ids / counts / status words / key rows of the short queries stored into one
+// host-visible block instead of the device outputs.
 #pragma once
 
 namespace nlsh {
 
 // Merge of ONE query's partial lists into its final top-k (one wavefront; `sc` = 64 u64 of LDS scratch owned by the wave).
-__device__ __forceinline__ void merge_query(const BArgs &a, long long q, int lane, uint64_t *sc, int2 *ltab) {
+// HOST: nothing is stored to the device outputs -- the ordered ids go to `stage_ids` (k words of LDS, the workgroup stores its queries' rows
+// as one run) and the candidate count is returned.
+template <bool HOST = false>
+__device__ __forceinline__ int merge_query(const BArgs &a, long long q, int lane, uint64_t *sc, int2 *ltab, int32_t *stage_ids = nullptr) {
     // lane p holds probe p's record (written by bscatter): where its partial lists are.  bscatter writes a record for EVERY slot of
     // the [Q, P] table -- zeros for slots past the query's key count, for repeated keys and for keys without a bucket -- so the key
     // count is not needed here (r04: its load sat in front of the record load, one dependent round trip per wave)
@@ -18,10 +23,9 @@ __device__ __forceinline__ void merge_query(const BArgs &a, long long q, int lan
         t0_l = rec.x; j_l = rec.y; size_l = rec.z; ng_l = rec.w;
         ns_l = (size_l + a.seg - 1) / a.seg;
     }
-    {   // n_candidates of the query (indexer.py:71,94) = rows of its probed buckets
-        const int c = __builtin_amdgcn_readlane(wave_incl_scan_i32(size_l), 63);
-        if (lane == 0) a.out_ncand[q] = c;
-    }
+    // n_candidates of the query (indexer.py:71,94) = rows of its probed buckets
+    const int c = __builtin_amdgcn_readlane(wave_incl_scan_i32(size_l), 63);
+    if (!HOST && lane == 0) a.out_ncand[q] = c;
     // The query's partial lists (one per probe and row segment) are numbered 0..L-1 by an inclusive scan of the
     // per-probe segment counts.  A round fetches 3 x R lists (R = 64/k per load instruction: lane -> (list, entry)) and
     // SELECTS the k best of them and the best so far (merge_round); typical queries (<= 18 lists at k = 10) take one round.
@@ -82,7 +86,9 @@ __device__ __forceinline__ void merge_query(const BArgs &a, long long q, int lan
             carry = merge_round<4>(key, a.k, lane, sc);
         }
     }
-    merge_finish(carry, a.k, lane, a.out_dist, a.out_idx, a.out_keys, q);
+    if (HOST) merge_finish_ids(carry, a.k, lane, stage_ids);
+    else merge_finish(carry, a.k, lane, a.out_dist, a.out_idx, a.out_keys, q);
+    return c;
 }
 
 // merge_query for k in 65..NLSH_MAX_K_TILED (the tiled schedule only): the same records, the same list table and the same search for
@@ -160,6 +166,46 @@ __global__ __launch_bounds__(256) void bmerge_kernel(BArgs a) {
     __shared__ uint64_t scratch[4][64];
     __shared__ int2 list_tab[4][128];    // merge_query's LIST_TAB entries per wave
     if (q < a.Q) merge_query(a, q, lane, scratch[threadIdx.x >> 6], list_tab[threadIdx.x >> 6]);
+}
+
+// The merge of nlsh_query_batch_host (k <= 64): `host` is a host-visible block of int32 words,
+//     ids [Q * k] | counts [Q] | status [2] | key rows of the short queries [Q * (P + 1)]
+// A workgroup's four queries are consecutive, so their id rows are ONE contiguous run of 4 * k words (160 bytes at k = 10) and their counts
+// one of 4: the waves leave the ordered ids and the count in LDS and the workgroup stores each run with consecutive lanes, 16 bytes per
+// lane where the run starts on a 16-byte boundary and is whole (always, but for the batch's last workgroup, when the block is 16-byte
+// aligned and Q * k a multiple of 4) -- ten 16-byte stores of one instruction per workgroup towards the host link instead of forty
+// scattered 4-byte ones of four (the block is uncached for the device: every store instruction leaves as the partial lines it covers).
+// Only a query with fewer than k candidates (the caller's special case: the reference's F7 rule) also stores its key row, nkeys[q] and
+// its P keys, at the query's own row of the last block; the rows of the other queries are not touched.  Nothing is stored to out_dist /
+// out_idx / out_ncand; the status words stay on the device as well and the first workgroup copies them (the scan kernel, earlier on the
+// stream, was the last to set them).  Plain vector stores; the end of the kernel makes them visible to the host.
+__global__ __launch_bounds__(256) void bmerge_host_kernel(BArgs a, int32_t *host) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long q0 = (long long)blockIdx.x * 4, q = q0 + wave;
+    __shared__ uint64_t scratch[4][64];
+    __shared__ int2 list_tab[4][128];
+    __shared__ __attribute__((aligned(16))) int32_t ids[4 * 64];      // the workgroup's id rows, packed: query w's row at [w * k, (w + 1) * k)
+    __shared__ __attribute__((aligned(16))) int32_t counts[4];
+    if (q < a.Q) {
+        const int c = merge_query<true>(a, q, lane, scratch[wave], list_tab[wave], ids + wave * a.k);
+        if (lane == 0) counts[wave] = c;
+        if (c < a.k) {       // wave-uniform
+            int32_t *row = host + a.Q * a.k + a.Q + 2 + q * (a.P + 1);
+            if (lane == 0) row[0] = a.nkeys[q];
+            if (lane < a.P) row[1 + lane] = a.qkeys[q * a.P + lane];
+        }
+    }
+    __syncthreads();
+    const int nq = (int)(a.Q - q0 < 4 ? a.Q - q0 : 4);
+    const int t = threadIdx.x, n_ids = nq * a.k;
+    int32_t *ids_out = host + q0 * a.k, *counts_out = host + a.Q * a.k + q0;
+    if ((((uintptr_t)ids_out & 15) | (n_ids & 3)) == 0) {      // workgroup-uniform
+        if (t < n_ids / 4) reinterpret_cast<int4 *>(ids_out)[t] = reinterpret_cast<const int4 *>(ids)[t];
+    } else if (t < n_ids) ids_out[t] = ids[t];
+    if (nq == 4 && ((uintptr_t)counts_out & 15) == 0) {
+        if (t == 0) *reinterpret_cast<int4 *>(counts_out) = *reinterpret_cast<const int4 *>(counts);
+    } else if (t < nq) counts_out[t] = counts[t];
+    if (blockIdx.x == 0 && t < 2) host[a.Q * a.k + a.Q + t] = a.status[t];
 }
 
 // Wide-k merge (k in 65..NLSH_MAX_K_TILED): KPL = ceil(k / 64) keys per lane, one list = KPL coalesced loads of the wave.

@@ -281,6 +281,21 @@ __device__ __forceinline__ void merge_finish(uint64_t carry, int k, int lane, fl
     }
 }
 
+// merge_finish for a caller that wants only the ids, in a buffer of its own (k words, LDS): same order, -1 past a short list.
+// (The ranking loop is merge_finish's, repeated: with the loop in a helper shared by both, bmerge_kernel and merge_shards_kernel no longer
+// compile to the parent's instructions -- tools/isa_lint.py --compare classes them d -- and the narrow merge is bound by its instruction count.)
+__device__ __forceinline__ void merge_finish_ids(uint64_t carry, int k, int lane, int32_t *ids) {
+    int rank = 0;
+    for (int j = 0; j < k; ++j) {
+        const uint64_t kj = read_lane64(carry, j);
+        rank += (kj < carry || (kj == carry && j < lane)) ? 1 : 0;
+    }
+    if (lane < k) {
+        const bool none = carry == KEY_NONE;
+        ids[none ? lane : rank] = none ? -1 : (int32_t)(uint32_t)carry;
+    }
+}
+
 // Wide k (65..NLSH_MAX_K_TILED = 256): the same merge by selection with KPL = ceil(k / 64) keys per lane -- entry e of a k-key list sits in
 // register e / 64 of lane e % 64.  A round selects the k best of the carry and of NL new lists (NK = KPL * (1 + NL) <= 8 keys per lane) into
 // the wave's LDS scratch (k keys; NLSH_MAX_K_TILED of them per wave are reserved) and reads the carry back from it.
@@ -412,6 +427,8 @@ struct BucketScanCall {
     const int32_t *cell_offsets;
     int n_cells;
     int plan_blocks;              // NLSH_PHASE_PLAN_REST: workgroups of the encode_hash launch that did the lookup (entries of `hits`)
+    int32_t *host_out;            // nlsh_query_batch_host: the MERGE phase (k <= NLSH_MAX_K) stores its results into this host-visible block
+                                  // (layout: bmerge_host_kernel) instead of out_dist / out_idx / out_ncand; nullptr everywhere else
 };
 // internal phase bit (not part of the C ABI's phase mask): the PLAN phase WITHOUT the bucket lookup, which the batch's encode_hash
 // launch already did in its epilogue (scan_plan.h, encode_plan_fuse_lookup): bscan + bscatter only

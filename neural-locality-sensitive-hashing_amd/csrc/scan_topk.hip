@@ -378,7 +378,7 @@ int nlsh::scan_topk_cells_phase_checked(const float *corpus_sorted, int64_t row_
         BucketScanCall c = {corpus_sorted, row_stride, d, gid, uniq_keys, offsets, n_buckets, inv_norm, queries, q_stride, Q,
                             qkeys, nkeys, P, k, metric, seg_rows, out_dist, out_idx, out_keys, out_ncand, status, workspace,
                             workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end, s, algo == NLSH_SCAN_BUCKET_TILED, bucket_order, phases,
-                            cell_of, cell_offsets, (int)n_cells, plan_blocks};
+                            cell_of, cell_offsets, (int)n_cells, plan_blocks, nullptr};
         if (call_out) { *call_out = c; return NLSH_OK; }
         return bucket_scan_run(c);
     }

@@ -348,3 +348,61 @@ extern "C" int nlsh_query_batch(const nlsh_step_desc_t *desc, size_t desc_bytes,
     }
     return scan_call(*desc, queries, q_stride, ev_scan_begin, ev_scan_end, stream, plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, plan_blocks, nullptr);
 }
+
+// nlsh_query_batch for a caller that wants the batch's results on the HOST (`Indexer.query`): the same five launches, the last one the
+// host-writing form of the merge (scan_bucket_merge.h, bmerge_host_kernel), which stores ids, candidate counts, the status words and the
+// key rows of the queries with fewer than k candidates straight into `host_out` -- no device->host copy command follows the kernels.
+// Every argument is checked before anything is enqueued.
+extern "C" int nlsh_query_batch_host(const nlsh_step_desc_t *desc, size_t desc_bytes, const float *queries, int64_t q_stride, uint64_t seed, int64_t row0,
+                                     int lookup_done, int32_t *host_out, size_t host_words, nlsh_stream_t stream) {
+    NLSH_REQUIRE(desc, NLSH_E_INVALID, "query_batch_host: null pointer");
+    NLSH_REQUIRE(desc_bytes == sizeof(nlsh_step_desc_t), NLSH_E_INVALID, "query_batch_host: descriptor of %zu bytes, this library's is %zu (ABI %d)", desc_bytes,
+                 sizeof(nlsh_step_desc_t), NLSH_ABI_VERSION);
+    NLSH_REQUIRE(desc->Q >= 0 && desc->Q < (1ll << 31), NLSH_E_INVALID, "query_batch_host: Q=%lld", (long long)desc->Q);
+    NLSH_REQUIRE(host_out, NLSH_E_INVALID, "query_batch_host: host_out is null");
+    NLSH_REQUIRE(desc->k >= 1 && desc->k <= NLSH_MAX_K, NLSH_E_INVALID, "query_batch_host: k=%d not in [1,%d] (the host-writing merge; nlsh_query_batch takes wider k)",
+                 desc->k, NLSH_MAX_K);
+    NLSH_REQUIRE(desc->algo == NLSH_SCAN_BUCKET_MAJOR || desc->algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_INVALID,
+                 "query_batch_host: algo=%d: only the bucket-major schedules (1, 2) have a host-writing merge", desc->algo);
+    NLSH_REQUIRE(desc->n_probes >= 1 && desc->n_probes <= NLSH_MAX_PROBES, NLSH_E_UNSUPPORTED, "query_batch_host: n_probes=%d not in [1,%d] (one scan call per batch)",
+                 desc->n_probes, NLSH_MAX_PROBES);
+    const size_t need = (size_t)desc->Q * (size_t)(desc->k + 1 + desc->n_probes + 1) + 2;   // ids | counts | status | key rows
+    NLSH_REQUIRE(host_words >= need, NLSH_E_INVALID, "query_batch_host: host_out of %zu words, Q=%lld k=%d n_probes=%d need %zu", host_words, (long long)desc->Q,
+                 desc->k, desc->n_probes, need);
+    if (desc->Q == 0) return NLSH_OK;
+    NLSH_REQUIRE(queries, NLSH_E_INVALID, "query_batch_host: null pointer");
+    NLSH_REQUIRE(desc->n_layers >= 1 && desc->n_layers <= NLSH_MAX_LAYERS && desc->dims && desc->dims[0] == desc->d, NLSH_E_INVALID,
+                 "query_batch_host: n_layers=%d, encoder input vs corpus dimension %d", desc->n_layers, desc->d);
+    // the kernel stores through the DEVICE's address of the block: it must be host memory the runtime has mapped for the device
+    // (hipHostMalloc / hipHostRegister, a pinned tensor), from its first word to its last
+    int32_t *mapped = nullptr;
+    for (const int32_t *p : {(const int32_t *)host_out, (const int32_t *)host_out + (need - 1)}) {
+        hipPointerAttribute_t at;
+        const hipError_t e = hipPointerGetAttributes(&at, p);
+        if (e != hipSuccess) (void)hipGetLastError();     // memory the runtime does not know: an answer, not a failure to keep
+        NLSH_REQUIRE(e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer != nullptr, NLSH_E_INVALID,
+                     "query_batch_host: host_out is not host memory mapped for the device (hipHostMalloc / hipHostRegister; a device pointer is refused)");
+        if (!mapped) mapped = (int32_t *)at.devicePointer;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    BucketScanCall c;      // the scan call's own checks, on the host, before the encode is launched
+    int rc = scan_call(*desc, queries, q_stride, nullptr, nullptr, stream, NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, 0, &c);
+    if (rc != NLSH_OK) return rc;
+    {
+        PlanArgs pa;
+        rc = bucket_scan_plan_args(c, &pa);     // workspace size
+        if (rc != NLSH_OK) return rc;
+    }
+    int plan_phase = NLSH_PHASE_PLAN, plan_blocks = 0;
+    if (!lookup_done) {
+        EncPlan enc;
+        rc = encode_plan_fill(enc, desc->Q, desc->n_layers, desc->dims, desc->packed, desc->act, desc->key_mode, desc->n_probes, desc->n_multi_rows, row0, nullptr,
+                              nullptr, nullptr, desc->qkeys, desc->nkeys);
+        if (rc == NLSH_OK) rc = launch_encode(enc, *desc, queries, q_stride, seed, s, &plan_phase, &plan_blocks);
+        if (rc != NLSH_OK) return rc;
+    }
+    c.phases = plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE;
+    c.plan_blocks = plan_blocks;
+    c.host_out = mapped;
+    return bucket_scan_run(c);
+}

@@ -32,6 +32,7 @@ SYMBOLS = (
     "nlsh_scan_workspace", "nlsh_scan_workspace_layout", "nlsh_scan_topk", "nlsh_scan_topk_phase", "nlsh_scan_topk_cells_phase",
     "nlsh_merge_topk",
     "nlsh_step_create", "nlsh_step_create_graph", "nlsh_step_destroy", "nlsh_step_set_weights", "nlsh_query_step_enqueue", "nlsh_step_release", "nlsh_step_busy", "nlsh_query_batch",
+    "nlsh_query_batch_host",
 )
 
 
@@ -140,6 +141,8 @@ def lib():
     L.nlsh_query_step_enqueue.argtypes = [vp, vp, i64, u64, vp, vp, vp]
     L.nlsh_query_batch.restype = i32
     L.nlsh_query_batch.argtypes = [ctypes.POINTER(StepDesc), sz, vp, i64, u64, i64, i32, vp, vp, vp]
+    L.nlsh_query_batch_host.restype = i32
+    L.nlsh_query_batch_host.argtypes = [ctypes.POINTER(StepDesc), sz, vp, i64, u64, i64, i32, vp, sz, vp]
     _lib = L
     return L
 

@@ -651,7 +651,7 @@ class Indexer:
     # weight walk, argument tuples) was 0.08 ms per range = 0.2 ms of a 1.1-ms call (tools/query_host_profile.py).  `query_tensors`
     # hands its tensors to the caller and keeps allocating fresh ones.  Like the scan workspace (one per stream), the kept buffers
     # assume one `query()` at a time per indexer and stream.
-    def _range_plan(self, q, keys, nkeys, k, lo, hi, algo, hash_times, n_multi):
+    def _range_plan(self, q, keys, nkeys, k, lo, hi, algo, hash_times, n_multi, host=None):
         import ctypes
         Q_all, P = keys.shape
         dev, m = q.device, hi - lo
@@ -668,7 +668,11 @@ class Indexer:
         wkey = (stream, True)
         ws = self._ws.get(wkey)
         sig = self._hashing._weights_signature()
-        if plan is not None and plan["max_tasks"] == max_tasks and plan["ws"] is ws and plan["window"] == window:
+        # `host`: the range's slice of the pinned result block (`_host_form`); the plan keeps its address and size only (a reference would
+        # hold an outgrown block's pinned pages for as long as the plan lives) -- the block is reallocated when a larger batch shape
+        # arrives, and a plan that names another address than the call's slice is rebuilt before it is used
+        host_ptr = None if host is None else host.data_ptr()
+        if plan is not None and plan["max_tasks"] == max_tasks and plan["ws"] is ws and plan["window"] == window and plan["host_ptr"] == host_ptr:
             if plan["sig"] != sig:        # a training step between two calls: the descriptor gets the new blob
                 plan["packed"] = self._hashing.packed_weights()
                 plan["desc"].packed = plan["packed"].data_ptr()
@@ -694,16 +698,25 @@ class Indexer:
             out_keys=ok, out_ncand=nc, status=st, workspace=wsp, workspace_bytes=wsb, max_tasks=mt, front=None, plan=None, mid=None, tail=None)
         plan = plans[ckey] = dict(desc=desc, ref=ctypes.byref(desc), size=ctypes.sizeof(desc), dims_arr=dims_arr, packed=self._hashing.packed_weights(), sig=sig,
                                   keys=rk, nkeys=rn, out_dist=out_dist, pack=pack, status=status, ws=ws, wkey=wkey, max_tasks=max_tasks, tkey=tkey,
-                                  window=window, stream=stream, order_rotates=bool(self.alternate_order))
+                                  window=window, stream=stream, order_rotates=bool(self.alternate_order), host_ptr=host_ptr,
+                                  host_words=0 if host is None else host.numel())
         if len(plans) > 64:           # batch shapes come and go (a caller sweeping Q): keep the dictionary bounded
             for old_key in list(plans)[:-32]:
                 del plans[old_key]
         return plan
 
-    def _range_tensors(self, q, keys, nkeys, k, lo, hi, algo, fused):
+    def _host_form(self, k, fused):
+        """Whether a row range's results reach the host from the merge kernel itself (`nlsh_query_batch_host`: no copy command behind the
+        kernels) -- the fused call with k <= 64.  Everything else (a streamed encoder, the query-major schedule, hash_times > 64: not
+        `fused`; wide k; the schedule-order experiment) keeps the device->host copies."""
+        return fused is not None and k <= _capi.MAX_K and not self.alternate_order
+
+    def _range_tensors(self, q, keys, nkeys, k, lo, hi, algo, fused, host=None):
         """One row range of a `query()` batch on the stream: `fused` = (hash_times, seed, rows of the batch that are multi-probe) --
         the range is hashed AND scanned by one `nlsh_query_batch` call into its slice of the batch's key table; None: the table was
-        filled by a whole-batch `hash_device` and the range is only scanned."""
+        filled by a whole-batch `hash_device` and the range is only scanned.  `host` (`_host_form`): the range's slice of the pinned
+        result block -- the call is `nlsh_query_batch_host`, whose merge kernel stores ids | counts | status | the short queries' key rows
+        there, and nothing has to be copied afterwards."""
         if fused is None:
             self.scan_tensors(q[lo:hi], keys[lo:hi], nkeys[lo:hi], k=k, check=False, algo=algo)
             return
@@ -712,10 +725,14 @@ class Indexer:
             self._batch_tensors(q[lo:hi], k, hash_times, seed, check=False, algo=algo, row0=lo, n_multi=min(max(n_multi - lo, 0), hi - lo),
                                 out=(keys[lo:hi], nkeys[lo:hi]))
             return
-        plan = self._range_plan(q, keys, nkeys, k, lo, hi, algo, hash_times, n_multi)
+        plan = self._range_plan(q, keys, nkeys, k, lo, hi, algo, hash_times, n_multi, host)
         qr = q[lo:hi]
         try:
-            _capi.check(_capi.lib().nlsh_query_batch(plan["ref"], plan["size"], qr.data_ptr(), qr.stride(0), seed, lo, 0, None, None, plan["stream"]))
+            if host is not None:
+                _capi.check(_capi.lib().nlsh_query_batch_host(plan["ref"], plan["size"], qr.data_ptr(), qr.stride(0), seed, lo, 0, plan["host_ptr"],
+                                                              plan["host_words"], plan["stream"]))
+            else:
+                _capi.check(_capi.lib().nlsh_query_batch(plan["ref"], plan["size"], qr.data_ptr(), qr.stride(0), seed, lo, 0, None, None, plan["stream"]))
         except _capi.NlshHipError:
             self._ws.pop(plan["wkey"], None)    # a call that failed part-way may have left the counters at the head non-zero
             self._range_plans.clear()
@@ -725,29 +742,38 @@ class Indexer:
         self._last_pack, self._last_tkey, self._last_max_tasks = plan["pack"], plan["tkey"], plan["max_tasks"]
 
     def _host_results(self, q, keys, nkeys, k, fused=None):
-        """Scan + device->host copies of (ids, candidate counts, status) and of the key table into pinned buffers + ONE
-        stream synchronisation: the only sync of a `query()` call (the key table rides along because the F7 rule needs
-        the key sets of the few queries with < k candidates: 400 KB more on the wire is cheaper than a second round of
+        """One range = the whole batch: scan, results into the pinned block, ONE stream synchronisation (the only sync of a `query()`
+        call).  `_host_form`: the merge kernel stores ids | counts | status | the short queries' key rows there itself and nothing is
+        copied.  Otherwise: device->host copies of (ids, candidate counts, status) and of the key table (it rides along because the F7
+        rule needs the key sets of the few queries with < k candidates: 400 KB more on the wire is cheaper than a second round of
         device indexing + copies + syncs after the first).  Repeats the scan if the task table overflowed."""
         Q, P = keys.shape
         algo = self.choose_algo(Q, P)
+        n, nk = Q * k + Q + 2, Q * P + Q
+        host_form = self._host_form(k, fused) and Q > 0
         while True:
-            self._range_tensors(q, keys, nkeys, k, 0, Q, algo, fused)
-            pack, tkey = self._last_pack, self._last_tkey
-            n, nk = pack.numel(), Q * P + Q
             pin = self._pin
             if pin is None or pin.numel() < n + nk:
                 pin = self._pin = torch.empty((max(n + nk, 1 << 16),), dtype=torch.int32, pin_memory=True)
-            pin[:n].copy_(pack, non_blocking=True)
-            if self.compat:
-                pin[n:n + Q * P].view(Q, P).copy_(keys, non_blocking=True)
-                pin[n + Q * P:n + nk].copy_(nkeys, non_blocking=True)
+            if host_form:           # the merge kernel stores into the pinned block itself: nothing to copy
+                self._range_tensors(q, keys, nkeys, k, 0, Q, algo, fused, pin[:n + nk])
+                tkey = self._last_tkey
+            else:
+                self._range_tensors(q, keys, nkeys, k, 0, Q, algo, fused)
+                pack, tkey = self._last_pack, self._last_tkey
+                pin[:n].copy_(pack, non_blocking=True)
+                if self.compat:
+                    pin[n:n + Q * P].view(Q, P).copy_(keys, non_blocking=True)
+                    pin[n + Q * P:n + nk].copy_(nkeys, non_blocking=True)
             self._release_held()                                    # the device is busy now: free what an earlier call left with us
             torch.cuda.current_stream(q.device).synchronize()
             host = pin.numpy()
             needed, overflow = int(host[n - 2]), int(host[n - 1])
             if not overflow or Q == 0:
                 self._trim_task_table(tkey, needed, self._last_max_tasks)
+                if host_form:       # key rows [Q, P + 1]: nkeys, then the keys -- written for the queries with < k candidates only
+                    rows = host[n:n + nk].reshape(Q, P + 1)
+                    return host[:Q * k].reshape(Q, k), host[Q * k:Q * k + Q], rows[:, 1:], rows[:, 0]
                 return (host[:Q * k].reshape(Q, k), host[Q * k:Q * k + Q], host[n:n + Q * P].reshape(Q, P), host[n + Q * P:n + nk])
             self._grow_task_table(tkey, needed, overflow)
 
@@ -775,23 +801,27 @@ class Indexer:
         stream = torch.cuda.current_stream(dev)
         bounds = [(Q * c // n_chunks, Q * (c + 1) // n_chunks) for c in range(n_chunks)]
         per = max(hi - lo for lo, hi in bounds)
-        words = per * k + per + 2 + per * P + per
+        words = (per * k + per + 2 + per * P + per + 3) // 4 * 4     # every range's block starts on a 16-byte boundary (the host-writing merge stores 16 bytes per lane there)
         if self._pin is None or self._pin.numel() < n_chunks * words:
             self._pin = torch.empty((max(n_chunks * words, 1 << 16),), dtype=torch.int32, pin_memory=True)
         pin = self._pin
         inflight = []
+        host_form = self._host_form(k, fused)
 
         def launch(c, lo, hi):
-            self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused)
-            pack, tkey = self._last_pack, self._last_tkey
-            base, n, m = c * words, pack.numel(), hi - lo
-            pin[base:base + n].copy_(pack, non_blocking=True)
-            if self.compat:
-                pin[base + n:base + n + m * P].view(m, P).copy_(keys[lo:hi], non_blocking=True)
-                pin[base + n + m * P:base + n + m * P + m].copy_(nkeys[lo:hi], non_blocking=True)
+            base, m = c * words, hi - lo
+            n = m * k + m + 2
+            if host_form and m:     # the merge kernel stores into the range's slice of the pinned block itself: nothing to copy
+                self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused, pin[base:base + n + m * P + m])
+            else:
+                self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused)
+                pin[base:base + n].copy_(self._last_pack, non_blocking=True)
+                if self.compat:
+                    pin[base + n:base + n + m * P].view(m, P).copy_(keys[lo:hi], non_blocking=True)
+                    pin[base + n + m * P:base + n + m * P + m].copy_(nkeys[lo:hi], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(stream)
-            return ev, pack, tkey, self._last_max_tasks
+            return ev, n, self._last_tkey, self._last_max_tasks
 
         for c, (lo, hi) in enumerate(bounds):
             inflight.append(launch(c, lo, hi))
@@ -800,9 +830,9 @@ class Indexer:
         for c, (lo, hi) in enumerate(bounds):
             m = hi - lo
             while True:
-                ev, pack, tkey, max_tasks = inflight[c]
+                ev, n, tkey, max_tasks = inflight[c]
                 ev.synchronize()
-                base, n = c * words, pack.numel()
+                base = c * words
                 needed, overflow = int(host[base + n - 2]), int(host[base + n - 1])
                 if not overflow or m == 0:
                     self._trim_task_table(tkey, needed, max_tasks)
@@ -810,7 +840,11 @@ class Indexer:
                 self._grow_task_table(tkey, needed, overflow)       # task table too small for this range: grow, repeat it
                 inflight[c] = launch(c, lo, hi)
             a = host[base:base + n + m * P + m]
-            yield (lo, hi, a[:m * k].reshape(m, k), a[m * k:m * k + m], a[n:n + m * P].reshape(m, P), a[n + m * P:n + m * P + m])
+            if host_form and m:     # key rows [m, P + 1]: nkeys, then the keys -- written for the queries with < k candidates only
+                rows = a[n:].reshape(m, P + 1)
+                yield (lo, hi, a[:m * k].reshape(m, k), a[m * k:m * k + m], rows[:, 1:], rows[:, 0])
+            else:
+                yield (lo, hi, a[:m * k].reshape(m, k), a[m * k:m * k + m], a[n:n + m * P].reshape(m, P), a[n + m * P:n + m * P + m])
 
     # The fresh result lists (10^4 per batch) land in the collector's youngest generation; the first container allocation after
     # the conversion then runs a generation-0 collection that walks all of them: 0.25-0.32 ms of a 1.55 ms call on the bench box
