@@ -371,6 +371,34 @@ int nlsh_step_busy(nlsh_step_t *step);
 int nlsh_merge_topk(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,
                     float *out_dist, int32_t *out_idx, int32_t *out_ncand, nlsh_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact brute-force k-NN: every row of `corpus` against every query, fp32-MFMA distances with the top-k fused behind them.
+ * Replaces the reference's mm + topk precompute (precompute.py:22-67): ground truth of a query set, self-kNN of a training set.
+ * Distances take precompute.py's forms, NOT the scan's pairwise_distance form (no square root, no epsilon):
+ *   NLSH_EXACT_L2      (||c||^2 - 2 (q.c)) + ||q||^2                    squared L2
+ *   NLSH_EXACT_COSINE  1 - ((q.c) * inv||q||) * inv||c||,  inv||x|| = 1 / max(||x||, 1e-12)
+ * Every dot product (q.c and the squared norms) is ONE fp32 chain over the dimension, ascending from 0 (an fmaf chain; for q.c the
+ * accumulator chain of v_mfma_f32_32x32x2_f32, which is the same bits): the distance of a (query, row) pair depends on the two vectors
+ * alone, never on the tile, the column split or the launch shape -- results are bitwise identical for every `splits`.
+ * Order: ascending 64-bit key monotone(dist) << 32 | row id, i.e. (distance bits, smaller row id); with fewer than k eligible rows the
+ * tail is id -1 / dist +inf (the scan's padding).  Inputs must be finite (precondition, not checked).
+ * self_row0 >= 0: query i skips corpus row self_row0 + i -- self-kNN of a row range of the same matrix.  The row is excluded BY ID; the
+ * reference drops column 0 of a (k + 1)-list instead, which among exact duplicates may drop a duplicate and keep the row itself.
+ * splits: column splits of the corpus per query tile (0 = automatic, a function of (Q, N, k) only); their partial lists are merged by
+ * nlsh_merge_topk's kernel.
+ * Workspace: 4 N bytes of corpus norms (the only term that depends on N) + O(splits * Q * k): 4 Q bytes of query norms and
+ * splits * Q candidate rows of 256 (k <= 64) or 512 keys.  Callers with many queries pass them in chunks to bound it.
+ * Limits: 1 <= k <= NLSH_MAX_K_TILED, 1 <= d <= NLSH_MAX_DIM (NLSH_E_UNSUPPORTED), N < 2^31, any Q; Q = 0 and N = 0 are valid
+ * (N = 0: padding only).  Arguments are checked on the host before anything touches the device.
+ * ------------------------------------------------------------------------------------------- */
+#define NLSH_EXACT_L2 0
+#define NLSH_EXACT_COSINE 1
+size_t nlsh_exact_workspace(int64_t Q, int64_t N, int k, int splits);   /* 0 = invalid arguments; splits 0 = automatic */
+int nlsh_exact_topk(const float *corpus, int64_t row_stride, int64_t N, int d,
+                    const float *queries, int64_t q_stride, int64_t Q, int k, int metric,
+                    int64_t self_row0 /* -1: none */, int splits /* 0: automatic */,
+                    float *out_dist, int32_t *out_idx, void *workspace, size_t workspace_bytes, nlsh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ MAX_K_TILED = 256  # k of the tiled schedule and of nlsh_merge_topk (NLSH_MAX_K_
 PHASE_PLAN, PHASE_SCAN, PHASE_MERGE = 1, 2, 4
 PHASE_ALL = 7
 MAX_ENCODE_PROBES = 128  # nlsh_encode_hash generates up to this many keys per row; the scan takes them in slices of MAX_PROBES
+EXACT_L2, EXACT_COSINE = 0, 1   # metrics of nlsh_exact_topk (precompute.py's forms: squared L2, 1 - cos; not the scan's METRIC_*)
 MAX_STREAM_WIDTH = 4096  # widest hidden layer of the streamed encoder form (nlsh_encode_hash_stream); MAX_WIDTH: the LDS-resident forms
 
 # every symbol include/nlsh_hip.h declares (tests/test_host_cpu.py::test_capi_library_exports_every_declared_symbol checks the header against this)
@@ -33,6 +34,7 @@ SYMBOLS = (
     "nlsh_merge_topk",
     "nlsh_step_create", "nlsh_step_create_graph", "nlsh_step_destroy", "nlsh_step_set_weights", "nlsh_query_step_enqueue", "nlsh_step_release", "nlsh_step_busy", "nlsh_query_batch",
     "nlsh_query_batch_host",
+    "nlsh_exact_workspace", "nlsh_exact_topk",
 )
 
 
@@ -143,6 +145,10 @@ def lib():
     L.nlsh_query_batch.argtypes = [ctypes.POINTER(StepDesc), sz, vp, i64, u64, i64, i32, vp, vp, vp]
     L.nlsh_query_batch_host.restype = i32
     L.nlsh_query_batch_host.argtypes = [ctypes.POINTER(StepDesc), sz, vp, i64, u64, i64, i32, vp, sz, vp]
+    L.nlsh_exact_workspace.restype = sz
+    L.nlsh_exact_workspace.argtypes = [i64, i64, i32, i32]
+    L.nlsh_exact_topk.restype = i32
+    L.nlsh_exact_topk.argtypes = [vp, i64, i64, i32, vp, i64, i64, i32, i32, i64, i32, vp, vp, vp, sz, vp]
     _lib = L
     return L
 

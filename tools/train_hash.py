@@ -43,6 +43,8 @@ def main():
     ap.add_argument("--tanh", action="store_true")
     ap.add_argument("--every", type=int, default=1000)
     ap.add_argument("--out", default="gpurun_out/hash.npz")
+    ap.add_argument("--knn-engine", default="torch", choices=["torch", "hip"],
+                    help="self-kNN when the dataset brings none: torch = training.self_knn (chunked mm + topk), hip = exact.self_knn (nlsh_exact_topk)")
     args = ap.parse_args()
 
     from nlsh_amd import synth, training
@@ -78,7 +80,11 @@ def main():
     if knn_file is not None and knn_file.shape[1] >= need_k:
         knn = torch.from_numpy(knn_file[:, :need_k].astype(np.int64)).cuda()
     else:
-        knn = training.self_knn(cg, need_k, metric=metric)
+        if args.knn_engine == "hip":
+            from nlsh_amd import exact
+            knn = exact.self_knn(cg, need_k, metric=metric)
+        else:
+            knn = training.self_knn(cg, need_k, metric=metric)
     gt = gt_file if gt_file is not None and gt_file.shape[1] >= 10 else brute_force_topk(qg, cg, 10, metric).cpu().numpy()
     torch.cuda.synchronize()
     print(f"[train] self-kNN + ground truth: {time.time() - t0:.1f}s", flush=True)
