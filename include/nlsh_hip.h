@@ -137,6 +137,39 @@ int nlsh_encode_hash_stream(const float *x, int64_t n, int64_t x_stride, int n_l
 int nlsh_pack_codes(const int32_t *codes, int64_t B, int n, int H, int key_mode, int32_t *keys_out,
                     nlsh_stream_t stream);
 
+/* Likelihood-ranked multi-probe keys: the n_probes most probable codes of every row in descending probability, instead of
+ * nlsh_encode_hash's Bernoulli draws (no seed, n_probes DISTINCT codes, probe sets nested in n_probes).  No reference counterpart
+ * (hashings.py:70-81 samples); SURVEY.md 8(f) N3 "flip the least-confident bits", the shift / expand best-first enumeration of
+ * multi-probe LSH (Lv et al., VLDB 2007).  For independent bits the log-odds of hasher bit h is z[h] (sigmoid head; 2 z[h] for the
+ * tanh head, the same order), so a code that differs from the hard code in the bits of a set costs the sum of their |z[h]|.
+ *   z    [dev] fp32 [n, H] with row stride z_stride >= H: the output pre-activations (z_out of nlsh_encode_hash / _stream)
+ *   code [dev] [n] the hard codes (code_out); hasher bit h is code bit H-1-h
+ *   keys_out [n, n_probes], nkeys_out [n] (required) as for nlsh_encode_hash: slot 0 = hard key, unused slots 0
+ *   cost_out [n, n_probes] fp32 (nullable): the cost of each kept slot, +inf past nkeys
+ * A row's result is a pure function of its z, its code, H, key_mode, n_probes and whether its index is < n_multi_rows:
+ *   1. c[h] = z[h] with the sign bit cleared.  The bit indices are sorted by (bit pattern of c[h] as uint32, h) ascending;
+ *      s[i] is the bit index at sorted position i.
+ *   2. A subset M of sorted positions is a uint32 mask (bit i = position i).  Its cost is the fp32 chain from t = +0.0f:
+ *      for i ascending in M, t = t + c[s[i]] (plain fp32 adds, never contracted).
+ *   3. Subsets are ordered by (cost bit pattern, mask as uint32) ascending; the empty set (cost 0: the hard code) is first.  The
+ *      first min(n_probes, 2^H) subsets are taken; rows >= n_multi_rows take the empty set only (Indexer.hash's trailing-batch rule).
+ *   4. The code of M is code XOR the OR of 1 << (H-1-s[i]) over i in M; its key follows key_mode as in nlsh_encode_hash; keys are
+ *      de-duplicated in first-occurrence order (only NLSH_KEY_REF_INT16 with H > 16 can collide); nkeys = number kept.
+ * The order is reachable best-first: every non-empty subset has one parent (top position j: remove j if j-1 is in the set -- the
+ * child was an EXPAND --, else move j to j-1 -- a SHIFT); a child changes or appends only the LAST term of the chain, rounding is
+ * monotone and its mask is larger, so (cost, mask) strictly increases along every edge and popping the frontier's minimum, starting
+ * from {0}, yields the global order.  With the chain-without-its-last-term kept beside each entry both children's costs ARE their
+ * chains, bit for bit.  After m pops the frontier holds at most m + 1 entries.
+ * The kernel makes a fixed n_probes - 1 pops per row and stays inside its buffers whatever the bits of z are: +-inf is legal (handled
+ * by the definition), a NaN is a precondition violation with an unspecified order.
+ * Checked on the host before anything touches the device: NULL required pointers, n < 0, z_stride < H, a bad key_mode
+ * (NLSH_E_INVALID); H outside [1, NLSH_MAX_HASH_BITS], n_probes outside [1, NLSH_MAX_ENCODE_PROBES] (NLSH_E_UNSUPPORTED).
+ * n = 0 is NLSH_OK without a launch. */
+int nlsh_probe_ranked(const float *z, int64_t z_stride, const uint32_t *code, int64_t n, int H,
+                      int key_mode, int n_probes, int64_t n_multi_rows,
+                      int32_t *keys_out, int32_t *nkeys_out, float *cost_out /* nullable */,
+                      nlsh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Index build.  Replaces build_index (nlsh/indexer.py:6-24): key -> ascending row list, as CSR.
  * ------------------------------------------------------------------------------------------- */

@@ -22,6 +22,8 @@ PHASE_PLAN, PHASE_SCAN, PHASE_MERGE = 1, 2, 4
 PHASE_ALL = 7
 MAX_ENCODE_PROBES = 128  # nlsh_encode_hash generates up to this many keys per row; the scan takes them in slices of MAX_PROBES
 EXACT_L2, EXACT_COSINE = 0, 1   # metrics of nlsh_exact_topk (precompute.py's forms: squared L2, 1 - cos; not the scan's METRIC_*)
+PROBES = ("sampled", "ranked")  # multi-probe modes of the hashing: Philox Bernoulli draws (the reference's form, the default) | nlsh_probe_ranked
+PROBE_RANKED_ROWS_PER_WORKGROUP = 4  # nlsh_probe_ranked: one wavefront per row, this many rows per workgroup (tests size their batches by it)
 MAX_STREAM_WIDTH = 4096  # widest hidden layer of the streamed encoder form (nlsh_encode_hash_stream); MAX_WIDTH: the LDS-resident forms
 
 # every symbol include/nlsh_hip.h declares (tests/test_host_cpu.py::test_capi_library_exports_every_declared_symbol checks the header against this)
@@ -35,6 +37,7 @@ SYMBOLS = (
     "nlsh_step_create", "nlsh_step_create_graph", "nlsh_step_destroy", "nlsh_step_set_weights", "nlsh_query_step_enqueue", "nlsh_step_release", "nlsh_step_busy", "nlsh_query_batch",
     "nlsh_query_batch_host",
     "nlsh_exact_workspace", "nlsh_exact_topk",
+    "nlsh_probe_ranked",
 )
 
 
@@ -149,6 +152,8 @@ def lib():
     L.nlsh_exact_workspace.argtypes = [i64, i64, i32, i32]
     L.nlsh_exact_topk.restype = i32
     L.nlsh_exact_topk.argtypes = [vp, i64, i64, i32, vp, i64, i64, i32, i32, i64, i32, vp, vp, vp, sz, vp]
+    L.nlsh_probe_ranked.restype = i32
+    L.nlsh_probe_ranked.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -156,6 +161,14 @@ def lib():
 def check(rc):
     if rc != OK:
         raise NlshHipError(rc, lib().nlsh_last_error().decode("utf-8", "replace"))
+
+
+def probe_mode(probes, default="sampled"):
+    """The multi-probe mode of a call: `probes` when given, else `default`; anything but "sampled" / "ranked" is a ValueError."""
+    mode = default if probes is None else probes
+    if mode not in PROBES:
+        raise ValueError(f"probes must be one of {PROBES}, got {mode!r}")
+    return mode
 
 
 def ptr(t):

@@ -6,6 +6,8 @@
 device->host copy of codes.  `hash_device()` is the device-resident form `Indexer` uses.
 Encoders with a hidden layer wider than `_capi.MAX_WIDTH` (632) are "streamed": they hash through `nlsh_encode_hash_stream`
 (one GEMM launch per layer, activations in a workspace the hashing owns, then the same epilogue), up to `_capi.MAX_STREAM_WIDTH`.
+`probes="ranked"` (attribute, constructor keyword or per call) replaces the Philox draws by the n most probable codes in descending
+probability (`nlsh_probe_ranked` on the encode's own z and hard code: two launches, no seed, n distinct codes); "sampled" is the default.
 There is no CPU fallback: a missing library or a non-device tensor raises.
 """
 import itertools
@@ -37,8 +39,13 @@ class MultivariateBernoulli:
     # bytes of device memory a streamed encoder's workspace may take per (device, stream): the C side makes as many passes over
     # the rows as this needs (at 1024-wide layers, 8.3 KB per row: ~32k rows per pass)
     stream_workspace_cap = 256 << 20
+    # multi-probe mode of hash() / hash_device(): "sampled" = the reference's Bernoulli(p) draws (Philox stream keyed by the seed),
+    # "ranked" = the n most probable codes in descending probability (include/nlsh_hip.h, nlsh_probe_ranked).  A call's `probes=`
+    # keyword overrides it for that call.
+    probes = "sampled"
 
-    def __init__(self, encoder, hash_size, distance_func, tanh_output=False, compat=True, seed=0):
+    def __init__(self, encoder, hash_size, distance_func, tanh_output=False, compat=True, seed=0, probes="sampled"):
+        self.probes = _capi.probe_mode(probes)
         if not 1 <= hash_size <= _capi.MAX_HASH_BITS:
             raise ValueError(f"hash_size must be in [1, {_capi.MAX_HASH_BITS}], got {hash_size}")
         self._encoder = encoder
@@ -87,24 +94,28 @@ class MultivariateBernoulli:
             return self._hasher(x)
         return self._run(x, 1, want_probs=True)[2]
 
-    def hash(self, query_vectors, n=1) -> List[Set[int]]:
-        """hashings.py:66-92: list of B sets of bucket keys (1 hard + n-1 sampled probes).
+    def hash(self, query_vectors, n=1, probes=None) -> List[Set[int]]:
+        """hashings.py:66-92: list of B sets of bucket keys (1 hard + n-1 sampled probes; `probes="ranked"`: the n most probable codes).
         Like the reference, the forward runs in whatever mode the module is in (`train_mode`): see `_run_train_mode`."""
+        probes = _capi.probe_mode(probes, self.probes)
         if n < 1:
             raise ValueError(f"`n` should be positive integer, but got {n}")
-        keys, nkeys, _ = self._run(query_vectors, n)
+        keys, nkeys, _ = self._run(query_vectors, n, probes=probes)
         return keys_to_sets(keys, nkeys, self.key_mode)
 
     # ------------------------------------------------------------------ device-resident form
-    def hash_device(self, x, n=1, n_multi_rows=None, seed=None, row0=0, out=None):
+    def hash_device(self, x, n=1, n_multi_rows=None, seed=None, row0=0, out=None, probes=None):
         """-> (keys int32 [B, n] distinct, first-occurrence order; nkeys int32 [B]) on the device.
 
         Rows >= n_multi_rows are single-probe (Indexer.hash's trailing-batch rule).  `seed`
         defaults to a per-call stream (base seed + call counter): identical on every rank.
+        `probes` ("sampled" | "ranked", None = the hasher's `probes` attribute): ranked keys are a function of the row alone,
+        `seed` and `row0` are accepted and ignored.
         """
+        probes = _capi.probe_mode(probes, self.probes)
         if n < 1:
             raise ValueError(f"`n` should be positive integer, but got {n}")
-        keys, nkeys, _ = self._run(x, n, n_multi_rows=n_multi_rows, seed=seed, row0=row0, out=out)
+        keys, nkeys, _ = self._run(x, n, n_multi_rows=n_multi_rows, seed=seed, row0=row0, out=out, probes=probes)
         return keys, nkeys
 
     def forward_device(self, x):
@@ -188,7 +199,11 @@ class MultivariateBernoulli:
     def encode_args(self, n, keys, nkeys):
         """Fixed part of an `nlsh_encode_hash` call that fills a caller-owned key table (weights as they are NOW):
         (n_layers, dims array, packed weights ptr, act, key_mode, n_probes) and the output pointers, as plain values
-        for callers that launch many batches (nlsh_amd/pipeline.py).  A streamed encoder has no such call: NlshHipError(E_UNSUPPORTED)."""
+        for callers that launch many batches (nlsh_amd/pipeline.py).  A streamed encoder has no such call, and neither has a ranked
+        hasher (its keys take a second launch): NlshHipError(E_UNSUPPORTED)."""
+        if self.probes == "ranked":
+            raise _capi.NlshHipError(_capi.E_UNSUPPORTED, "probes='ranked': the keys come from nlsh_probe_ranked behind the encode "
+                                                          "(no fused / pipelined encode launch); batch slots are sampled-only")
         dims = self.dims()
         if self.streamed():
             raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"hidden width {max(dims[1:-1])} > {_capi.MAX_WIDTH}: the encoder hashes "
@@ -237,10 +252,14 @@ class MultivariateBernoulli:
             keys_t, nkeys_t = out
         return keys_t, nkeys_t, (probs if want_probs else None)
 
-    def _run(self, x, n, n_multi_rows=None, seed=None, row0=0, want_probs=False, z_out=None, code_out=None, out=None):
+    def _run(self, x, n, n_multi_rows=None, seed=None, row0=0, want_probs=False, z_out=None, code_out=None, out=None, probes="sampled"):
         if x.device.type != "cuda":
             raise _capi.NlshHipError(_capi.E_INVALID, "encode_hash needs a device tensor; there is no CPU path")
+        ranked = probes == "ranked"
         if self._needs_train_forward():
+            if ranked:
+                raise _capi.NlshHipError(_capi.E_UNSUPPORTED, "probes='ranked' needs eval mode for BatchNorm encoders (train_mode(False)): "
+                                                              "the train-mode forward has no z")
             if z_out is not None or code_out is not None:
                 raise _capi.NlshHipError(_capi.E_UNSUPPORTED, "forward_device() needs eval mode for BatchNorm encoders (train_mode(False))")
             if x.dtype != torch.float32:
@@ -267,23 +286,38 @@ class MultivariateBernoulli:
             keys = torch.empty((B, n), dtype=torch.int32, device=x.device)
             nkeys = torch.empty((B,), dtype=torch.int32, device=x.device)
         probs = torch.empty((B, self._hash_size), dtype=torch.float32, device=x.device) if want_probs else None
-        if seed is None:
+        if ranked:
+            seed = 0              # no draw is made: the call counter of the sampled mode's seeds is left alone
+        elif seed is None:
             seed = (self._seed + 0x9E3779B97F4A7C15 * (next(self._calls) + 1)) & 0xFFFFFFFFFFFFFFFF
         stream = torch.cuda.current_stream(x.device).cuda_stream
+        n_multi = B if n_multi_rows is None else int(n_multi_rows)
+        # ranked: the encode makes one probe and hands out z and the hard code; nlsh_probe_ranked then fills the caller's table
+        ekeys, enkeys, en = keys, nkeys, n
+        ranked = ranked and n > 1     # one probe is the hard key in either mode
+        if ranked:
+            en = 1
+            ekeys = torch.empty((B, 1), dtype=torch.int32, device=x.device)
+            enkeys = torch.empty((B,), dtype=torch.int32, device=x.device)
+            if z_out is None:
+                z_out = torch.empty((B, self._hash_size), dtype=torch.float32, device=x.device)
+            if code_out is None:
+                code_out = torch.empty((B,), dtype=torch.int32, device=x.device)
         if self.streamed():
             ws = self._stream_workspace(L, dims, B, x.device, stream)
             _capi.check(L.nlsh_encode_hash_stream(
                 _capi.ptr(x), B, x.stride(0) if B else dims[0], len(dims) - 1, _capi.int_array(dims), _capi.ptr(packed),
-                _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID, self.key_mode, n,
-                B if n_multi_rows is None else int(n_multi_rows), seed, row0,
-                _capi.ptr(z_out), _capi.ptr(probs), _capi.ptr(code_out), _capi.ptr(keys), _capi.ptr(nkeys),
+                _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID, self.key_mode, en, n_multi, seed, row0,
+                _capi.ptr(z_out), _capi.ptr(probs), _capi.ptr(code_out), _capi.ptr(ekeys), _capi.ptr(enkeys),
                 _capi.ptr(ws), ws.numel(), stream))
-            return keys, nkeys, probs
-        _capi.check(L.nlsh_encode_hash(
-            _capi.ptr(x), B, x.stride(0) if B else dims[0], len(dims) - 1, _capi.int_array(dims), _capi.ptr(packed),
-            _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID, self.key_mode, n,
-            B if n_multi_rows is None else int(n_multi_rows), seed, row0,
-            _capi.ptr(z_out), _capi.ptr(probs), _capi.ptr(code_out), _capi.ptr(keys), _capi.ptr(nkeys), stream))
+        else:
+            _capi.check(L.nlsh_encode_hash(
+                _capi.ptr(x), B, x.stride(0) if B else dims[0], len(dims) - 1, _capi.int_array(dims), _capi.ptr(packed),
+                _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID, self.key_mode, en, n_multi, seed, row0,
+                _capi.ptr(z_out), _capi.ptr(probs), _capi.ptr(code_out), _capi.ptr(ekeys), _capi.ptr(enkeys), stream))
+        if ranked:
+            _capi.check(L.nlsh_probe_ranked(_capi.ptr(z_out), z_out.stride(0) if B else self._hash_size, _capi.ptr(code_out), B,
+                                            self._hash_size, self.key_mode, n, n_multi, _capi.ptr(keys), _capi.ptr(nkeys), None, stream))
         return keys, nkeys, probs
 
 

@@ -11,6 +11,7 @@ computation with device-resident results (what bench.py times).  compat=True (de
 reference quirks: int16 key wrap (F2), single-probe trailing partial batch (F6), `<k` fallback =
 last key's bucket rows (F7).  No CPU fallback exists anywhere in this module.
 """
+import contextlib
 import gc
 import threading
 from typing import Dict, List, Optional, Sequence, Set, Tuple
@@ -271,7 +272,27 @@ class Indexer:
         # indexer.py:43-53: only full batches get hash_times; the trailing partial batch is n=1 (F6)
         return (n // batch_size) * batch_size if self.compat else n
 
-    def hash_device(self, query_vectors, batch_size=HASH_BATCH, hash_times=1, seed=None, out=None):
+    @contextlib.contextmanager
+    def _probe_mode(self, probes):
+        """A call's `probes=` keyword ("sampled" | "ranked"): the hasher's `probes` attribute is set for the duration of the call and
+        restored on every exit.  Anything else is a ValueError before the call does anything.  (Callers skip this for None: the
+        hasher is left as it is and the default path pays nothing.)"""
+        mode = _capi.probe_mode(probes)
+        h = self._hashing
+        old = getattr(h, "probes", "sampled")
+        h.probes = mode
+        try:
+            yield
+        finally:
+            h.probes = old
+
+    def hash_device(self, query_vectors, batch_size=HASH_BATCH, hash_times=1, seed=None, out=None, probes=None):
+        if probes is None:
+            return self._hash_device(query_vectors, batch_size, hash_times, seed, out)
+        with self._probe_mode(probes):
+            return self._hash_device(query_vectors, batch_size, hash_times, seed, out)
+
+    def _hash_device(self, query_vectors, batch_size=HASH_BATCH, hash_times=1, seed=None, out=None):
         needs_train = getattr(self._hashing, "_needs_train_forward", None)
         if needs_train is not None and needs_train() and query_vectors.shape[0] > batch_size:
             # BatchNorm encoder in TRAIN mode: the reference feeds the module `batch_size`-row batches (nlsh/indexer.py:40-53), so the
@@ -296,8 +317,8 @@ class Indexer:
         return self._hashing.hash_device(query_vectors, n=hash_times,
                                          n_multi_rows=self._n_multi_rows(query_vectors.shape[0], batch_size), seed=seed, out=out)
 
-    def hash(self, query_vectors, batch_size=HASH_BATCH, hash_times=1) -> List[Set[int]]:
-        keys, nkeys = self.hash_device(query_vectors, batch_size, hash_times)
+    def hash(self, query_vectors, batch_size=HASH_BATCH, hash_times=1, probes=None) -> List[Set[int]]:
+        keys, nkeys = self.hash_device(query_vectors, batch_size, hash_times, probes=probes)
         return keys_to_sets(keys, nkeys, self._hashing.key_mode)
 
     # ------------------------------------------------------------------ query
@@ -533,18 +554,25 @@ class Indexer:
             keys64 = torch.where(idx < 0, torch.full_like(mono, -1), (mono << 32) | (idx.long() & 0xFFFFFFFF))
         return dist, idx, ncand, keys64
 
-    def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None):
+    def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None, probes=None):
         """Device-resident form of `query`: hashing + scan, nothing copied to the host.
-        events = (begin, end) torch.cuda.Event pair (already recorded once) bracketing the scan kernel."""
-        return self._batch_tensors(query_vectors, k, hash_times, seed, want_keys=want_keys, check=check, events=events)[:4]
+        events = (begin, end) torch.cuda.Event pair (already recorded once) bracketing the scan kernel.
+        probes ("sampled" | "ranked", None = the hasher's `probes` attribute): the multi-probe mode of this call."""
+        if probes is None:
+            return self._batch_tensors(query_vectors, k, hash_times, seed, want_keys=want_keys, check=check, events=events)[:4]
+        with self._probe_mode(probes):
+            return self._batch_tensors(query_vectors, k, hash_times, seed, want_keys=want_keys, check=check, events=events)[:4]
 
     def _fuses(self, q, hash_times, algo):
         """One `nlsh_query_batch` call (ABI v4: five launches, the bucket lookup in the encode's epilogue) serves a batch when the
         fused kernel may hash it at all (not a BatchNorm encoder in train mode), the key table fits one scan call and the schedule
         is a bucket-major one (the query-major stream's PLAN phase is a single kernel of its own).  A streamed encoder (hidden layer
-        wider than `_capi.MAX_WIDTH`) has no fused encode launch: `hash_device` + `scan_tensors`, the same results by design."""
+        wider than `_capi.MAX_WIDTH`) has no fused encode launch: `hash_device` + `scan_tensors`, the same results by design.  Neither
+        has a ranked hasher (`probes="ranked"`): its keys come from `nlsh_probe_ranked` behind the encode."""
         needs_train = getattr(self._hashing, "_needs_train_forward", None)
         streamed = getattr(self._hashing, "streamed", None)
+        if getattr(self._hashing, "probes", "sampled") == "ranked":
+            return False
         return (self.metric in ("l2", "cosine") and 1 <= hash_times <= _capi.MAX_PROBES and algo != _capi.SCAN_QUERY_MAJOR
                 and self.n_buckets > 0 and q.shape[0] > 0 and not (needs_train is not None and needs_train())
                 and hasattr(self._hashing, "encode_args") and not (streamed is not None and streamed()))
@@ -935,9 +963,13 @@ class Indexer:
     # of two threads and the nested pause of `_plain_lists` leave the collector as the FIRST of them found it (r06).
     pause_collector_for_call = True
 
-    def query(self, query_vectors, k=10, hash_times=10, seed=None) -> Tuple[List[List[int]], List[int]]:
+    def query(self, query_vectors, k=10, hash_times=10, seed=None, probes=None) -> Tuple[List[List[int]], List[int]]:
         """nlsh/indexer.py:56-96.  `seed` (not in the reference): the Philox seed of the multi-probe draws; None takes the next one
-        from the hasher's call counter, like every other hashing call."""
+        from the hasher's call counter, like every other hashing call.  `probes` (not in the reference): "sampled" | "ranked", the
+        multi-probe mode of this call; None = the hasher's `probes` attribute."""
+        if probes is not None:
+            with self._probe_mode(probes):
+                return self.query(query_vectors, k, hash_times, seed)
         if not self.pause_collector_for_call:
             return self._keep(self._query(query_vectors, k, hash_times, seed))
         with _collector_pause:

@@ -61,6 +61,9 @@ class QueryPipeline:
         if streamed is not None and streamed():
             raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"pipelined batches take encoders with hidden layers <= {_capi.MAX_WIDTH} wide, "
                                                           f"not {max(indexer._hashing.dims()[1:-1])} (the streamed form has no batch slot)")
+        if getattr(indexer._hashing, "probes", "sampled") == "ranked":
+            raise _capi.NlshHipError(_capi.E_UNSUPPORTED, "pipelined batches take sampled probes only: a ranked hasher's keys come from "
+                                                          "nlsh_probe_ranked behind the encode (no batch slot)")
         if hash_times > _capi.MAX_PROBES:
             raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"pipelined batches take hash_times <= {_capi.MAX_PROBES}")
         if depth < 2:

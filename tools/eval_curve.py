@@ -5,6 +5,10 @@ candidates and recall@K -- the recall-vs-candidates trade-off curve eval.py prin
 
     python tools/eval_curve.py --model checkpoints/sift1m_manifold_h16.npz --data synth:sift1m [--max-samples 32]
     python tools/eval_curve.py --model run_cpu.pt --base base.fvecs --query query.fvecs --gt gt.ivecs --metric l2
+    python tools/eval_curve.py --model checkpoints/sift1m_manifold_h16.npz --data synth:sift1m --probes ranked
+
+--probes ranked probes the n_samples most probable codes in descending probability (nlsh_probe_ranked) instead of the Philox draws:
+n_samples distinct buckets per query and no seed.  avg_n_keys is the mean number of distinct keys a query probes.
 
 Differences from eval.py, on purpose: keys are full width (eval.py's `_binarr_to_int`, eval.py:49-53),
 every query is multi-probed (no trailing-batch rule), `<K` candidates return all of them (eval.py:185-186).
@@ -35,6 +39,8 @@ def main():
     ap.add_argument("--q", type=int, default=10000)
     ap.add_argument("--tanh", action="store_true")
     ap.add_argument("--seed", type=int, default=1, help="Philox seed of the probes: one stream, so the probe sets are nested in n_samples")
+    ap.add_argument("--probes", default="sampled", choices=["sampled", "ranked"],
+                    help="sampled: Bernoulli draws (the reference's form) | ranked: the n_samples most probable codes (no seed)")
     args = ap.parse_args()
     from nlsh_amd import io as nio, synth
     from nlsh_amd.data import Glove, SIFT, brute_force_topk
@@ -62,19 +68,21 @@ def main():
     indexer = Indexer(hashing, cg, SIFT.distance if metric == "l2" else Glove.distance, compat=False)
     torch.cuda.synchronize()
     print(f"# index: {indexer.bucket_stats()} built in {time.time() - t0:.3f}s", flush=True)
-    print("n_samples avg_n_candidates recall qps")
+    print("n_samples avg_n_candidates recall qps avg_n_keys")
     rows = []
     for n_samples in range(1, min(args.max_samples, 100) + 1):   # eval.py:148 range(1, 101)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        dist, idx, nc, _ = indexer.query_tensors(qg, k=args.k, hash_times=n_samples, seed=args.seed)
+        dist, idx, nc, _ = indexer.query_tensors(qg, k=args.k, hash_times=n_samples, seed=args.seed, probes=args.probes)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        _, nkeys = indexer.hash_device(qg, hash_times=n_samples, seed=args.seed, probes=args.probes)    # the same keys again, for their count
         ids = [r[r >= 0].tolist() for r in idx.cpu().numpy()]
         rec = float(np.mean(calculate_recall(list(gt), ids)))
-        rows.append({"n_samples": n_samples, "avg_n_candidates": float(nc.float().mean()), "recall": rec, "qps": len(ids) / dt})
-        print(n_samples, f"{rows[-1]['avg_n_candidates']:.1f}", f"{rec:.4f}", f"{rows[-1]['qps']:.0f}", flush=True)
-    print(json.dumps({"model": args.model, "metric": metric, "k": args.k, "curve": rows}))
+        rows.append({"n_samples": n_samples, "avg_n_candidates": float(nc.float().mean()), "recall": rec, "qps": len(ids) / dt,
+                     "avg_n_keys": float(nkeys.float().mean())})
+        print(n_samples, f"{rows[-1]['avg_n_candidates']:.1f}", f"{rec:.4f}", f"{rows[-1]['qps']:.0f}", f"{rows[-1]['avg_n_keys']:.3f}", flush=True)
+    print(json.dumps({"model": args.model, "metric": metric, "k": args.k, "probes": args.probes, "curve": rows}))
 
 
 if __name__ == "__main__":
