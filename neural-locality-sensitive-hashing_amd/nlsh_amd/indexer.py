@@ -12,7 +12,9 @@ reference quirks: int16 key wrap (F2), single-probe trailing partial batch (F6),
 last key's bucket rows (F7).  No CPU fallback exists anywhere in this module.
 """
 import contextlib
+import ctypes
 import gc
+import operator
 import threading
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
@@ -93,6 +95,13 @@ _rows_to_lists = _load_fastlists()
 
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+# `nlsh_scan_topk_cells_phase`'s arguments either side of (queries, q_stride), by their names in `Indexer._scan_fields`
+_SCAN_ARGS_BEFORE_QUERIES = operator.itemgetter("corpus_sorted", "row_stride", "d", "gid", "uniq_keys", "offsets", "bucket_order", "n_buckets",
+                                                "cell_of", "cell_offsets", "n_cells", "inv_norm")
+_SCAN_ARGS_AFTER_QUERIES = operator.itemgetter("Q", "qkeys", "nkeys", "n_probes", "k", "metric", "algo", "seg_rows", "out_dist", "out_idx", "out_keys",
+                                               "out_ncand", "status", "workspace", "workspace_bytes", "max_tasks")
 
 
 def build_csr_device(keys: torch.Tensor):
@@ -369,26 +378,6 @@ class Indexer:
             got = self._cells[window_rows] = (cell_of, cell_offsets[:nc + 1], cell_order[:max(nc, 1)], nc)
         return got
 
-    # EXPERIMENT (r06, off by default): consecutive batches walk the schedule order of the cells in OPPOSITE directions behind a common
-    # prefix of the `alternate_keep` largest cells.  The order changes speed, never results.  Idea: a batch of a balanced hash touches
-    # most of the corpus (GloVe-shaped: 0.36 of 0.47 GB) in the SAME order every time, so what the 256-MiB Infinity Cache holds at the
-    # end of batch i -- the rows of the schedule's tail -- is what batch i+1 needs last; walked backwards it needs them first.
-    alternate_order = False
-    alternate_keep = 0
-
-    def _order_for_this_batch(self, window, cell_order, nc):
-        if not self.alternate_order or nc < 2:
-            return cell_order
-        self._order_phase = getattr(self, "_order_phase", 0) ^ 1
-        if not self._order_phase:
-            return cell_order
-        rev = self.__dict__.setdefault("_cell_order_rev", {}).get((window, self.alternate_keep))
-        if rev is None:
-            keep = min(max(int(self.alternate_keep), 0), nc)
-            rev = torch.cat([cell_order[:keep], cell_order[keep:nc].flip(0)]).contiguous()
-            self._cell_order_rev[(window, self.alternate_keep)] = rev
-        return rev
-
     def choose_window(self, Q, P, algo):
         """Row window of the small-bucket packing for one batch shape (tiled schedule only): 64 rows unless forced.
         Measured (r04, tools/scan_bench.py --window 0,64,128,256 --rounds 4, same process and keys, scan kernel ms, one box):
@@ -420,16 +409,50 @@ class Indexer:
             est = Q * (1.0 + min(P, 4) * biased / seg)
         return int(min(max(1.5 * est + 1024, Q + 1024), 2 ** 31 - 8))
 
+    def _task_table(self, algo, Q, P):
+        """(tkey, window, max_tasks) of a batch shape -- the only place that consults or seeds `_max_tasks` for one.  The task table is
+        sized per (schedule, batch shape): a larger batch after a smaller one re-estimates instead of reusing a table that `check=False`
+        callers would silently overflow; a smaller one takes the smallest table of the same schedule and window that served a batch at
+        least as large."""
+        tkey = self._tkey(algo, Q, P)
+        window = tkey[3]
+        max_tasks = self._max_tasks.get(tkey)
+        if max_tasks is None:
+            grown = [v for (a_, q_, p_, w_), v in self._max_tasks.items() if a_ == algo and q_ >= Q and p_ >= P and w_ == window]
+            max_tasks = self._max_tasks[tkey] = min(grown) if grown else self._estimate_tasks(Q, P, self.seg_rows or 512, algo)
+        return tkey, window, max_tasks
+
+    def _workspace(self, dev, stream, bucket_major, ws_bytes):
+        """(wkey, ws): one workspace per stream and schedule family, fetched or zero-allocated -- the bucket-major PLAN phase keeps its
+        per-bucket counters at the head of the workspace ZERO between calls (include/nlsh_hip.h), so nothing else may write there."""
+        wkey = (stream, bucket_major)
+        ws = self._ws.get(wkey)
+        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
+            ws = self._ws[wkey] = torch.zeros((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        return wkey, ws
+
+    @staticmethod
+    def _outputs(Q, k, dev, want_keys=False):
+        """One batch's outputs: (out_dist, pack, out_idx, ncand, status, out_keys | None).  ids, candidate counts and the two status
+        words share ONE int32 buffer (`pack`): `query()` brings all three to the host with a single copy (and a single
+        synchronisation) instead of four."""
+        out_dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
+        pack = torch.empty((Q * k + Q + 2,), dtype=torch.int32, device=dev)
+        out_keys = torch.empty((Q, k), dtype=torch.int64, device=dev) if want_keys else None
+        out_idx, ncand, status = pack.split((Q * k, Q, 2))
+        return out_dist, pack, out_idx.view(Q, k), ncand, status, out_keys
+
+    def _set_last(self, status, algo, window, pack, tkey, max_tasks):
+        """What the last launch ran with (`max_tasks`: its table, before any trim); bench.py, the tests and the tools read these."""
+        self.last_status = status
+        self.last_algo, self.last_window = algo, window
+        self._last_pack, self._last_tkey, self._last_max_tasks = pack, tkey, max_tasks
+
     def scan_tensors(self, query_vectors, keys, nkeys, k=10, want_keys=False, check=True, events=None, algo=None):
         """Scan stage on a device key table -> (dist [Q,k], idx [Q,k], ncand [Q], keys64 | None)."""
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("fused scan needs metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
-        L = _capi.lib()
-        q = query_vectors
-        if q.device.type != "cuda":
-            raise _capi.NlshHipError(_capi.E_INVALID, "queries must be device-resident; there is no CPU path")
-        if q.dtype != torch.float32 or q.stride(1) != 1:
-            q = q.float().contiguous()
+        q = self._as_queries(query_vectors)
         Q, d = q.shape
         if d != self.dim:
             raise ValueError(f"query dim {d} != corpus dim {self.dim}")
@@ -439,49 +462,37 @@ class Indexer:
         keys = keys.contiguous()
         nkeys = nkeys.contiguous()
         P = keys.shape[1]
-        seg = self.seg_rows or 512
-        out_dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
-        # ids, candidate counts and the two status words share ONE int32 buffer: `query()` brings all three to the host
-        # with a single copy (and a single synchronisation) instead of four
-        pack = torch.empty((Q * k + Q + 2,), dtype=torch.int32, device=dev)
-        out_idx, ncand, status = pack[:Q * k].view(Q, k), pack[Q * k:Q * k + Q], pack[Q * k + Q:]
-        out_keys = torch.empty((Q, k), dtype=torch.int64, device=dev) if want_keys else None
+        out_dist, pack, out_idx, ncand, status, out_keys = self._outputs(Q, k, dev, want_keys)
         if algo is None:
             algo = self.choose_algo(Q, P)
-        # the task table is sized per (schedule, batch shape): a larger batch after a smaller one re-estimates instead of
-        # reusing a table that `check=False` callers would silently overflow
-        window = self.choose_window(Q, P, algo)
-        tkey = self._tkey(algo, Q, P)
-        if tkey not in self._max_tasks:
-            grown = [v for (a_, q_, p_, w_), v in self._max_tasks.items() if a_ == algo and q_ >= Q and p_ >= P and w_ == window]
-            self._max_tasks[tkey] = min(grown) if grown else self._estimate_tasks(Q, P, seg, algo)
+        stream = _stream(dev)
         while True:
-            max_tasks = self._max_tasks[tkey]
-            ws_bytes = L.nlsh_scan_workspace(Q, P, k, max_tasks, self.n_buckets, d)
-            stream = _stream(dev)
-            # one workspace per stream and schedule family: the bucket-major PLAN phase keeps its per-bucket counters at the
-            # head of the workspace ZERO between calls (include/nlsh_hip.h), so nothing else may write there
-            wkey = (stream, algo != _capi.SCAN_QUERY_MAJOR)
-            ws = self._ws.get(wkey)
-            if ws is None or ws.numel() < ws_bytes or ws.device != dev:
-                ws = self._ws[wkey] = torch.zeros((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+            tkey, window, max_tasks = self._task_table(algo, Q, P)
+            wkey, ws = self._workspace(dev, stream, algo != _capi.SCAN_QUERY_MAJOR,
+                                       _capi.lib().nlsh_scan_workspace(Q, P, k, max_tasks, self.n_buckets, d))
             try:
                 self._scan_launch(q, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws,
-                                  _capi.PHASE_ALL, events, window)
+                                  _capi.PHASE_ALL, events, window, stream)
             except _capi.NlshHipError:
                 self._ws.pop(wkey, None)    # a call that failed part-way may have left the counters at the head non-zero
                 raise
             if not check or Q == 0:
                 break
             needed, overflow = status.cpu().tolist()
-            if not overflow:
-                self._trim_task_table(tkey, needed, max_tasks)
+            if self._settle(tkey, needed, overflow, max_tasks):     # else: segment table too small, grown: repeat
                 break
-            self._grow_task_table(tkey, needed, overflow)           # segment table too small: grow and repeat
-        self.last_status = status
-        self.last_algo, self.last_window = algo, window
-        self._last_pack, self._last_tkey, self._last_max_tasks = pack, tkey, max_tasks
+        self._set_last(status, algo, window, pack, tkey, max_tasks)
         return out_dist, out_idx, ncand, out_keys
+
+    def _settle(self, tkey, needed, overflow, max_tasks):
+        """What every launch path does once the host has read a launch's status words (`needed`, `overflow`): True = the results
+        stand (the table is trimmed if it was far too large); False = the task table was too small and has been grown, the caller
+        repeats the launch.  Raises on a broken workspace or cell contract (`_grow_task_table`)."""
+        if overflow:
+            self._grow_task_table(tkey, needed, overflow)
+            return False
+        self._trim_task_table(tkey, needed, max_tasks)
+        return True
 
     def _trim_task_table(self, tkey, needed, max_tasks):
         """The one-shot tiled kernel launches a workgroup per table slot: a table sized for the bucket-per-task estimate and then
@@ -505,32 +516,48 @@ class Indexer:
                                                         "were not zero on entry (workspace contract, include/nlsh_hip.h)")
         self._max_tasks[tkey] = int(needed * 1.25) + 1024
 
-    def _scan_args(self, Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window=None):
-        """The arguments of `nlsh_scan_topk_cells_phase` that do not change between batches of one shape, as plain ints:
-        (everything before `queries`, everything between `q_stride`/`Q` and the events).  Callers that launch many
-        batches (nlsh_amd/pipeline.py) build them once per buffer set; a call is then one ctypes transition."""
-        a = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    def _scan_fields(self, Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window=None):
+        """The scan's share of a launch -- everything that does not change between batches of one shape -- as plain ints under the
+        field names of `_capi.StepDesc`: `_scan_launch` passes them to `nlsh_scan_topk_cells_phase`, `_step_desc` fills a descriptor
+        from them.  Callers that launch many batches (the kept range plans, nlsh_amd/pipeline.py) build them once per buffer set; a
+        call is then one ctypes transition."""
+        a = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (the tensors that may be absent)
         metric = (_capi.METRIC_L2_EPS_FOLDED if self.l2_form == "folded" else _capi.METRIC_L2_EPS) if self.metric == "l2" else _capi.METRIC_COSINE
         if window is None:
             window = self.choose_window(Q, keys.shape[1], algo)
         if window and algo == _capi.SCAN_BUCKET_TILED:
-            cell_of, cell_offsets, cell_order, nc = self.cells(window)
-            sched = (a(self._order_for_this_batch(window, cell_order, nc)), self.n_buckets, a(cell_of), a(cell_offsets), nc)
+            cell_of, cell_offsets, order, n_cells = self.cells(window)
         else:
-            sched = (a(self.bucket_order), self.n_buckets, None, None, 0)
-        pre = (a(self.corpus_sorted), self.row_stride, d, a(self.gid), a(self.uniq_keys), a(self.offsets), *sched, a(self.inv_norm))
-        post = (Q, a(keys), a(nkeys), keys.shape[1], k, metric, algo, self.seg_rows or 512, a(out_dist), a(out_idx), a(out_keys),
-                a(ncand), a(status), a(ws), ws.numel(), max_tasks)
-        return pre, post
+            cell_of, cell_offsets, order, n_cells = None, None, self.bucket_order, 0
+        return {"corpus_sorted": self.corpus_sorted.data_ptr(), "row_stride": self.row_stride, "d": d, "gid": self.gid.data_ptr(),
+                "uniq_keys": self.uniq_keys.data_ptr(), "offsets": self.offsets.data_ptr(), "bucket_order": order.data_ptr(),
+                "n_buckets": self.n_buckets, "cell_of": a(cell_of), "cell_offsets": a(cell_offsets), "n_cells": n_cells,
+                "inv_norm": a(self.inv_norm), "Q": Q, "qkeys": keys.data_ptr(), "nkeys": nkeys.data_ptr(), "n_probes": keys.shape[1], "k": k,
+                "metric": metric, "algo": algo, "seg_rows": self.seg_rows or 512, "out_dist": out_dist.data_ptr(),
+                "out_idx": out_idx.data_ptr(), "out_keys": a(out_keys), "out_ncand": ncand.data_ptr(), "status": status.data_ptr(),
+                "workspace": ws.data_ptr(), "workspace_bytes": ws.numel(), "max_tasks": max_tasks}
+
+    @staticmethod
+    def _step_desc(fields, encode_args, n_multi_rows, hold_done=0, streams=None):
+        """The one place a `_capi.StepDesc` is filled: the scan's `fields` (`_scan_fields`), the hasher's `encode_args(...)[0]`, the
+        range's multi-probe rows and -- pipeline slots only -- `hold_done` and the (front, plan, mid, tail) stream handles.  The
+        descriptor holds addresses only: its owner keeps the dims array and the packed weights alive for as long as it can be launched."""
+        n_layers, dims_arr, packed_ptr, act, key_mode, n_probes = encode_args
+        assert n_probes == fields["n_probes"], "the encoder's probes per row are the key table's width"
+        front, plan, mid, tail = streams or (None, None, None, None)
+        return _capi.StepDesc(n_layers=n_layers, act=act, key_mode=key_mode, dims=ctypes.cast(dims_arr, ctypes.c_void_p), packed=packed_ptr,
+                              n_multi_rows=int(n_multi_rows), hold_done=int(hold_done), front=front, plan=plan, mid=mid, tail=tail, **fields)
 
     def _scan_launch(self, q, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, phases, events=None,
-                     window=None):
-        """One `nlsh_scan_topk_cells_phase` call on the current stream with caller-owned buffers (any subset of the phases)."""
+                     window=None, stream=None):
+        """One `nlsh_scan_topk_cells_phase` call on the current stream (`stream`: its handle, when the caller has already looked it up)
+        with caller-owned buffers (any subset of the phases)."""
         Q, d = q.shape
-        pre, post = self._scan_args(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window)
+        f = self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window)
         _capi.check(_capi.lib().nlsh_scan_topk_cells_phase(
-            *pre, q.data_ptr(), q.stride(0) if Q else d, *post,
-            events[0].cuda_event if events else None, events[1].cuda_event if events else None, _stream(q.device), phases))
+            *_SCAN_ARGS_BEFORE_QUERIES(f), q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
+            events[0].cuda_event if events else None, events[1].cuda_event if events else None,
+            _stream(q.device) if stream is None else stream, phases))
 
     def _scan_sliced(self, q, keys, nkeys, k, want_keys, check):
         """hash_times > 64 (eval.py:148 sweeps n_samples up to 100): the key table is scanned in column slices of
@@ -598,43 +625,23 @@ class Indexer:
             return self.scan_tensors(q, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events, algo=algo) + (keys, nkeys)
         if d != self.dim:
             raise ValueError(f"query dim {d} != corpus dim {self.dim}")
-        import ctypes
         L, h, dev, P = _capi.lib(), self._hashing, q.device, hash_times
         if out is not None:
             keys, nkeys = out
         else:
             keys = torch.empty((Q, P), dtype=torch.int32, device=dev)
             nkeys = torch.empty((Q,), dtype=torch.int32, device=dev)
-        out_dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
-        pack = torch.empty((Q * k + Q + 2,), dtype=torch.int32, device=dev)    # ids, counts, status: ONE buffer, one copy for `query()`
-        out_idx, ncand, status = pack[:Q * k].view(Q, k), pack[Q * k:Q * k + Q], pack[Q * k + Q:]
-        out_keys = torch.empty((Q, k), dtype=torch.int64, device=dev) if want_keys else None
-        window = self.choose_window(Q, P, algo)
-        tkey = self._tkey(algo, Q, P)
-        if tkey not in self._max_tasks:
-            grown = [v for (a_, q_, p_, w_), v in self._max_tasks.items() if a_ == algo and q_ >= Q and p_ >= P and w_ == window]
-            self._max_tasks[tkey] = min(grown) if grown else self._estimate_tasks(Q, P, self.seg_rows or 512, algo)
+        out_dist, pack, out_idx, ncand, status, out_keys = self._outputs(Q, k, dev, want_keys)
         if seed is None:
             seed = h.next_seed()
-        (n_layers, dims_arr, packed_ptr, act, key_mode, n_probes), _ = h.encode_args(P, keys, nkeys)
+        enc, _ = h.encode_args(P, keys, nkeys)      # (held to the end of the call: the descriptor names its dims array)
         stream = _stream(dev)
         lookup_done = 0
         while True:
-            max_tasks = self._max_tasks[tkey]
-            ws_bytes = L.nlsh_scan_workspace(Q, P, k, max_tasks, self.n_buckets, d)
-            wkey = (stream, True)
-            ws = self._ws.get(wkey)
-            if ws is None or ws.numel() < ws_bytes or ws.device != dev:
-                ws = self._ws[wkey] = torch.zeros((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
-            pre, post = self._scan_args(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window)
-            (corpus, row_stride, d_, gid, uniq, offsets, order, n_buckets, cell_of, cell_offsets, n_cells, inv_norm) = pre
-            (Q_, qkeys_p, nkeys_p, P_, k_, metric, algo_, seg, od, oi, ok, nc, st, wsp, wsb, mt) = post
-            desc = _capi.StepDesc(
-                n_layers=n_layers, act=act, key_mode=key_mode, n_probes=n_probes, dims=ctypes.cast(dims_arr, ctypes.c_void_p), packed=packed_ptr,
-                n_multi_rows=int(n_multi), corpus_sorted=corpus, row_stride=row_stride, gid=gid, uniq_keys=uniq, offsets=offsets,
-                bucket_order=order, cell_of=cell_of, cell_offsets=cell_offsets, inv_norm=inv_norm, d=d_, n_buckets=n_buckets, n_cells=n_cells,
-                k=k_, metric=metric, algo=algo_, seg_rows=seg, hold_done=0, Q=Q_, qkeys=qkeys_p, nkeys=nkeys_p, out_dist=od, out_idx=oi,
-                out_keys=ok, out_ncand=nc, status=st, workspace=wsp, workspace_bytes=wsb, max_tasks=mt, front=None, plan=None, mid=None, tail=None)
+            tkey, window, max_tasks = self._task_table(algo, Q, P)
+            wkey, ws = self._workspace(dev, stream, True, L.nlsh_scan_workspace(Q, P, k, max_tasks, self.n_buckets, d))
+            desc = self._step_desc(self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws,
+                                                     window), enc, n_multi)
             try:
                 _capi.check(L.nlsh_query_batch(ctypes.byref(desc), ctypes.sizeof(desc), q.data_ptr(), q.stride(0), seed, int(row0), lookup_done,
                                                events[0].cuda_event if events else None, events[1].cuda_event if events else None, stream))
@@ -644,14 +651,10 @@ class Indexer:
             if not check:
                 break
             needed, overflow = status.cpu().tolist()
-            if not overflow:
-                self._trim_task_table(tkey, needed, max_tasks)
+            if self._settle(tkey, needed, overflow, max_tasks):
                 break
-            self._grow_task_table(tkey, needed, overflow)           # task table too small: grow and repeat the scan part on the same keys
-            lookup_done = 1
-        self.last_status = status
-        self.last_algo, self.last_window = algo, window
-        self._last_pack, self._last_tkey, self._last_max_tasks = pack, tkey, max_tasks
+            lookup_done = 1                 # task table too small, grown: repeat the scan part on the same keys
+        self._set_last(status, algo, window, pack, tkey, max_tasks)
         return out_dist, out_idx, ncand, out_keys, keys, nkeys
 
     def _rows_of_key(self, key):
@@ -679,55 +682,36 @@ class Indexer:
     # weight walk, argument tuples) was 0.08 ms per range = 0.2 ms of a 1.1-ms call (tools/query_host_profile.py).  `query_tensors`
     # hands its tensors to the caller and keeps allocating fresh ones.  Like the scan workspace (one per stream), the kept buffers
     # assume one `query()` at a time per indexer and stream.
-    def _range_plan(self, q, keys, nkeys, k, lo, hi, algo, hash_times, n_multi, host=None):
-        import ctypes
+    def _range_plan(self, q, keys, nkeys, k, lo, hi, algo, n_multi, host=None):
         Q_all, P = keys.shape
         dev, m = q.device, hi - lo
         stream = _stream(dev)
         ckey = (stream, Q_all, lo, hi, P, k, algo, self.l2_form, keys.data_ptr(), q.shape[1])
         plans = self.__dict__.setdefault("_range_plans", {})
         plan = plans.get(ckey)
-        tkey = self._tkey(algo, m, P)
-        window = self.choose_window(m, P, algo)
-        if tkey not in self._max_tasks:
-            grown = [v for (a_, q_, p_, w_), v in self._max_tasks.items() if a_ == algo and q_ >= m and p_ >= P and w_ == window]
-            self._max_tasks[tkey] = min(grown) if grown else self._estimate_tasks(m, P, self.seg_rows or 512, algo)
-        max_tasks = self._max_tasks[tkey]
-        wkey = (stream, True)
-        ws = self._ws.get(wkey)
+        tkey, window, max_tasks = self._task_table(algo, m, P)
         sig = self._hashing._weights_signature()
         # `host`: the range's slice of the pinned result block (`_host_form`); the plan keeps its address and size only (a reference would
         # hold an outgrown block's pinned pages for as long as the plan lives) -- the block is reallocated when a larger batch shape
         # arrives, and a plan that names another address than the call's slice is rebuilt before it is used
         host_ptr = None if host is None else host.data_ptr()
-        if plan is not None and plan["max_tasks"] == max_tasks and plan["ws"] is ws and plan["window"] == window and plan["host_ptr"] == host_ptr:
+        if (plan is not None and plan["max_tasks"] == max_tasks and plan["ws"] is self._ws.get(plan["wkey"]) and plan["window"] == window
+                and plan["host_ptr"] == host_ptr):
             if plan["sig"] != sig:        # a training step between two calls: the descriptor gets the new blob
                 plan["packed"] = self._hashing.packed_weights()
                 plan["desc"].packed = plan["packed"].data_ptr()
                 plan["sig"] = sig
             return plan
-        L, d = _capi.lib(), q.shape[1]
-        ws_bytes = L.nlsh_scan_workspace(m, P, k, max_tasks, self.n_buckets, d)
-        if ws is None or ws.numel() < ws_bytes or ws.device != dev:
-            ws = self._ws[wkey] = torch.zeros((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        d = q.shape[1]
+        wkey, ws = self._workspace(dev, stream, True, _capi.lib().nlsh_scan_workspace(m, P, k, max_tasks, self.n_buckets, d))
         rk, rn = keys[lo:hi], nkeys[lo:hi]
-        out_dist = torch.empty((m, k), dtype=torch.float32, device=dev)
-        pack = torch.empty((m * k + m + 2,), dtype=torch.int32, device=dev)
-        out_idx, ncand, status = pack[:m * k].view(m, k), pack[m * k:m * k + m], pack[m * k + m:]
-        (n_layers, dims_arr, packed_ptr, act, key_mode, n_probes), _ = self._hashing.encode_args(P, rk, rn)
-        pre, post = self._scan_args(m, d, rk, rn, k, algo, max_tasks, out_dist, out_idx, None, ncand, status, ws, window)
-        (corpus, row_stride, d_, gid, uniq, offsets, order, n_buckets, cell_of, cell_offsets, n_cells, inv_norm) = pre
-        (Q_, qkeys_p, nkeys_p, P_, k_, metric, algo_, seg, od, oi, ok, nc, st, wsp, wsb, mt) = post
-        desc = _capi.StepDesc(
-            n_layers=n_layers, act=act, key_mode=key_mode, n_probes=n_probes, dims=ctypes.cast(dims_arr, ctypes.c_void_p), packed=packed_ptr,
-            n_multi_rows=int(min(max(n_multi - lo, 0), m)), corpus_sorted=corpus, row_stride=row_stride, gid=gid, uniq_keys=uniq, offsets=offsets,
-            bucket_order=order, cell_of=cell_of, cell_offsets=cell_offsets, inv_norm=inv_norm, d=d_, n_buckets=n_buckets, n_cells=n_cells,
-            k=k_, metric=metric, algo=algo_, seg_rows=seg, hold_done=0, Q=Q_, qkeys=qkeys_p, nkeys=nkeys_p, out_dist=od, out_idx=oi,
-            out_keys=ok, out_ncand=nc, status=st, workspace=wsp, workspace_bytes=wsb, max_tasks=mt, front=None, plan=None, mid=None, tail=None)
-        plan = plans[ckey] = dict(desc=desc, ref=ctypes.byref(desc), size=ctypes.sizeof(desc), dims_arr=dims_arr, packed=self._hashing.packed_weights(), sig=sig,
+        out_dist, pack, out_idx, ncand, status, _ = self._outputs(m, k, dev)
+        enc, _ = self._hashing.encode_args(P, rk, rn)
+        desc = self._step_desc(self._scan_fields(m, d, rk, rn, k, algo, max_tasks, out_dist, out_idx, None, ncand, status, ws, window),
+                               enc, min(max(n_multi - lo, 0), m))
+        plan = plans[ckey] = dict(desc=desc, ref=ctypes.byref(desc), size=ctypes.sizeof(desc), dims_arr=enc[1], packed=self._hashing.packed_weights(), sig=sig,
                                   keys=rk, nkeys=rn, out_dist=out_dist, pack=pack, status=status, ws=ws, wkey=wkey, max_tasks=max_tasks, tkey=tkey,
-                                  window=window, stream=stream, order_rotates=bool(self.alternate_order), host_ptr=host_ptr,
-                                  host_words=0 if host is None else host.numel())
+                                  window=window, stream=stream, host_ptr=host_ptr, host_words=0 if host is None else host.numel())
         if len(plans) > 64:           # batch shapes come and go (a caller sweeping Q): keep the dictionary bounded
             for old_key in list(plans)[:-32]:
                 del plans[old_key]
@@ -736,8 +720,8 @@ class Indexer:
     def _host_form(self, k, fused):
         """Whether a row range's results reach the host from the merge kernel itself (`nlsh_query_batch_host`: no copy command behind the
         kernels) -- the fused call with k <= 64.  Everything else (a streamed encoder, the query-major schedule, hash_times > 64: not
-        `fused`; wide k; the schedule-order experiment) keeps the device->host copies."""
-        return fused is not None and k <= _capi.MAX_K and not self.alternate_order
+        `fused`; wide k) keeps the device->host copies."""
+        return fused is not None and k <= _capi.MAX_K
 
     def _range_tensors(self, q, keys, nkeys, k, lo, hi, algo, fused, host=None):
         """One row range of a `query()` batch on the stream: `fused` = (hash_times, seed, rows of the batch that are multi-probe) --
@@ -746,14 +730,13 @@ class Indexer:
         result block -- the call is `nlsh_query_batch_host`, whose merge kernel stores ids | counts | status | the short queries' key rows
         there, and nothing has to be copied afterwards."""
         if fused is None:
-            self.scan_tensors(q[lo:hi], keys[lo:hi], nkeys[lo:hi], k=k, check=False, algo=algo)
+            if hi - lo == q.shape[0]:     # the whole batch (`_host_results`): nothing to slice
+                self.scan_tensors(q, keys, nkeys, k=k, check=False, algo=algo)
+            else:
+                self.scan_tensors(q[lo:hi], keys[lo:hi], nkeys[lo:hi], k=k, check=False, algo=algo)
             return
-        hash_times, seed, n_multi = fused
-        if self.alternate_order:      # (experiment switch: the schedule order changes from call to call, so nothing is kept)
-            self._batch_tensors(q[lo:hi], k, hash_times, seed, check=False, algo=algo, row0=lo, n_multi=min(max(n_multi - lo, 0), hi - lo),
-                                out=(keys[lo:hi], nkeys[lo:hi]))
-            return
-        plan = self._range_plan(q, keys, nkeys, k, lo, hi, algo, hash_times, n_multi, host)
+        _, seed, n_multi = fused
+        plan = self._range_plan(q, keys, nkeys, k, lo, hi, algo, n_multi, host)
         qr = q[lo:hi]
         try:
             if host is not None:
@@ -765,9 +748,19 @@ class Indexer:
             self._ws.pop(plan["wkey"], None)    # a call that failed part-way may have left the counters at the head non-zero
             self._range_plans.clear()
             raise
-        self.last_status = plan["status"]
-        self.last_algo, self.last_window = algo, plan["window"]
-        self._last_pack, self._last_tkey, self._last_max_tasks = plan["pack"], plan["tkey"], plan["max_tasks"]
+        self._set_last(plan["status"], algo, plan["window"], plan["pack"], plan["tkey"], plan["max_tasks"])
+
+    @staticmethod
+    def _block_views(a, m, k, P, host_form):
+        """A range's block of the pinned buffer (host array of m*k + m + 2 + m*P + m words) -> (ids [m, k], counts [m], keys [m, P],
+        nkeys [m]).  Behind the ids | counts | status words the copy form holds keys | nkeys; the host-writing merge stores key rows
+        [m, P + 1] there -- nkeys, then the keys -- written for the queries with < k candidates only."""
+        n = m * k + m + 2
+        ids, counts = a[:m * k].reshape(m, k), a[m * k:m * k + m]
+        if host_form:
+            rows = a[n:n + m * (P + 1)].reshape(m, P + 1)
+            return ids, counts, rows[:, 1:], rows[:, 0]
+        return ids, counts, a[n:n + m * P].reshape(m, P), a[n + m * P:n + m * P + m]
 
     def _host_results(self, q, keys, nkeys, k, fused=None):
         """One range = the whole batch: scan, results into the pinned block, ONE stream synchronisation (the only sync of a `query()`
@@ -777,33 +770,26 @@ class Indexer:
         device indexing + copies + syncs after the first).  Repeats the scan if the task table overflowed."""
         Q, P = keys.shape
         algo = self.choose_algo(Q, P)
-        n, nk = Q * k + Q + 2, Q * P + Q
+        n, words = Q * k + Q + 2, Q * k + Q + 2 + Q * P + Q
         host_form = self._host_form(k, fused) and Q > 0
         while True:
             pin = self._pin
-            if pin is None or pin.numel() < n + nk:
-                pin = self._pin = torch.empty((max(n + nk, 1 << 16),), dtype=torch.int32, pin_memory=True)
+            if pin is None or pin.numel() < words:
+                pin = self._pin = torch.empty((max(words, 1 << 16),), dtype=torch.int32, pin_memory=True)
             if host_form:           # the merge kernel stores into the pinned block itself: nothing to copy
-                self._range_tensors(q, keys, nkeys, k, 0, Q, algo, fused, pin[:n + nk])
-                tkey = self._last_tkey
+                self._range_tensors(q, keys, nkeys, k, 0, Q, algo, fused, pin[:words])
             else:
                 self._range_tensors(q, keys, nkeys, k, 0, Q, algo, fused)
-                pack, tkey = self._last_pack, self._last_tkey
-                pin[:n].copy_(pack, non_blocking=True)
+                to_ids, to_keys, to_nkeys, _ = pin.split((n, Q * P, Q, pin.numel() - words))
+                to_ids.copy_(self._last_pack, non_blocking=True)
                 if self.compat:
-                    pin[n:n + Q * P].view(Q, P).copy_(keys, non_blocking=True)
-                    pin[n + Q * P:n + nk].copy_(nkeys, non_blocking=True)
+                    to_keys.view(Q, P).copy_(keys, non_blocking=True)
+                    to_nkeys.copy_(nkeys, non_blocking=True)
             self._release_held()                                    # the device is busy now: free what an earlier call left with us
             torch.cuda.current_stream(q.device).synchronize()
             host = pin.numpy()
-            needed, overflow = int(host[n - 2]), int(host[n - 1])
-            if not overflow or Q == 0:
-                self._trim_task_table(tkey, needed, self._last_max_tasks)
-                if host_form:       # key rows [Q, P + 1]: nkeys, then the keys -- written for the queries with < k candidates only
-                    rows = host[n:n + nk].reshape(Q, P + 1)
-                    return host[:Q * k].reshape(Q, k), host[Q * k:Q * k + Q], rows[:, 1:], rows[:, 0]
-                return (host[:Q * k].reshape(Q, k), host[Q * k:Q * k + Q], host[n:n + Q * P].reshape(Q, P), host[n + Q * P:n + nk])
-            self._grow_task_table(tkey, needed, overflow)
+            if self._settle(self._last_tkey, int(host[n - 2]), int(host[n - 1]) if Q else 0, self._last_max_tasks):
+                return self._block_views(host, Q, k, P, host_form)
 
     # `query()` on a large batch scans it in `query_chunks` row ranges on the stream and converts range c to Python lists while
     # the device scans range c+1: the conversion (0.45 ms per 10^4 queries) is as long as the scan, and a single range leaves
@@ -824,55 +810,47 @@ class Indexer:
         """Generator over row ranges of the batch: (lo, hi, ids [hi-lo, k], counts [hi-lo], keys, nkeys) as host arrays, each
         yielded as soon as ITS scan and copies are done (one event per range; later ranges keep the device busy meanwhile)."""
         Q, P = keys.shape
-        dev = q.device
         algo = self.choose_algo(Q, P)
-        stream = torch.cuda.current_stream(dev)
+        stream = torch.cuda.current_stream(q.device)
         bounds = [(Q * c // n_chunks, Q * (c + 1) // n_chunks) for c in range(n_chunks)]
         per = max(hi - lo for lo, hi in bounds)
         words = (per * k + per + 2 + per * P + per + 3) // 4 * 4     # every range's block starts on a 16-byte boundary (the host-writing merge stores 16 bytes per lane there)
         if self._pin is None or self._pin.numel() < n_chunks * words:
             self._pin = torch.empty((max(n_chunks * words, 1 << 16),), dtype=torch.int32, pin_memory=True)
         pin = self._pin
-        inflight = []
         host_form = self._host_form(k, fused)
 
         def launch(c, lo, hi):
-            base, m = c * words, hi - lo
+            m = hi - lo
             n = m * k + m + 2
+            block = pin[c * words:c * words + n + m * P + m]
             if host_form and m:     # the merge kernel stores into the range's slice of the pinned block itself: nothing to copy
-                self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused, pin[base:base + n + m * P + m])
+                self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused, block)
             else:
                 self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused)
-                pin[base:base + n].copy_(self._last_pack, non_blocking=True)
+                to_ids, to_keys, to_nkeys = block.split((n, m * P, m))
+                to_ids.copy_(self._last_pack, non_blocking=True)
                 if self.compat:
-                    pin[base + n:base + n + m * P].view(m, P).copy_(keys[lo:hi], non_blocking=True)
-                    pin[base + n + m * P:base + n + m * P + m].copy_(nkeys[lo:hi], non_blocking=True)
+                    to_keys.view(m, P).copy_(keys[lo:hi], non_blocking=True)
+                    to_nkeys.copy_(nkeys[lo:hi], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(stream)
-            return ev, n, self._last_tkey, self._last_max_tasks
+            return ev, self._last_tkey, self._last_max_tasks
 
-        for c, (lo, hi) in enumerate(bounds):
-            inflight.append(launch(c, lo, hi))
+        inflight = [launch(c, lo, hi) for c, (lo, hi) in enumerate(bounds)]
         self._release_held()                                        # the device is busy now: free what an earlier call left with us
         host = pin.numpy()
         for c, (lo, hi) in enumerate(bounds):
             m = hi - lo
+            a = host[c * words:(c + 1) * words]
+            n = m * k + m + 2
             while True:
-                ev, n, tkey, max_tasks = inflight[c]
+                ev, tkey, max_tasks = inflight[c]
                 ev.synchronize()
-                base = c * words
-                needed, overflow = int(host[base + n - 2]), int(host[base + n - 1])
-                if not overflow or m == 0:
-                    self._trim_task_table(tkey, needed, max_tasks)
+                if self._settle(tkey, int(a[n - 2]), int(a[n - 1]) if m else 0, max_tasks):
                     break
-                self._grow_task_table(tkey, needed, overflow)       # task table too small for this range: grow, repeat it
-                inflight[c] = launch(c, lo, hi)
-            a = host[base:base + n + m * P + m]
-            if host_form and m:     # key rows [m, P + 1]: nkeys, then the keys -- written for the queries with < k candidates only
-                rows = a[n:].reshape(m, P + 1)
-                yield (lo, hi, a[:m * k].reshape(m, k), a[m * k:m * k + m], rows[:, 1:], rows[:, 0])
-            else:
-                yield (lo, hi, a[:m * k].reshape(m, k), a[m * k:m * k + m], a[n:n + m * P].reshape(m, P), a[n + m * P:n + m * P + m])
+                inflight[c] = launch(c, lo, hi)                     # task table too small for this range, grown: repeat it
+            yield (lo, hi) + self._block_views(a, m, k, P, host_form and m > 0)
 
     # The fresh result lists (10^4 per batch) land in the collector's youngest generation; the first container allocation after
     # the conversion then runs a generation-0 collection that walks all of them: 0.25-0.32 ms of a 1.55 ms call on the bench box
@@ -1003,21 +981,19 @@ class Indexer:
         elif self._n_chunks() > 1 and q.shape[0] >= self._n_chunks() * self._CHUNK_MIN_ROWS:
             results, counts = [], []
             for lo, hi, idx_h, nc_h, keys_h, nkeys_h in self._chunked_results(q, keys, nkeys, k, self._n_chunks(), fused):
-                key_sets = {}
-                if self.compat:
-                    for qi in np.nonzero(nc_h < k)[0].tolist():
-                        key_sets[qi] = host_key_set(keys_h[qi], int(nkeys_h[qi]), self._hashing.key_mode)
-                r, c = self._to_lists(key_sets, idx_h, nc_h, k)
+                r, c = self._to_lists(self._short_key_sets(nc_h, keys_h, nkeys_h, k), idx_h, nc_h, k)
                 results += r
                 counts += c
             return results, counts
         else:
             idx_h, nc_h, keys_h, nkeys_h = self._host_results(q, keys, nkeys, k, fused)
-        key_sets = {}
-        if self.compat:  # F7 needs the key SET (Python iteration order) of the queries with < k candidates only
-            for qi in np.nonzero(nc_h < k)[0].tolist():
-                key_sets[qi] = host_key_set(keys_h[qi], int(nkeys_h[qi]), self._hashing.key_mode)
-        return self._to_lists(key_sets, idx_h, nc_h, k)
+        return self._to_lists(self._short_key_sets(nc_h, keys_h, nkeys_h, k), idx_h, nc_h, k)
+
+    def _short_key_sets(self, nc_h, keys_h, nkeys_h, k):
+        """{query: its key set} for the queries with < k candidates: F7 (compat) needs their key SETS (Python iteration order) only."""
+        if not self.compat:
+            return {}
+        return {qi: host_key_set(keys_h[qi], int(nkeys_h[qi]), self._hashing.key_mode) for qi in np.nonzero(nc_h < k)[0].tolist()}
 
     def _as_queries(self, query_vectors):
         q = query_vectors

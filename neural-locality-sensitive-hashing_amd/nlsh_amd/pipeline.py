@@ -141,20 +141,13 @@ class QueryPipeline:
     def _make_step(self, s):
         """The slot's `nlsh_step_t`: everything about its launches that does not change from batch to batch."""
         import ctypes
-        ix, h = self.indexer, self.indexer._hashing
-        (n_layers, dims_arr, packed_ptr, act, key_mode, n_probes), _ = h.encode_args(self.P, s.keys, s.nkeys)
-        pre, post = ix._scan_args(self.Q, self.d, s.keys, s.nkeys, self.k, self.algo, self.max_tasks, s.out_dist, s.out_idx, s.out_keys,
-                                  s.ncand, s.status, s.ws)
-        (corpus, row_stride, d, gid, uniq, offsets, order, n_buckets, cell_of, cell_offsets, n_cells, inv_norm) = pre
-        (Q, qkeys, nkeys, P, k, metric, algo, seg, out_dist, out_idx, out_keys, ncand, status, ws, ws_bytes, max_tasks) = post
-        desc = _capi.StepDesc(
-            n_layers=n_layers, act=act, key_mode=key_mode, n_probes=n_probes, dims=ctypes.cast(dims_arr, ctypes.c_void_p), packed=packed_ptr,
-            n_multi_rows=self._n_multi, corpus_sorted=corpus, row_stride=row_stride, gid=gid, uniq_keys=uniq, offsets=offsets,
-            bucket_order=order, cell_of=cell_of, cell_offsets=cell_offsets, inv_norm=inv_norm, d=d, n_buckets=n_buckets, n_cells=n_cells,
-            k=k, metric=metric, algo=algo, seg_rows=seg, hold_done=int(self._hold_done), Q=Q, qkeys=qkeys, nkeys=nkeys, out_dist=out_dist,
-            out_idx=out_idx, out_keys=out_keys, out_ncand=ncand, status=status, workspace=ws, workspace_bytes=ws_bytes, max_tasks=max_tasks,
-            front=self.front.cuda_stream, plan=self.plan.cuda_stream if self.plan is not None else None, mid=self.mid.cuda_stream,
-            tail=self.tail.cuda_stream)
+        ix = self.indexer
+        enc, _ = ix._hashing.encode_args(self.P, s.keys, s.nkeys)
+        fields = ix._scan_fields(self.Q, self.d, s.keys, s.nkeys, self.k, self.algo, self.max_tasks, s.out_dist, s.out_idx, s.out_keys,
+                                 s.ncand, s.status, s.ws)
+        desc = ix._step_desc(fields, enc, self._n_multi, self._hold_done,
+                             (self.front.cuda_stream, self.plan.cuda_stream if self.plan is not None else None, self.mid.cuda_stream,
+                              self.tail.cuda_stream))
         handle = ctypes.c_void_p()
         if self.graph:
             _capi.check(self._lib.nlsh_step_create_graph(ctypes.byref(desc), ctypes.sizeof(desc), s.lane.cuda_stream, ctypes.byref(handle)))

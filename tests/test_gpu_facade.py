@@ -512,3 +512,63 @@ def test_query_keeps_its_range_plans_and_follows_weight_updates_and_table_growth
     ix._max_tasks = {key: 64 for key in ix._max_tasks}        # every kept descriptor now names a table that is too small
     got = ix.query(qa, k=k, hash_times=P, seed=901)
     assert list(got) == list(fresh(qa, 901)) and min(ix._max_tasks[key] for key in ix._max_tasks if key[1] in (2250,)) > 64
+
+
+# ----------------------------------------------------------------------------- query()'s launch paths under task-table overflow
+_overflow_case = {}
+
+
+def _overflow_index():
+    if not _overflow_case:
+        from nlsh_amd.data import SIFT
+        from nlsh_amd.indexer import Indexer
+        N, Q, d, H = 20000, 2100, 24, 10
+        corpus, mean, std = synth.standardise(synth.sift_like(N, d, seed=411))
+        queries = synth.standardise(synth.sift_like(Q, d, seed=412), mean, std)[0]
+        Ws, bs = synth.make_weights([d, 32, H], seed=413)
+        ix = Indexer(make_hashing(d, [32], H, Ws, bs, compat=False, seed=5), dev(corpus), SIFT.distance, compat=False)
+        ix._CHUNK_MIN_ROWS = 1024
+        _overflow_case.update(ix=ix, q=dev(queries))
+    return _overflow_case["ix"], _overflow_case["q"]
+
+
+@pytest.mark.parametrize("k,algo,probes", [(10, None, None), (65, None, None), (10, "query", None), (10, None, "ranked")],
+                         ids=["k10_tiled", "k65_tiled_copy_form", "k10_query_major", "k10_ranked"])
+def test_query_launch_paths_repeat_an_overflowed_range_and_report_what_they_ran_with(k, algo, probes):
+    """Every way `Indexer.query` launches a row range -- the kept plan whose merge kernel writes the host block (k = 10, tiled), the
+    kept plan with device->host copies (k = 65), and the unfused ranges of the query-major schedule and of a ranked hasher -- with
+    every task table set to ONE entry behind a warm call: the range overflows, the table is grown, the range is repeated, and the
+    lists equal those derived from `hash_device` + a checked `scan_tensors` on the same seed, as one range and as two.  After each
+    call the `last_*` / `_last_*` attributes name the last range's launch."""
+    from nlsh_amd import _capi
+    ix, q = _overflow_index()
+    Q, P, seed = q.shape[0], 10, 4321
+    ix.algo = algo
+    try:
+        keys, nkeys = ix.hash_device(q, hash_times=P, seed=seed, probes=probes)
+        _, idx, nc, _ = ix.scan_tensors(q, keys, nkeys, k=k, check=True)
+        idx, nc = idx.cpu().numpy(), nc.cpu().numpy()
+        want = [row.tolist() if n >= k else [int(v) for v in row if v >= 0] for row, n in zip(idx, nc)], nc.tolist()
+        # on the CPU, from the key histogram of the seeded data: the case holds queries with at least k candidates (the lists compared
+        # below are not empty ones) -- and the scan's counts are that histogram's
+        uniq, sizes = np.unique(ix.corpus_keys.cpu().numpy(), return_counts=True)
+        kh, nkh = keys.cpu().numpy(), nkeys.cpu().numpy()
+        pos = np.minimum(np.searchsorted(uniq, kh), len(uniq) - 1)
+        cand = (np.where(uniq[pos] == kh, sizes[pos], 0) * (np.arange(P)[None, :] < nkh[:, None])).sum(1)
+        assert int((cand >= k).sum()) > 0 and np.array_equal(cand, nc)
+        if algo is None:
+            assert ix.choose_algo(Q // 2, P) == _capi.SCAN_BUCKET_TILED
+        for chunks in (1, 2):
+            ix.query_chunks = chunks
+            ix.query(q, k=k, hash_times=P, seed=seed - 1, probes=probes)              # warm: the range's plan and task table exist
+            ix._max_tasks = {key: 1 for key in ix._max_tasks}                         # ... and now name a one-entry task table
+            got = ix.query(q, k=k, hash_times=P, seed=seed, probes=probes)
+            assert got[1] == want[1]
+            assert got[0] == want[0]
+            m = Q - Q * (chunks - 1) // chunks                                        # rows of the last range
+            assert ix._last_tkey in ix._max_tasks and ix._last_tkey[1:3] == (m, P)
+            assert ix._max_tasks[ix._last_tkey] > 1
+            assert int(ix.last_status.cpu()[1]) == 0
+            assert ix.last_algo == ix.choose_algo(m, P) and ix.last_window == ix.choose_window(m, P, ix.last_algo)
+    finally:
+        ix.algo, ix.query_chunks = None, None

@@ -570,6 +570,98 @@ def test_deferred_release_never_holds_more_than_two_results():
     assert ix._held == []
 
 
+def _bare_indexer_for_task_tables():
+    """Host logic only: no index, no device -- the attributes the task-table policy reads, on an object that never ran `__init__`."""
+    from nlsh_amd.indexer import Indexer
+    ix = Indexer.__new__(Indexer)
+    ix.bucket_sizes, ix.n_buckets = np.array([300, 20, 20, 4, 1, 1]), 6
+    ix.window_rows, ix.seg_rows, ix.algo = None, 0, None
+    ix._e_sb, ix._max_tasks, ix._ws = None, {}, {("s", True): 1}
+    return ix
+
+
+def test_task_table_policy_seeds_reuses_trims_and_grows_on_a_bare_indexer():
+    """One sizing and one retry rule for every launch path of `Indexer` (`_task_table`, `_settle`): a batch shape's table is seeded from
+    the estimate, or from the smallest table of the same schedule and window that served a batch at least as large; the status words
+    of a launch trim it, grow it, or -- flags 2 and 3 -- raise and drop every workspace.  `_max_tasks` and `_estimate_tasks` are looked
+    up through the instance at every use (tests and tools rebind both)."""
+    from nlsh_amd import _capi
+    ix = _bare_indexer_for_task_tables()
+    tiled, query_major = _capi.SCAN_BUCKET_TILED, _capi.SCAN_QUERY_MAJOR
+    # the documented estimate: E = sum(s^2) / sum(s), the size of the bucket a point lands in; tiled tasks = (256-row segment, <= 16
+    # queries) over min(P, 4) probes + one per bucket; query-major = one per query + its min(P, 4) probes' 512-row segments; the table
+    # holds 1.5x that + 1024, at least Q + 1024
+    s = ix.bucket_sizes.astype(np.float64)
+    biased = float((s * s).sum() / s.sum())
+    want_tiled = int(max(1.5 * (257 * 4 * (1.0 / 16 + biased / 256 / 16) + 6) + 1024, 257 + 1024))
+    want_query = int(max(1.5 * (3 * (1.0 + 4 * biased / 512)) + 1024, 3 + 1024))
+    assert (want_tiled, want_query) == (1281, 1037)
+    assert ix._task_table(tiled, 257, 10) == ((tiled, 257, 10, 64), 64, 1281) and ix._max_tasks == {(tiled, 257, 10, 64): 1281}
+    assert ix._task_table(query_major, 3, 10) == ((query_major, 3, 10, 0), 0, 1037) and ix._max_tasks[(query_major, 3, 10, 0)] == 1037
+    assert ix._tkey(tiled, 257, 10) == (tiled, 257, 10, 64)
+    # a smaller batch of the same schedule and window takes the 257-row entry's value, not a new estimate (which would be 1094) ...
+    ix._max_tasks[(tiled, 257, 10, 64)] = 777
+    assert ix._task_table(tiled, 70, 10) == ((tiled, 70, 10, 64), 64, 777) and ix._max_tasks[(tiled, 70, 10, 64)] == 777
+    # ... a larger one, more probes or another window do not
+    assert ix._task_table(tiled, 258, 10)[2] == ix._estimate_tasks(258, 10, 512, tiled) != 777
+    assert ix._task_table(tiled, 70, 11)[2] == ix._estimate_tasks(70, 11, 512, tiled) != 777
+    ix.window_rows = 128
+    assert ix._task_table(tiled, 70, 10) == ((tiled, 70, 10, 128), 128, ix._estimate_tasks(70, 10, 512, tiled))
+    ix.window_rows = None
+    # a replaced estimate on the instance and a rebound dict are both honoured
+    ix._estimate_tasks = lambda *a, **kw: 64
+    assert ix._task_table(tiled, 9000, 10)[2] == 64
+    rebound = ix._max_tasks = {(tiled, 500, 10, 64): 5}
+    assert ix._task_table(tiled, 400, 10)[2] == 5 and ix._task_table(tiled, 501, 10)[2] == 64
+    assert ix._max_tasks is rebound and rebound == {(tiled, 500, 10, 64): 5, (tiled, 400, 10, 64): 5, (tiled, 501, 10, 64): 64}
+    # the status words of a launch: trim (only a table more than 3x what the batch needed + 1024), keep, grow
+    tkey = (tiled, 500, 10, 64)
+    assert ix._settle(tkey, 100, 0, 5000) is True and ix._max_tasks[tkey] == 1149
+    ix._max_tasks[tkey] = 3372
+    assert ix._settle(tkey, 100, 0, 3372) is True and ix._max_tasks[tkey] == 3372          # 3 * (100 + 1024) >= 3372: nothing changes
+    assert ix._settle(tkey, 4000, 1, 3372) is False and ix._max_tasks[tkey] == 6024
+    assert ix._ws == {("s", True): 1}
+    for flag, code in ((2, _capi.E_WORKSPACE), (3, _capi.E_INVALID)):
+        ix._ws = {("s", True): 1}
+        with pytest.raises(_capi.NlshHipError) as err:
+            ix._settle(tkey, 4000, flag, 6024)
+        assert err.value.code == code and ix._ws == {} and ix._max_tasks[tkey] == 6024
+
+
+def test_descriptor_builder_fills_every_field_of_the_step_descriptor_by_name(monkeypatch):
+    """`Indexer._step_desc` is the one place the package fills a `_capi.StepDesc` (the fused batch call, the kept range plans and the
+    pipeline's slots all go through it): the keywords it passes are exactly the structure's fields, so a dropped or misspelt one is
+    noticed without a GPU, and each value lands in the field of its name."""
+    import ctypes
+    from nlsh_amd import _capi
+    from nlsh_amd.indexer import Indexer
+    ix = Indexer.__new__(Indexer)
+    ix.metric, ix.l2_form, ix.seg_rows, ix.window_rows, ix.n_buckets, ix.row_stride = "l2", "folded", 0, 0, 7, 28
+    t = {name: torch.zeros(4, dtype=torch.int32) for name in ("corpus_sorted", "gid", "uniq_keys", "offsets", "bucket_order", "keys", "nkeys",
+                                                               "out_dist", "out_idx", "ncand", "status", "ws")}
+    ix.corpus_sorted, ix.gid, ix.uniq_keys, ix.offsets, ix.bucket_order, ix.inv_norm = (t["corpus_sorted"], t["gid"], t["uniq_keys"],
+                                                                                      t["offsets"], t["bucket_order"], None)
+    keys = t["keys"].view(2, 2)
+    fields = ix._scan_fields(2, 25, keys, t["nkeys"], 10, _capi.SCAN_BUCKET_MAJOR, 99, t["out_dist"], t["out_idx"], None, t["ncand"],
+                             t["status"], t["ws"])
+    dims = _capi.int_array([25, 32, 10])
+    seen = []
+    real = _capi.StepDesc
+    monkeypatch.setattr(_capi, "StepDesc", lambda **kw: seen.append(kw) or real(**kw))
+    desc = Indexer._step_desc(fields, (2, dims, 0x1000, _capi.ACT_TANH, _capi.KEY_FULL, 2), 1, hold_done=1, streams=(0x10, None, 0x30, 0x40))
+    assert len(seen) == 1 and sorted(seen[0]) == sorted(f[0] for f in real._fields_) and len(seen[0]) == len(real._fields_)
+    want = dict(n_layers=2, act=_capi.ACT_TANH, key_mode=_capi.KEY_FULL, n_probes=2, dims=ctypes.addressof(dims), packed=0x1000, n_multi_rows=1,
+                corpus_sorted=t["corpus_sorted"].data_ptr(), row_stride=28, gid=t["gid"].data_ptr(), uniq_keys=t["uniq_keys"].data_ptr(),
+                offsets=t["offsets"].data_ptr(), bucket_order=t["bucket_order"].data_ptr(), cell_of=None, cell_offsets=None, inv_norm=None,
+                d=25, n_buckets=7, n_cells=0, k=10, metric=_capi.METRIC_L2_EPS_FOLDED, algo=_capi.SCAN_BUCKET_MAJOR, seg_rows=512, hold_done=1,
+                Q=2, qkeys=keys.data_ptr(), nkeys=t["nkeys"].data_ptr(), out_dist=t["out_dist"].data_ptr(), out_idx=t["out_idx"].data_ptr(),
+                out_keys=None, out_ncand=t["ncand"].data_ptr(), status=t["status"].data_ptr(), workspace=t["ws"].data_ptr(), workspace_bytes=4,
+                max_tasks=99, front=0x10, plan=None, mid=0x30, tail=0x40)
+    assert {name: getattr(desc, name) for name, _ in real._fields_} == want
+    none = Indexer._step_desc(fields, (2, dims, 0x1000, _capi.ACT_SIGMOID, _capi.KEY_REF_INT16, 2), 0)      # the query() forms: no streams
+    assert (none.front, none.plan, none.mid, none.tail, none.hold_done) == (None, None, None, None, 0)
+
+
 def test_design_md_stays_within_120_columns():
     """DESIGN.md is wrapped (tools/wrap_md.py re-flows it; tables and code are reported, not altered)."""
     over = [(i + 1, len(ln)) for i, ln in enumerate(open(os.path.join(ROOT, "DESIGN.md")).read().split("\n")) if len(ln) > 120]

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Does walking the cells' schedule order in alternating directions on consecutive batches let the Infinity Cache serve part of a batch?
-(r06 experiment; `Indexer.alternate_order`).  Sequential device-resident steps over 4 rotating batches, scan kernel by HIP events:
-same order every batch | alternating | alternating behind a prefix of the largest cells | same order with the cache flushed between
-batches (a 512-MiB write: what a batch costs when NOTHING of the previous one is left on the die).
+"""How much of a batch does the Infinity Cache serve from what the previous batch left on the die?  Sequential device-resident steps
+over 4 rotating batches, scan kernel by HIP events: the launch as it is | the same launch with the cache flushed between batches (a
+512-MiB write: what a batch costs when NOTHING of the previous one is left on the die).  (The r06 experiment that walked the cells'
+schedule order in alternating directions on consecutive batches was measured with this tool and removed: DESIGN.md.)
 
     python tools/order_alternation.py glove|clusters|sift1m
 """
@@ -43,8 +43,7 @@ for a, b in ev:
     a.record(); b.record()
 
 
-def run(alternate, keep=0, flush_between=False):
-    Indexer.alternate_order, Indexer.alternate_keep = alternate, keep
+def run(flush_between=False):
     for i in range(4):
         ix.query_tensors(qb[i % B], k=10, hash_times=10, seed=10 + i, check=False)
     torch.cuda.synchronize()
@@ -59,10 +58,6 @@ def run(alternate, keep=0, flush_between=False):
 
 out = {"workload": wl}
 for rep in range(2):
-    out[f"same_order_{rep}"] = run(False)
-    out[f"alternating_{rep}"] = run(True)
-    out[f"alternating_keep_256_{rep}"] = run(True, 256)
-    out[f"alternating_keep_2048_{rep}"] = run(True, 2048)
-out["same_order_cache_flushed_between_batches"] = run(False, flush_between=True)
-Indexer.alternate_order = False
+    out[f"same_order_{rep}"] = run()
+out["same_order_cache_flushed_between_batches"] = run(flush_between=True)
 print(json.dumps(out))
