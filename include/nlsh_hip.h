@@ -170,6 +170,29 @@ int nlsh_probe_ranked(const float *z, int64_t z_stride, const uint32_t *code, in
                       int32_t *keys_out, int32_t *nkeys_out, float *cost_out /* nullable */,
                       nlsh_stream_t stream);
 
+/* nlsh_probe_ranked with a per-row CANDIDATE BUDGET: a row walks its ranked keys, looks each one's bucket size up in the index and
+ * stops after the first key that brings its candidate count to `budget` (n_probes is the cap).  The query-adaptive form of
+ * multi-probe LSH: the work knob is candidates, not probes, whatever the skew of the bucket sizes.
+ *   uniq_keys [dev] int32 [n_buckets] ascending as signed int32, offsets [dev] int32 [n_buckets + 1]: the CSR arrays of nlsh_build_csr
+ *   budget >= 1;  ncand_out [dev] int32 [n] (nullable): the candidates of the kept keys;  everything else as for nlsh_probe_ranked
+ * For one row let K[0..nk) be the keys nlsh_probe_ranked writes for the same z, code, H, key_mode, n_probes, n_multi_rows (already
+ * de-duplicated in first-occurrence order).  size(key) = offsets[b+1] - offsets[b] if uniq_keys[b] == key for some b, else 0;
+ * cum(m) = sum of size(K[i]) over i < m (distinct keys are disjoint buckets: cum <= N < 2^31).  Then
+ *   nkeys_out = min{ m in [1, nk] : cum(m) >= budget }, or nk if there is none  (slot 0, the hard key, is always kept; rows >=
+ *   n_multi_rows keep it alone);  keys_out = K[0..nkeys_out) then zeros;  cost_out = the kept costs then +inf;  ncand_out = cum(nkeys_out).
+ * The result is a prefix of the unbudgeted row; with budget = INT32_MAX it is nlsh_probe_ranked's output in every word.
+ * The pop loop itself ends at the stop (nothing is enumerated and then cut); a popped code whose key was kept before takes no slot and
+ * adds no candidates, decided at pop time.  A lookup is a 64-way search across the lanes: ceil(log64(n_buckets)) dependent global round
+ * trips, one fewer above 64 buckets (the first round's probes are loaded once per row).
+ * Checked on the host before anything touches the device: budget < 1, n_buckets < 0, NULL uniq_keys or offsets with n_buckets > 0
+ * (NLSH_E_INVALID), then every refusal of nlsh_probe_ranked.  n_buckets == 0 is legal (every size is 0, no row stops early); n = 0 is
+ * NLSH_OK without a launch. */
+int nlsh_probe_ranked_budget(const float *z, int64_t z_stride, const uint32_t *code, int64_t n, int H, int key_mode,
+                             int n_probes, int64_t n_multi_rows,
+                             const int32_t *uniq_keys, const int32_t *offsets, int32_t n_buckets, int32_t budget,
+                             int32_t *keys_out, int32_t *nkeys_out, float *cost_out /* nullable */, int32_t *ncand_out /* nullable */,
+                             nlsh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Index build.  Replaces build_index (nlsh/indexer.py:6-24): key -> ascending row list, as CSR.
  * ------------------------------------------------------------------------------------------- */

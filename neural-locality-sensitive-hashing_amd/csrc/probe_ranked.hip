@@ -16,6 +16,16 @@
 //   - the popped codes stay in registers (slot p = lane p & 63) until the row is de-duplicated and stored.
 // Every register set is named, none is indexed at run time: the kernel has no private segment.  The loop makes a fixed
 // n_probes - 1 pops and every slot index is bounded by a constant, whatever the bits of z are.
+//
+// nlsh_probe_ranked_budget is the same loop (`probe_row<true>`) with a per-row stop: each KEPT key's bucket size is looked up in the
+// index's CSR arrays and the loop ends after the first key that brings the row's candidate count to `budget`.  What differs:
+//   - the first-occurrence de-duplication happens at pop time (the popped key against the kept keys, which sit one per lane: a compare
+//     and a ballot), so a duplicate takes no slot and adds no candidates, and kept slot c lives in lane c & 63;
+//   - the lookup is a 64-way search over uniq_keys: lane l probes the l-th of 64 evenly spaced entries of the current range, a ballot
+//     of `entry <= key` names the sub-range, the range shrinks 64-fold per round.  The first round's 64 entries depend on n_buckets
+//     alone and are loaded once per row into a register; the last round (stride 1) loads the two offsets beside the key, so a lookup
+//     is ceil(log64(n_buckets)) dependent global round trips, one fewer when n_buckets > 64 (65 k buckets: 2).
+// The unbudgeted kernel is `probe_row<false>`: every budget branch is `if constexpr`, its code is what it was.
 #include "common.h"
 
 namespace nlsh {
@@ -34,10 +44,42 @@ __device__ __forceinline__ int32_t key_of(uint32_t code, int key_mode) {
     return key_mode == NLSH_KEY_REF_INT16 ? (int32_t)(int16_t)(uint16_t)(code & 0xFFFFu) : (int32_t)code;
 }
 
-__global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_kernel(const float *__restrict__ z, long long z_stride,
-                                                                    const uint32_t *__restrict__ code, long long n, int H, int key_mode,
-                                                                    int P, long long n_multi_rows, int32_t *__restrict__ keys_out,
-                                                                    int32_t *__restrict__ nkeys_out, float *__restrict__ cost_out) {
+// 64-way search of `key` in uniq_keys [nb] (ascending as signed int32) -> its bucket's size, 0 when absent.  Everything but `lane` is
+// wave-uniform.  `top` = uniq_keys[lane * ceil(nb / 64)] where that index is < nb (the first round's probes, loaded once per row).
+__device__ __forceinline__ int32_t bucket_size(int32_t key, const int32_t *__restrict__ uniq, const int32_t *__restrict__ offsets,
+                                               uint32_t nb, int32_t top, int lane) {
+    uint32_t lo = 0, len = nb;   // the range [lo, lo + len) holds the key if anything does; len >= 1
+    bool first = true;
+    while (true) {
+        const uint32_t step = (len + 63u) >> 6;
+        const uint32_t off = (uint32_t)lane * step;          // < len + 63: no wrap for len < 2^31
+        const bool valid = off < len;
+        const uint32_t idx = lo + off;                          // < lo + len <= nb when valid
+        int32_t v = top;
+        if (!first) v = valid ? uniq[idx] : 0;
+        if (step == 1u) {
+            int32_t sz = 0;
+            if (valid) sz = offsets[idx + 1] - offsets[idx];  // issued beside the key's load: no extra round trip
+            const unsigned long long eq = __ballot(valid && v == key);
+            if (eq == 0ull) return 0;
+            return (int32_t)lane_read((uint32_t)sz, __ffsll((long long)eq) - 1);
+        }
+        const unsigned long long le = __ballot(valid && v <= key);   // ascending keys: a prefix of the valid lanes
+        if (le == 0ull) return 0;                                   // below the range's first key
+        const uint32_t c = (uint32_t)__popcll(le) - 1u;
+        const uint32_t rest = len - c * step;                       // entries from the chosen probe to the range's end
+        lo += c * step;
+        len = rest < step ? rest : step;
+        first = false;
+    }
+}
+
+template <bool BUDGET>
+__device__ __forceinline__ void probe_row(const float *__restrict__ z, long long z_stride, const uint32_t *__restrict__ code, long long n,
+                                          int H, int key_mode, int P, long long n_multi_rows, const int32_t *__restrict__ uniq,
+                                          const int32_t *__restrict__ offsets, uint32_t nb, int32_t budget,
+                                          int32_t *__restrict__ keys_out, int32_t *__restrict__ nkeys_out, float *__restrict__ cost_out,
+                                          int32_t *__restrict__ ncand_out) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * PR_ROWS + (threadIdx.x >> 6);
     if (row >= n) return;   // wave-uniform
@@ -45,7 +87,8 @@ __global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_kernel(const float 
     // ---- costs, sorted by (bit pattern, bit index): lanes past H hold a sentinel above every cleared-sign pattern
     uint32_t c = PR_NONE;
     if (lane < H) c = __builtin_bit_cast(uint32_t, z[row * z_stride + lane]) & 0x7FFFFFFFu;
-    const uint32_t hard = code[row];
+    // budgeted: made wave-uniform for the compiler (one address per wave), so the popped keys and the lookups are scalar
+    const uint32_t hard = BUDGET ? (uint32_t)__builtin_amdgcn_readfirstlane((int)code[row]) : code[row];
     int rank = 0;
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
@@ -73,7 +116,18 @@ __global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_kernel(const float 
     // popped subsets: slot p in lane p & 63; slot 0 is the empty set
     uint32_t o_code0 = hard, o_cost0 = 0u, o_code1 = hard, o_cost1 = 0u;
     int cnt = 1;
-    const int np = row < n_multi_rows ? P : 1;
+    int np = row < n_multi_rows ? P : 1;
+    // budget: slot 0 is kept whatever its bucket holds; a row whose hard bucket meets the budget makes no pop
+    [[maybe_unused]] int32_t top = 0, cum = 0;
+    [[maybe_unused]] const bool collide = key_mode == NLSH_KEY_REF_INT16 && H > 16;
+    if constexpr (BUDGET) {
+        if (nb) {
+            const uint32_t at = (uint32_t)lane * ((nb + 63u) >> 6);
+            if (at < nb) top = uniq[at];
+            cum = bucket_size(key_of(hard, key_mode), uniq, offsets, nb, top, lane);
+        }
+        if (cum >= budget) np = 1;
+    }
     for (int p = 1; p < np; ++p) {
         const unsigned long long ka = (unsigned long long)a_cost << 32 | a_mask, kb = (unsigned long long)b_cost << 32 | b_mask;
         const bool use_b = kb < ka;
@@ -88,12 +142,34 @@ __global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_kernel(const float 
         const int wl = __ffsll((long long)__ballot(km == g)) - 1;
         const uint32_t t = (uint32_t)(g >> 32), mask = (uint32_t)g;
         const uint32_t tp = lane_read(use_b ? b_tp : a_tp, wl), flip = lane_read(use_b ? b_flip : a_flip, wl);
-        if (p < 64) {
-            if (lane == p) { o_code0 = hard ^ flip; o_cost0 = t; }
-        } else if (lane == p - 64) {
-            o_code1 = hard ^ flip; o_cost1 = t;
+        [[maybe_unused]] bool stop = false;
+        if constexpr (BUDGET) {
+            // a key seen before adds no candidates and takes no slot (its children are still pushed: the enumeration is the same)
+            const int32_t key = key_of(hard ^ flip, key_mode);
+            bool dup = false;
+            if (collide)
+                dup = __ballot((lane < cnt && key_of(o_code0, key_mode) == key) || (lane + 64 < cnt && key_of(o_code1, key_mode) == key)) != 0ull;
+            if (!dup) {
+                if (cnt < 64) {
+                    if (lane == cnt) { o_code0 = hard ^ flip; o_cost0 = t; }
+                } else if (lane == cnt - 64) {
+                    o_code1 = hard ^ flip; o_cost1 = t;
+                }
+                ++cnt;
+                if (nb) cum += bucket_size(key, uniq, offsets, nb, top, lane);   // disjoint buckets: cum <= N < 2^31
+                stop = cum >= budget;
+            }
+        } else {
+            if (p < 64) {
+                if (lane == p) { o_code0 = hard ^ flip; o_cost0 = t; }
+            } else if (lane == p - 64) {
+                o_code1 = hard ^ flip; o_cost1 = t;
+            }
+            cnt = p + 1;
         }
-        cnt = p + 1;
+        if constexpr (BUDGET) {
+            if (stop) break;   // wave-uniform; the frontier is not needed any more
+        }
         // children: only the last term of the chain changes (shift) or is appended (expand)
         const int j = 31 - __clz((int)mask);
         uint32_t s_cost = PR_NONE, s_mask = PR_NONE, s_tp = 0, s_flip = 0;
@@ -117,7 +193,7 @@ __global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_kernel(const float 
     // ---- keys, first-occurrence de-duplication (only 16-bit keys of wider codes can collide), store
     const int32_t key0 = key_of(o_code0, key_mode), key1 = key_of(o_code1, key_mode);
     bool first0 = lane < cnt, first1 = lane + 64 < cnt;
-    if (key_mode == NLSH_KEY_REF_INT16 && H > 16) {
+    if (!BUDGET && key_mode == NLSH_KEY_REF_INT16 && H > 16) {   // (the budgeted loop kept distinct keys only)
         for (int u = 0; u < cnt; ++u) {
             const int32_t ku = (int32_t)(u < 64 ? lane_read((uint32_t)key0, u) : lane_read((uint32_t)key1, u - 64));
             if (u < lane && ku == key0) first0 = false;
@@ -144,6 +220,26 @@ __global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_kernel(const float 
         }
     }
     if (lane == 0) nkeys_out[row] = nk;
+    if constexpr (BUDGET) {
+        if (lane == 0 && ncand_out) ncand_out[row] = cum;
+    }
+}
+
+__global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_kernel(const float *__restrict__ z, long long z_stride,
+                                                                    const uint32_t *__restrict__ code, long long n, int H, int key_mode,
+                                                                    int P, long long n_multi_rows, int32_t *__restrict__ keys_out,
+                                                                    int32_t *__restrict__ nkeys_out, float *__restrict__ cost_out) {
+    probe_row<false>(z, z_stride, code, n, H, key_mode, P, n_multi_rows, nullptr, nullptr, 0u, 0, keys_out, nkeys_out, cost_out, nullptr);
+}
+
+__global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_budget_kernel(const float *__restrict__ z, long long z_stride,
+                                                                           const uint32_t *__restrict__ code, long long n, int H,
+                                                                           int key_mode, int P, long long n_multi_rows,
+                                                                           const int32_t *__restrict__ uniq, const int32_t *__restrict__ offsets,
+                                                                           uint32_t nb, int32_t budget, int32_t *__restrict__ keys_out,
+                                                                           int32_t *__restrict__ nkeys_out, float *__restrict__ cost_out,
+                                                                           int32_t *__restrict__ ncand_out) {
+    probe_row<true>(z, z_stride, code, n, H, key_mode, P, n_multi_rows, uniq, offsets, nb, budget, keys_out, nkeys_out, cost_out, ncand_out);
 }
 
 }  // namespace
@@ -151,8 +247,9 @@ __global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_kernel(const float 
 
 using namespace nlsh;
 
-extern "C" int nlsh_probe_ranked(const float *z, int64_t z_stride, const uint32_t *code, int64_t n, int H, int key_mode, int n_probes,
-                                 int64_t n_multi_rows, int32_t *keys_out, int32_t *nkeys_out, float *cost_out, nlsh_stream_t stream) {
+// the refusals both entry points make, before anything touches the device
+static int probe_ranked_check(const float *z, int64_t z_stride, const uint32_t *code, int64_t n, int H, int key_mode, int n_probes,
+                              const int32_t *keys_out, const int32_t *nkeys_out) {
     NLSH_REQUIRE(n >= 0, NLSH_E_INVALID, "probe_ranked: n=%lld", (long long)n);
     NLSH_REQUIRE(key_mode == NLSH_KEY_REF_INT16 || key_mode == NLSH_KEY_FULL, NLSH_E_INVALID, "probe_ranked: key_mode=%d", key_mode);
     NLSH_REQUIRE(H >= 1 && H <= NLSH_MAX_HASH_BITS, NLSH_E_UNSUPPORTED, "probe_ranked: H=%d not in [1, NLSH_MAX_HASH_BITS=%d]", H,
@@ -161,11 +258,36 @@ extern "C" int nlsh_probe_ranked(const float *z, int64_t z_stride, const uint32_
                  "probe_ranked: n_probes=%d not in [1, NLSH_MAX_ENCODE_PROBES=%d]", n_probes, NLSH_MAX_ENCODE_PROBES);
     NLSH_REQUIRE(z_stride >= H, NLSH_E_INVALID, "probe_ranked: z_stride=%lld < H=%d", (long long)z_stride, H);
     NLSH_REQUIRE(n == 0 || (z && code && keys_out && nkeys_out), NLSH_E_INVALID, "probe_ranked: null pointer (z, code, keys_out and nkeys_out are required)");
-    if (n == 0) return NLSH_OK;
     const int64_t grid = (n + PR_ROWS - 1) / PR_ROWS;
     NLSH_REQUIRE(grid <= 0x7FFFFFFF, NLSH_E_UNSUPPORTED, "probe_ranked: n=%lld rows need more than 2^31 workgroups", (long long)n);
+    return NLSH_OK;
+}
+
+extern "C" int nlsh_probe_ranked(const float *z, int64_t z_stride, const uint32_t *code, int64_t n, int H, int key_mode, int n_probes,
+                                 int64_t n_multi_rows, int32_t *keys_out, int32_t *nkeys_out, float *cost_out, nlsh_stream_t stream) {
+    if (const int rc = probe_ranked_check(z, z_stride, code, n, H, key_mode, n_probes, keys_out, nkeys_out)) return rc;
+    if (n == 0) return NLSH_OK;
+    const int64_t grid = (n + PR_ROWS - 1) / PR_ROWS;
     hipLaunchKernelGGL(probe_ranked_kernel, dim3((unsigned)grid), dim3(PR_ROWS * 64), 0, (hipStream_t)stream, z, (long long)z_stride, code,
                        (long long)n, H, key_mode, n_probes, (long long)n_multi_rows, keys_out, nkeys_out, cost_out);
+    NLSH_CHECK_HIP(hipGetLastError());
+    return NLSH_OK;
+}
+
+extern "C" int nlsh_probe_ranked_budget(const float *z, int64_t z_stride, const uint32_t *code, int64_t n, int H, int key_mode,
+                                        int n_probes, int64_t n_multi_rows, const int32_t *uniq_keys, const int32_t *offsets,
+                                        int32_t n_buckets, int32_t budget, int32_t *keys_out, int32_t *nkeys_out, float *cost_out,
+                                        int32_t *ncand_out, nlsh_stream_t stream) {
+    NLSH_REQUIRE(budget >= 1, NLSH_E_INVALID, "probe_ranked_budget: budget=%d < 1", (int)budget);
+    NLSH_REQUIRE(n_buckets >= 0, NLSH_E_INVALID, "probe_ranked_budget: n_buckets=%d", (int)n_buckets);
+    NLSH_REQUIRE(n_buckets == 0 || (uniq_keys && offsets), NLSH_E_INVALID,
+                 "probe_ranked_budget: null pointer (uniq_keys and offsets are required when n_buckets=%d > 0)", (int)n_buckets);
+    if (const int rc = probe_ranked_check(z, z_stride, code, n, H, key_mode, n_probes, keys_out, nkeys_out)) return rc;
+    if (n == 0) return NLSH_OK;
+    const int64_t grid = (n + PR_ROWS - 1) / PR_ROWS;
+    hipLaunchKernelGGL(probe_ranked_budget_kernel, dim3((unsigned)grid), dim3(PR_ROWS * 64), 0, (hipStream_t)stream, z, (long long)z_stride,
+                       code, (long long)n, H, key_mode, n_probes, (long long)n_multi_rows, uniq_keys, offsets, (uint32_t)n_buckets, budget,
+                       keys_out, nkeys_out, cost_out, ncand_out);
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
 }

@@ -37,7 +37,7 @@ SYMBOLS = (
     "nlsh_step_create", "nlsh_step_create_graph", "nlsh_step_destroy", "nlsh_step_set_weights", "nlsh_query_step_enqueue", "nlsh_step_release", "nlsh_step_busy", "nlsh_query_batch",
     "nlsh_query_batch_host",
     "nlsh_exact_workspace", "nlsh_exact_topk",
-    "nlsh_probe_ranked",
+    "nlsh_probe_ranked", "nlsh_probe_ranked_budget",
 )
 
 
@@ -154,6 +154,8 @@ def lib():
     L.nlsh_exact_topk.argtypes = [vp, i64, i64, i32, vp, i64, i64, i32, i32, i64, i32, vp, vp, vp, sz, vp]
     L.nlsh_probe_ranked.restype = i32
     L.nlsh_probe_ranked.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp]
+    L.nlsh_probe_ranked_budget.restype = i32
+    L.nlsh_probe_ranked_budget.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

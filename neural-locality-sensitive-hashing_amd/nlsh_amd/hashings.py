@@ -126,6 +126,16 @@ class MultivariateBernoulli:
         _, _, probs = self._run(x, 1, want_probs=True, z_out=z, code_out=code)
         return z, probs, code
 
+    def encode_device(self, x):
+        """-> (z [B,H], code uint32-as-int32 [B]): the one-probe encode launch of the ranked mode alone (LDS-resident or streamed form),
+        for callers that probe behind it themselves (`Indexer`'s candidate budget: `nlsh_probe_ranked_budget` needs the index's CSR
+        arrays).  No seed is drawn; a BatchNorm encoder in train mode is refused as for `probes="ranked"`."""
+        B = x.shape[0]
+        z = torch.empty((B, self._hash_size), dtype=torch.float32, device=x.device)
+        code = torch.empty((B,), dtype=torch.int32, device=x.device)
+        self._run(x, 1, z_out=z, code_out=code, probes="ranked")
+        return z, code
+
     # ------------------------------------------------------------------ internals
     def linear_stack(self):
         stack = list(self._encoder.linear_stack())

@@ -14,6 +14,7 @@ last key's bucket rows (F7).  No CPU fallback exists anywhere in this module.
 import contextlib
 import ctypes
 import gc
+import numbers
 import operator
 import threading
 from typing import Dict, List, Optional, Sequence, Set, Tuple
@@ -295,7 +296,52 @@ class Indexer:
         finally:
             h.probes = old
 
-    def hash_device(self, query_vectors, batch_size=HASH_BATCH, hash_times=1, seed=None, out=None, probes=None):
+    def _candidate_budget(self, candidate_budget, probes):
+        """A call's `candidate_budget=` keyword, checked before the call does anything: an integer >= 1, the ranked mode (the call's
+        `probes=` or the hasher's attribute) and a device metric.  -> the int32 the kernel takes (a row holds fewer than 2^31
+        candidates, so anything above INT32_MAX is INT32_MAX)."""
+        mode = _capi.probe_mode(probes, getattr(self._hashing, "probes", "sampled"))
+        if isinstance(candidate_budget, bool) or not isinstance(candidate_budget, numbers.Integral):
+            raise ValueError(f"candidate_budget must be None or an integer >= 1, got {candidate_budget!r}")
+        if candidate_budget < 1:
+            raise ValueError(f"candidate_budget must be >= 1, got {candidate_budget}")
+        if mode != "ranked":
+            raise ValueError("candidate_budget needs the ranked probe mode (probes='ranked' on the call or a ranked hasher): "
+                             "sampled draws come in no order to cut")
+        if self.metric not in ("l2", "cosine"):
+            raise NotImplementedError("candidate_budget needs metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
+        return min(int(candidate_budget), 0x7FFFFFFF)
+
+    def _hash_budget(self, query_vectors, batch_size, hash_times, budget, out=None):
+        """Ranked keys cut at a candidate budget -> (keys, nkeys, ncand): the hasher's one-probe encode for z and the hard code, then
+        `nlsh_probe_ranked_budget` on this index's CSR arrays; `hash_times` is the cap."""
+        if hash_times < 1:
+            raise ValueError(f"`n` should be positive integer, but got {hash_times}")
+        if hash_times > _capi.MAX_ENCODE_PROBES:
+            raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"hash_times={hash_times} > {_capi.MAX_ENCODE_PROBES}")
+        h = self._hashing
+        q = self._as_queries(query_vectors)
+        z, code = h.encode_device(q)
+        B, H, dev = q.shape[0], z.shape[1], q.device
+        if out is not None:
+            keys, nkeys = out
+            if keys.shape != (B, hash_times) or keys.dtype != torch.int32 or nkeys.shape != (B,) or nkeys.dtype != torch.int32:
+                raise ValueError("out must be (int32 [B, n], int32 [B])")
+        else:
+            keys = torch.empty((B, hash_times), dtype=torch.int32, device=dev)
+            nkeys = torch.empty((B,), dtype=torch.int32, device=dev)
+        ncand = torch.empty((B,), dtype=torch.int32, device=dev)
+        _capi.check(_capi.lib().nlsh_probe_ranked_budget(
+            _capi.ptr(z), z.stride(0) if B else H, _capi.ptr(code), B, H, h.key_mode, hash_times, self._n_multi_rows(B, batch_size),
+            _capi.ptr(self.uniq_keys), _capi.ptr(self.offsets), self.n_buckets, budget, _capi.ptr(keys), _capi.ptr(nkeys), None,
+            _capi.ptr(ncand), _stream(dev)))
+        return keys, nkeys, ncand
+
+    def hash_device(self, query_vectors, batch_size=HASH_BATCH, hash_times=1, seed=None, out=None, probes=None, candidate_budget=None):
+        """`candidate_budget` (ranked mode only; None = off): every query stops probing after the first key that brings its candidates
+        to the budget, `hash_times` is the cap (include/nlsh_hip.h, nlsh_probe_ranked_budget)."""
+        if candidate_budget is not None:
+            return self._hash_budget(query_vectors, batch_size, hash_times, self._candidate_budget(candidate_budget, probes), out)[:2]
         if probes is None:
             return self._hash_device(query_vectors, batch_size, hash_times, seed, out)
         with self._probe_mode(probes):
@@ -326,8 +372,8 @@ class Indexer:
         return self._hashing.hash_device(query_vectors, n=hash_times,
                                          n_multi_rows=self._n_multi_rows(query_vectors.shape[0], batch_size), seed=seed, out=out)
 
-    def hash(self, query_vectors, batch_size=HASH_BATCH, hash_times=1, probes=None) -> List[Set[int]]:
-        keys, nkeys = self.hash_device(query_vectors, batch_size, hash_times, probes=probes)
+    def hash(self, query_vectors, batch_size=HASH_BATCH, hash_times=1, probes=None, candidate_budget=None) -> List[Set[int]]:
+        keys, nkeys = self.hash_device(query_vectors, batch_size, hash_times, probes=probes, candidate_budget=candidate_budget)
         return keys_to_sets(keys, nkeys, self._hashing.key_mode)
 
     # ------------------------------------------------------------------ query
@@ -581,10 +627,18 @@ class Indexer:
             keys64 = torch.where(idx < 0, torch.full_like(mono, -1), (mono << 32) | (idx.long() & 0xFFFFFFFF))
         return dist, idx, ncand, keys64
 
-    def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None, probes=None):
+    def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None, probes=None,
+                      candidate_budget=None):
         """Device-resident form of `query`: hashing + scan, nothing copied to the host.
         events = (begin, end) torch.cuda.Event pair (already recorded once) bracketing the scan kernel.
-        probes ("sampled" | "ranked", None = the hasher's `probes` attribute): the multi-probe mode of this call."""
+        probes ("sampled" | "ranked", None = the hasher's `probes` attribute): the multi-probe mode of this call.
+        candidate_budget (ranked mode only; None = off): a query probes its ranked keys until their buckets hold that many candidates,
+        `hash_times` keys at the most."""
+        if candidate_budget is not None:
+            budget = self._candidate_budget(candidate_budget, probes)
+            q = self._as_queries(query_vectors)
+            keys, nkeys, _ = self._hash_budget(q, HASH_BATCH, hash_times, budget)
+            return self.scan_tensors(q, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events)
         if probes is None:
             return self._batch_tensors(query_vectors, k, hash_times, seed, want_keys=want_keys, check=check, events=events)[:4]
         with self._probe_mode(probes):
@@ -941,10 +995,15 @@ class Indexer:
     # of two threads and the nested pause of `_plain_lists` leave the collector as the FIRST of them found it (r06).
     pause_collector_for_call = True
 
-    def query(self, query_vectors, k=10, hash_times=10, seed=None, probes=None) -> Tuple[List[List[int]], List[int]]:
+    def query(self, query_vectors, k=10, hash_times=10, seed=None, probes=None, candidate_budget=None) -> Tuple[List[List[int]], List[int]]:
         """nlsh/indexer.py:56-96.  `seed` (not in the reference): the Philox seed of the multi-probe draws; None takes the next one
         from the hasher's call counter, like every other hashing call.  `probes` (not in the reference): "sampled" | "ranked", the
-        multi-probe mode of this call; None = the hasher's `probes` attribute."""
+        multi-probe mode of this call; None = the hasher's `probes` attribute.  `candidate_budget` (not in the reference; ranked mode
+        only, None = off): a query probes its ranked keys until their buckets hold that many candidates, `hash_times` keys at the most."""
+        if candidate_budget is not None:
+            budget = self._candidate_budget(candidate_budget, probes)
+            with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
+                return self._keep(self._query(query_vectors, k, hash_times, seed, budget))
         if probes is not None:
             with self._probe_mode(probes):
                 return self.query(query_vectors, k, hash_times, seed)
@@ -953,7 +1012,7 @@ class Indexer:
         with _collector_pause:
             return self._keep(self._query(query_vectors, k, hash_times, seed))
 
-    def _query(self, query_vectors, k, hash_times, seed):
+    def _query(self, query_vectors, k, hash_times, seed, budget=None):
         if self.metric not in ("l2", "cosine"):
             return self._query_generic(query_vectors, k, hash_times)
         q = self._as_queries(query_vectors)
@@ -961,7 +1020,9 @@ class Indexer:
         if hash_times < 1:
             raise ValueError(f"`n` should be positive integer, but got {hash_times}")
         fused = None
-        if self._fuses(q, hash_times, self.choose_algo(Q, hash_times)):
+        if budget is not None:              # ranked keys cut at the candidate budget: never fused, like every ranked call
+            keys, nkeys, _ = self._hash_budget(q, HASH_BATCH, hash_times, budget)
+        elif self._fuses(q, hash_times, self.choose_algo(Q, hash_times)):
             # every row range is hashed and scanned by ONE call (five launches); the ranges share the batch's key table, seed and the
             # Philox counters of its rows, so the split changes no key
             tab = self.__dict__.setdefault("_key_tables", {})
