@@ -415,6 +415,28 @@ int nlsh_query_batch(const nlsh_step_desc_t *desc, size_t desc_bytes, const floa
  * memory mapped for the device (hipPointerGetAttributes). */
 int nlsh_query_batch_host(const nlsh_step_desc_t *desc, size_t desc_bytes, const float *queries, int64_t q_stride, uint64_t seed,
                           int64_t row0, int lookup_done, int32_t *host_out, size_t host_words, nlsh_stream_t stream);
+/* The RANKED multi-probe mode (nlsh_probe_ranked; with budget >= 1 nlsh_probe_ranked_budget's per-row stop) as one call of five launches
+ * on one stream: nlsh_encode_hash with one probe (z and the hard code go to `scratch`), ONE kernel that ranks every row's keys into
+ * desc->qkeys / desc->nkeys -- exactly the words nlsh_probe_ranked[_budget] writes for the same z and code -- and looks them up in the index
+ * (the bucket lookup of nlsh/indexer.py:68 rides in the launch that made the keys, as it does in nlsh_query_batch's encode), the two
+ * task-layout launches, the scan kernel, the merge.  Same results as nlsh_encode_hash + nlsh_probe_ranked[_budget] + nlsh_scan_topk on the
+ * same descriptor, bit for bit.
+ *   desc: as for nlsh_query_batch; n_probes in [1, NLSH_MAX_PROBES] is the width of the key table (the budget's cap),
+ *         H = desc->dims[desc->n_layers]; n_multi_rows keeps its meaning.  Ranked keys are a function of the row alone: no seed, no row0.
+ *   budget: 0 = none, >= 1 = nlsh_probe_ranked_budget's rule on desc->uniq_keys / offsets.
+ *   scratch [dev], scratch_bytes >= nlsh_query_batch_ranked_scratch(desc->Q, H): z [Q, H], the hard codes [Q] and the one-probe encode's own
+ *         key table; nothing in it is read after the call.  nlsh_query_batch_ranked_scratch is 0 for Q < 0 or H outside [1, 32].
+ *   host_out NULL: the results stay on the device (out_dist / out_idx / out_ncand, nlsh_query_batch's form).  Otherwise the host-writing
+ *         merge of nlsh_query_batch_host stores its block there, with that call's layout, host_words rule and refusals.
+ *   lookup_done != 0: repeat the scan part only, on the keys already in desc->qkeys (their lookup redone by the stand-alone kernel): the
+ *         retry after status[1] = 1, exactly as for nlsh_query_batch.
+ * Refused before anything is enqueued: what nlsh_query_batch / nlsh_query_batch_host refuse; the query-major schedule (NLSH_E_INVALID);
+ * n_buckets <= 0 (NLSH_E_INVALID); H outside [1, 32] (NLSH_E_UNSUPPORTED); budget < 0 (NLSH_E_INVALID); a NULL scratch (NLSH_E_INVALID) or
+ * one that is too small (NLSH_E_WORKSPACE).  Q == 0 is NLSH_OK without a launch. */
+size_t nlsh_query_batch_ranked_scratch(int64_t Q, int H);
+int nlsh_query_batch_ranked(const nlsh_step_desc_t *desc, size_t desc_bytes, const float *queries, int64_t q_stride, int lookup_done,
+                            int32_t budget, void *scratch, size_t scratch_bytes, int32_t *host_out, size_t host_words,
+                            void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream);
 /* 1 while the slot's last batch has not left the tail stream, 0 once it has, < 0 on error.  Never blocks. */
 int nlsh_step_busy(nlsh_step_t *step);
 

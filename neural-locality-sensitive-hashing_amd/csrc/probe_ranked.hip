@@ -26,12 +26,25 @@
 //     alone and are loaded once per row into a register; the last round (stride 1) loads the two offsets beside the key, so a lookup
 //     is ceil(log64(n_buckets)) dependent global round trips, one fewer when n_buckets > 64 (65 k buckets: 2).
 // The unbudgeted kernel is `probe_row<false>`: every budget branch is `if constexpr`, its code is what it was.
+//
+// probe_ranked_plan_kernel<BUDGET> (nlsh_query_batch_ranked, step.hip) is the same loop again (`probe_row<BUDGET, true>`) and the THIRD
+// home of the bucket lookup of the scan's PLAN phase (scan_plan.h; after bplan_kernel and encode_hash's epilogue): the row's kept keys sit
+// one per lane after the compaction, so each lane looks its key up (`plan_pair`) in the launch that ranked it and the scan call continues
+// with NLSH_PHASE_PLAN_REST -- the key table still goes out (the merge's key rows, the retry after a task-table overflow), but no kernel
+// reads it back for a per-key search.  16 rows (wavefronts) per workgroup instead of 4: the `hits` array of the workspace has an entry per
+// 16 queries (plan_blocks_max, scan_bucket.hip), and the 4-KB coarse key table is loaded once per 16 rows.  Waves past the last row skip
+// the row work and still reach both barriers.  The plan branches are `if constexpr` too: the two kernels above compile to what they were.
+// (Persistent workgroups -- two per CU, every wave walking its own rows, the coarse table loaded once per workgroup and no wave waiting
+// for its neighbours' rows -- do not fit: inside a row loop the compiler needs 90 VGPRs, or spills 36-120 bytes per lane to scratch when
+// held to the 64 that two 16-wave workgroups per CU leave; profiles/ranked_one_call.txt.)
 #include "common.h"
+#include "scan_plan.h"
 
 namespace nlsh {
 namespace {
 
 constexpr int PR_ROWS = 4;          // rows (wavefronts) per workgroup
+constexpr int PRP_ROWS = 16;        // ... of the kernel that also does the bucket lookup: one entry of `hits` per 16 queries
 constexpr uint32_t PR_NONE = 0xFFFFFFFFu;
 
 __device__ __forceinline__ uint32_t lane_read(uint32_t v, int l) {   // l is wave-uniform
@@ -74,15 +87,17 @@ __device__ __forceinline__ int32_t bucket_size(int32_t key, const int32_t *__res
     }
 }
 
-template <bool BUDGET>
+template <bool BUDGET, bool PLAN = false>
 __device__ __forceinline__ void probe_row(const float *__restrict__ z, long long z_stride, const uint32_t *__restrict__ code, long long n,
                                           int H, int key_mode, int P, long long n_multi_rows, const int32_t *__restrict__ uniq,
                                           const int32_t *__restrict__ offsets, uint32_t nb, int32_t budget,
                                           int32_t *__restrict__ keys_out, int32_t *__restrict__ nkeys_out, float *__restrict__ cost_out,
-                                          int32_t *__restrict__ ncand_out) {
+                                          int32_t *__restrict__ ncand_out, [[maybe_unused]] const PlanArgs *pa = nullptr,
+                                          [[maybe_unused]] const int32_t *coarse = nullptr, [[maybe_unused]] bool *hit_out = nullptr,
+                                          [[maybe_unused]] int *viol_out = nullptr) {
     const int lane = threadIdx.x & 63;
-    const long long row = (long long)blockIdx.x * PR_ROWS + (threadIdx.x >> 6);
-    if (row >= n) return;   // wave-uniform
+    const long long row = (long long)blockIdx.x * (PLAN ? PRP_ROWS : PR_ROWS) + (threadIdx.x >> 6);
+    if (row >= n) return;   // wave-uniform (PLAN: back to the kernel, which goes on to its barrier)
 
     // ---- costs, sorted by (bit pattern, bit index): lanes past H hold a sentinel above every cleared-sign pattern
     uint32_t c = PR_NONE;
@@ -217,7 +232,12 @@ __device__ __forceinline__ void probe_row(const float *__restrict__ z, long long
         if (t >= nk) {
             keys_out[base + t] = 0;
             if (cost_out) cost_out[base + t] = __builtin_bit_cast(float, 0x7F800000u);
+            if constexpr (PLAN) pa->ppair[base + t] = make_int4(-1, 0, 0, 0);   // a dead slot: bscatter_kernel reads all Q * P records
         }
+    }
+    if constexpr (PLAN) {
+        // P <= 64 here, so every kept key is in the first register set, one per lane: the row's lookups are issued together
+        if (first0) *hit_out = plan_pair(*pa, coarse, base + __popcll(m0 & below), key0, true, *viol_out);
     }
     if (lane == 0) nkeys_out[row] = nk;
     if constexpr (BUDGET) {
@@ -242,7 +262,66 @@ __global__ __launch_bounds__(PR_ROWS * 64) void probe_ranked_budget_kernel(const
     probe_row<true>(z, z_stride, code, n, H, key_mode, P, n_multi_rows, uniq, offsets, nb, budget, keys_out, nkeys_out, cost_out, ncand_out);
 }
 
+// Ranked keys AND their bucket lookup (see the head of this file).  What the launch leaves is what bplan_kernel leaves for the same key
+// table: a pair record per (row, slot), the cell counters incremented, tauq, the padded / pre-normalised query copy when the schedule
+// reads one (by the wave that owns the query), status / look-back slots initialised by block 0, and the block's entry of `hits`.
+template <bool BUDGET>
+__global__ __launch_bounds__(PRP_ROWS * 64) void probe_ranked_plan_kernel(const float *__restrict__ z, long long z_stride,
+                                                                          const uint32_t *__restrict__ code, int H, int key_mode,
+                                                                          long long n_multi_rows, int32_t budget, PlanArgs a,
+                                                                          int32_t *__restrict__ keys_out, int32_t *__restrict__ nkeys_out) {
+    __shared__ int32_t coarse[1024];
+    __shared__ int whits[PRP_ROWS], wviol[PRP_ROWS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < a.nco; i += PRP_ROWS * 64) coarse[i] = a.uniq[(long long)i * a.stride];
+    if (blockIdx.x == 0) plan_batch_init(a, threadIdx.x, PRP_ROWS * 64);
+    const long long row = (long long)blockIdx.x * PRP_ROWS + wave;
+    if (row < a.Q) {   // wave-uniform
+        if (lane == 0) a.tauq[row] = KEY_NONE;   // running bound of the query
+        if (a.prep_metric >= 0) prep_query(a, row, lane);
+    }
+    __syncthreads();
+    bool hit = false;
+    int viol = 0;
+    probe_row<BUDGET, true>(z, z_stride, code, a.Q, H, key_mode, a.P, n_multi_rows, a.uniq, a.offsets, (uint32_t)a.nb, budget, keys_out,
+                            nkeys_out, nullptr, nullptr, &a, coarse, &hit, &viol);
+    const unsigned long long m = __ballot(hit);
+    const unsigned long long v1 = __ballot(viol & PLAN_VIOL_COUNTER), v2 = __ballot(viol & PLAN_VIOL_CELLS);
+    if (lane == 0) {
+        whits[wave] = __popcll(m);
+        wviol[wave] = (v1 ? PLAN_VIOL_COUNTER : 0) | (v2 ? PLAN_VIOL_CELLS : 0);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int h = 0, v = 0;
+        for (int w = 0; w < PRP_ROWS; ++w) { h += whits[w]; v |= wviol[w]; }
+        a.hits[blockIdx.x] = h | v;
+    }
+}
+
 }  // namespace
+
+// the launch of nlsh_query_batch_ranked (step.hip): `pa` = the PlanArgs of the scan call the keys go to (bucket_scan_plan_args); the coarse
+// table is sized here.  *blocks_out = workgroups launched = entries of `hits` the scan call's NLSH_PHASE_PLAN_REST sums.
+int probe_ranked_plan_launch(const float *z, long long z_stride, const uint32_t *code, int H, int key_mode, long long n_multi_rows, int32_t budget,
+                             PlanArgs &pa, int32_t *keys_out, int32_t *nkeys_out, hipStream_t stream, int *blocks_out) {
+    NLSH_REQUIRE(pa.Q > 0 && pa.nb > 0 && pa.P >= 1 && pa.P <= 64 && H >= 1 && H <= NLSH_MAX_HASH_BITS && budget >= 0 && z_stride >= H,
+                 NLSH_E_INVALID, "probe_ranked + lookup: Q=%lld n_buckets=%d n_probes=%d H=%d budget=%d", pa.Q, pa.nb, pa.P, H, (int)budget);
+    NLSH_REQUIRE(z && code && keys_out && nkeys_out, NLSH_E_INVALID, "probe_ranked + lookup: null pointer");
+    const long long grid = (pa.Q + PRP_ROWS - 1) / PRP_ROWS;
+    NLSH_REQUIRE(grid <= 0x7FFFFFFF, NLSH_E_UNSUPPORTED, "probe_ranked + lookup: Q=%lld rows need more than 2^31 workgroups", pa.Q);
+    plan_coarse(pa, 1024);
+    if (budget > 0)
+        hipLaunchKernelGGL(probe_ranked_plan_kernel<true>, dim3((unsigned)grid), dim3(PRP_ROWS * 64), 0, stream, z, z_stride, code, H, key_mode,
+                           n_multi_rows, budget, pa, keys_out, nkeys_out);
+    else
+        hipLaunchKernelGGL(probe_ranked_plan_kernel<false>, dim3((unsigned)grid), dim3(PRP_ROWS * 64), 0, stream, z, z_stride, code, H, key_mode,
+                           n_multi_rows, budget, pa, keys_out, nkeys_out);
+    NLSH_CHECK_HIP(hipGetLastError());
+    *blocks_out = (int)grid;
+    return NLSH_OK;
+}
+
 }  // namespace nlsh
 
 using namespace nlsh;

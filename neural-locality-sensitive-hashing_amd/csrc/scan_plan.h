@@ -151,4 +151,9 @@ __device__ __forceinline__ bool plan_pair(const PlanArgs &a, const int32_t *coar
     return hit;
 }
 
+// The lookup's third home (probe_ranked.hip): ranked multi-probe keys made from z [Q, z_stride] and the hard codes AND looked up, in one
+// launch of 16 rows per workgroup.  budget 0 = none, >= 1 = nlsh_probe_ranked_budget's rule.  Writes the [Q, P] key table and counts.
+int probe_ranked_plan_launch(const float *z, long long z_stride, const uint32_t *code, int H, int key_mode, long long n_multi_rows, int32_t budget,
+                             PlanArgs &pa, int32_t *keys_out, int32_t *nkeys_out, hipStream_t stream, int *blocks_out);
+
 }  // namespace nlsh

@@ -349,6 +349,21 @@ extern "C" int nlsh_query_batch(const nlsh_step_desc_t *desc, size_t desc_bytes,
     return scan_call(*desc, queries, q_stride, ev_scan_begin, ev_scan_end, stream, plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, plan_blocks, nullptr);
 }
 
+// The merge's host-writing form stores through the DEVICE's address of the result block: it must be host memory the runtime has mapped
+// for the device (hipHostMalloc / hipHostRegister, a pinned tensor), from its first word to its last.
+static int host_block_mapped(const char *who, const int32_t *host_out, size_t need, int32_t **mapped) {
+    *mapped = nullptr;
+    for (const int32_t *p : {host_out, host_out + (need - 1)}) {
+        hipPointerAttribute_t at;
+        const hipError_t e = hipPointerGetAttributes(&at, p);
+        if (e != hipSuccess) (void)hipGetLastError();     // memory the runtime does not know: an answer, not a failure to keep
+        NLSH_REQUIRE(e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer != nullptr, NLSH_E_INVALID,
+                     "%s: host_out is not host memory mapped for the device (hipHostMalloc / hipHostRegister; a device pointer is refused)", who);
+        if (!*mapped) *mapped = (int32_t *)at.devicePointer;
+    }
+    return NLSH_OK;
+}
+
 // nlsh_query_batch for a caller that wants the batch's results on the HOST (`Indexer.query`): the same five launches, the last one the
 // host-writing form of the merge (scan_bucket_merge.h, bmerge_host_kernel), which stores ids, candidate counts, the status words and the
 // key rows of the queries with fewer than k candidates straight into `host_out` -- no device->host copy command follows the kernels.
@@ -373,17 +388,8 @@ extern "C" int nlsh_query_batch_host(const nlsh_step_desc_t *desc, size_t desc_b
     NLSH_REQUIRE(queries, NLSH_E_INVALID, "query_batch_host: null pointer");
     NLSH_REQUIRE(desc->n_layers >= 1 && desc->n_layers <= NLSH_MAX_LAYERS && desc->dims && desc->dims[0] == desc->d, NLSH_E_INVALID,
                  "query_batch_host: n_layers=%d, encoder input vs corpus dimension %d", desc->n_layers, desc->d);
-    // the kernel stores through the DEVICE's address of the block: it must be host memory the runtime has mapped for the device
-    // (hipHostMalloc / hipHostRegister, a pinned tensor), from its first word to its last
     int32_t *mapped = nullptr;
-    for (const int32_t *p : {(const int32_t *)host_out, (const int32_t *)host_out + (need - 1)}) {
-        hipPointerAttribute_t at;
-        const hipError_t e = hipPointerGetAttributes(&at, p);
-        if (e != hipSuccess) (void)hipGetLastError();     // memory the runtime does not know: an answer, not a failure to keep
-        NLSH_REQUIRE(e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer != nullptr, NLSH_E_INVALID,
-                     "query_batch_host: host_out is not host memory mapped for the device (hipHostMalloc / hipHostRegister; a device pointer is refused)");
-        if (!mapped) mapped = (int32_t *)at.devicePointer;
-    }
+    if (const int mrc = host_block_mapped("query_batch_host", host_out, need, &mapped)) return mrc;
     hipStream_t s = (hipStream_t)stream;
     BucketScanCall c;      // the scan call's own checks, on the host, before the encode is launched
     int rc = scan_call(*desc, queries, q_stride, nullptr, nullptr, stream, NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, 0, &c);
@@ -400,6 +406,93 @@ extern "C" int nlsh_query_batch_host(const nlsh_step_desc_t *desc, size_t desc_b
                               nullptr, nullptr, desc->qkeys, desc->nkeys);
         if (rc == NLSH_OK) rc = launch_encode(enc, *desc, queries, q_stride, seed, s, &plan_phase, &plan_blocks);
         if (rc != NLSH_OK) return rc;
+    }
+    c.phases = plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE;
+    c.plan_blocks = plan_blocks;
+    c.host_out = mapped;
+    return bucket_scan_run(c);
+}
+
+// The ranked multi-probe mode (nlsh_probe_ranked, optionally with nlsh_probe_ranked_budget's per-row stop) as ONE call of five launches:
+// encode_hash with one probe, handing out z and the hard code; probe_ranked_plan_kernel (probe_ranked.hip), which ranks a row's keys into
+// desc->qkeys / desc->nkeys AND looks them up -- the third home of the lookup of scan_plan.h --; then bscan, bscatter, the scan kernel and
+// the merge (NLSH_PHASE_PLAN_REST | SCAN | MERGE).  The two-step form it replaces made seven: the key table went out to memory and came
+// back through the stand-alone bplan_kernel.  Ranked keys are a function of the row alone: no seed, no row0.
+struct RankedScratch {
+    size_t z, code, keys, nkeys, total;
+};
+static void ranked_scratch_layout(int64_t Q, int H, RankedScratch *w) {
+    const size_t rows = (size_t)(Q > 0 ? Q : 1);
+    size_t o = 0;
+    w->z = o;     o += ws_align(rows * (size_t)H * 4);
+    w->code = o;  o += ws_align(rows * 4);
+    w->keys = o;  o += ws_align(rows * 4);    // the one-probe encode's own [Q, 1] key table and counts: required outputs of the launch,
+    w->nkeys = o; o += ws_align(rows * 4);    // read by nobody (the ranked kernel re-derives slot 0 from the hard code)
+    w->total = o;
+}
+
+extern "C" size_t nlsh_query_batch_ranked_scratch(int64_t Q, int H) {
+    if (Q < 0 || Q >= (1ll << 31) || H < 1 || H > NLSH_MAX_HASH_BITS) return 0;
+    RankedScratch w;
+    ranked_scratch_layout(Q, H, &w);
+    return w.total;
+}
+
+extern "C" int nlsh_query_batch_ranked(const nlsh_step_desc_t *desc, size_t desc_bytes, const float *queries, int64_t q_stride, int lookup_done,
+                                       int32_t budget, void *scratch, size_t scratch_bytes, int32_t *host_out, size_t host_words,
+                                       void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream) {
+    NLSH_REQUIRE(desc, NLSH_E_INVALID, "query_batch_ranked: null pointer");
+    NLSH_REQUIRE(desc_bytes == sizeof(nlsh_step_desc_t), NLSH_E_INVALID, "query_batch_ranked: descriptor of %zu bytes, this library's is %zu (ABI %d)",
+                 desc_bytes, sizeof(nlsh_step_desc_t), NLSH_ABI_VERSION);
+    NLSH_REQUIRE(desc->Q >= 0 && desc->Q < (1ll << 31), NLSH_E_INVALID, "query_batch_ranked: Q=%lld", (long long)desc->Q);
+    NLSH_REQUIRE(desc->algo == NLSH_SCAN_BUCKET_MAJOR || desc->algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_INVALID,
+                 "query_batch_ranked: algo=%d: the lookup rides in the ranking launch for the bucket-major schedules (1, 2) only", desc->algo);
+    NLSH_REQUIRE(desc->n_buckets > 0, NLSH_E_INVALID, "query_batch_ranked: n_buckets=%d (an empty index has nothing to look up)", (int)desc->n_buckets);
+    NLSH_REQUIRE(desc->n_probes >= 1 && desc->n_probes <= NLSH_MAX_PROBES, NLSH_E_UNSUPPORTED, "query_batch_ranked: n_probes=%d not in [1,%d] (one scan call per batch)",
+                 desc->n_probes, NLSH_MAX_PROBES);
+    NLSH_REQUIRE(desc->n_layers >= 1 && desc->n_layers <= NLSH_MAX_LAYERS && desc->dims && desc->dims[0] == desc->d, NLSH_E_INVALID,
+                 "query_batch_ranked: n_layers=%d, encoder input vs corpus dimension %d", desc->n_layers, desc->d);
+    const int H = desc->dims[desc->n_layers];
+    NLSH_REQUIRE(H >= 1 && H <= NLSH_MAX_HASH_BITS, NLSH_E_UNSUPPORTED, "query_batch_ranked: H=%d not in [1, NLSH_MAX_HASH_BITS=%d]", H, NLSH_MAX_HASH_BITS);
+    NLSH_REQUIRE(budget >= 0, NLSH_E_INVALID, "query_batch_ranked: budget=%d < 0 (0 = no budget)", (int)budget);
+    RankedScratch w;
+    ranked_scratch_layout(desc->Q, H, &w);
+    NLSH_REQUIRE(scratch, NLSH_E_INVALID, "query_batch_ranked: scratch is null");
+    NLSH_REQUIRE(scratch_bytes >= w.total, NLSH_E_WORKSPACE, "query_batch_ranked: scratch of %zu bytes, Q=%lld H=%d need %zu (nlsh_query_batch_ranked_scratch)",
+                 scratch_bytes, (long long)desc->Q, H, w.total);
+    size_t need = 0;
+    if (host_out) {     // the host-writing merge: nlsh_query_batch_host's form and checks
+        NLSH_REQUIRE(desc->k >= 1 && desc->k <= NLSH_MAX_K, NLSH_E_INVALID, "query_batch_ranked: k=%d not in [1,%d] (the host-writing merge; pass host_out = NULL for wider k)",
+                     desc->k, NLSH_MAX_K);
+        need = (size_t)desc->Q * (size_t)(desc->k + 1 + desc->n_probes + 1) + 2;   // ids | counts | status | key rows
+        NLSH_REQUIRE(host_words >= need, NLSH_E_INVALID, "query_batch_ranked: host_out of %zu words, Q=%lld k=%d n_probes=%d need %zu", host_words,
+                     (long long)desc->Q, desc->k, desc->n_probes, need);
+    }
+    if (desc->Q == 0) return NLSH_OK;
+    NLSH_REQUIRE(queries, NLSH_E_INVALID, "query_batch_ranked: null pointer");
+    int32_t *mapped = nullptr;
+    if (host_out)
+        if (const int mrc = host_block_mapped("query_batch_ranked", host_out, need, &mapped)) return mrc;
+    hipStream_t s = (hipStream_t)stream;
+    BucketScanCall c;      // the scan call's own checks, on the host, before anything is launched
+    int rc = scan_call(*desc, queries, q_stride, ev_scan_begin, ev_scan_end, stream, NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, 0, &c);
+    if (rc != NLSH_OK) return rc;
+    PlanArgs pa;
+    rc = bucket_scan_plan_args(c, &pa);     // workspace size
+    if (rc != NLSH_OK) return rc;
+    int plan_phase = NLSH_PHASE_PLAN, plan_blocks = 0;
+    if (!lookup_done) {
+        char *base = (char *)scratch;
+        float *z = (float *)(base + w.z);
+        uint32_t *code = (uint32_t *)(base + w.code);
+        EncPlan enc;
+        rc = encode_plan_fill(enc, desc->Q, desc->n_layers, desc->dims, desc->packed, desc->act, desc->key_mode, 1, desc->n_multi_rows, 0, z, nullptr, code,
+                              (int32_t *)(base + w.keys), (int32_t *)(base + w.nkeys));
+        if (rc == NLSH_OK) rc = encode_plan_launch(enc, queries, q_stride, 0, s);
+        if (rc == NLSH_OK)
+            rc = probe_ranked_plan_launch(z, H, code, H, desc->key_mode, desc->n_multi_rows, budget, pa, desc->qkeys, desc->nkeys, s, &plan_blocks);
+        if (rc != NLSH_OK) return rc;
+        plan_phase = NLSH_PHASE_PLAN_REST;
     }
     c.phases = plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE;
     c.plan_blocks = plan_blocks;

@@ -38,6 +38,7 @@ SYMBOLS = (
     "nlsh_query_batch_host",
     "nlsh_exact_workspace", "nlsh_exact_topk",
     "nlsh_probe_ranked", "nlsh_probe_ranked_budget",
+    "nlsh_query_batch_ranked_scratch", "nlsh_query_batch_ranked",
 )
 
 
@@ -156,6 +157,10 @@ def lib():
     L.nlsh_probe_ranked.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp]
     L.nlsh_probe_ranked_budget.restype = i32
     L.nlsh_probe_ranked_budget.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.nlsh_query_batch_ranked_scratch.restype = sz
+    L.nlsh_query_batch_ranked_scratch.argtypes = [i64, i32]
+    L.nlsh_query_batch_ranked.restype = i32     # desc, sizeof(desc), queries, q_stride, lookup_done, budget, scratch, bytes, host_out, words, scan events, stream
+    L.nlsh_query_batch_ranked.argtypes = [ctypes.POINTER(StepDesc), sz, vp, i64, i32, ctypes.c_int32, vp, sz, vp, sz, vp, vp, vp]
     _lib = L
     return L
 

@@ -7,7 +7,8 @@ device->host copy of codes.  `hash_device()` is the device-resident form `Indexe
 Encoders with a hidden layer wider than `_capi.MAX_WIDTH` (632) are "streamed": they hash through `nlsh_encode_hash_stream`
 (one GEMM launch per layer, activations in a workspace the hashing owns, then the same epilogue), up to `_capi.MAX_STREAM_WIDTH`.
 `probes="ranked"` (attribute, constructor keyword or per call) replaces the Philox draws by the n most probable codes in descending
-probability (`nlsh_probe_ranked` on the encode's own z and hard code: two launches, no seed, n distinct codes); "sampled" is the default.
+probability (`nlsh_probe_ranked` on the encode's own z and hard code: two launches, no seed, n distinct codes; `Indexer` has an opt-in
+one-call form of the whole ranked batch, `ranked_encode_args`); "sampled" is the default.
 There is no CPU fallback: a missing library or a non-device tensor raises.
 """
 import itertools
@@ -222,6 +223,19 @@ class MultivariateBernoulli:
         packed = self.packed_weights()
         return ((len(dims) - 1, self._dims_arr, packed.data_ptr(), _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID,
                  self.key_mode, n), (None, None, None, keys.data_ptr(), nkeys.data_ptr()))
+
+    def ranked_encode_args(self, n):
+        """`encode_args`' sibling for the ranked mode's one-call form (`nlsh_query_batch_ranked`): the descriptor's encoder fields
+        (n_layers, dims array, packed weights ptr, act, key_mode, n = width of the ranked key table) with the weights as they are NOW.
+        The call's encode launch makes one probe into the call's scratch, so there are no output pointers; no seed is involved.  A
+        streamed encoder has no such call: NlshHipError(E_UNSUPPORTED)."""
+        dims = self.dims()
+        if self.streamed():
+            raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"hidden width {max(dims[1:-1])} > {_capi.MAX_WIDTH}: the encoder hashes "
+                                                          "through the streamed form only (no one-call ranked batch)")
+        self._dims_arr = _capi.int_array(dims)
+        packed = self.packed_weights()
+        return (len(dims) - 1, self._dims_arr, packed.data_ptr(), _capi.ACT_TANH if self._tanh_output else _capi.ACT_SIGMOID, self.key_mode, n)
 
     def next_seed(self):
         return (self._seed + 0x9E3779B97F4A7C15 * (next(self._calls) + 1)) & 0xFFFFFFFFFFFFFFFF

@@ -637,6 +637,10 @@ class Indexer:
         if candidate_budget is not None:
             budget = self._candidate_budget(candidate_budget, probes)
             q = self._as_queries(query_vectors)
+            algo = self.choose_algo(q.shape[0], hash_times)
+            if self._fuses_ranked(q, hash_times, algo, ranked=True):
+                return self._ranked_tensors(q, k, hash_times, budget, want_keys, check, events, algo, self._n_multi_rows(q.shape[0]))[:4]
+            self.last_query_path = "two_step"
             keys, nkeys, _ = self._hash_budget(q, HASH_BATCH, hash_times, budget)
             return self.scan_tensors(q, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events)
         if probes is None:
@@ -658,6 +662,78 @@ class Indexer:
                 and self.n_buckets > 0 and q.shape[0] > 0 and not (needs_train is not None and needs_train())
                 and hasattr(self._hashing, "encode_args") and not (streamed is not None and streamed()))
 
+    # The ranked mode's one-call form (`nlsh_query_batch_ranked`: five launches, the keys looked up by the kernel that ranks them) against
+    # its two-step form (`hash_device` / `_hash_budget` + `scan_tensors`: seven launches); same results, bit for bit.  OFF by default: on
+    # the SIFT1M-shaped batch the one-call form measured slower than the two-step form in five of six comparisons (device-resident
+    # batch: +0.030 / +0.015 / +0.051 ms at hash_times 10 / 32 / budget 3000; `query()`: -0.030 / +0.061 / +0.032 ms;
+    # profiles/ranked_one_call.txt, tools/ranked_path_bench.py) -- the fused kernel takes longer than the two it replaces and the
+    # launches it saves were not idle time.  True selects it (the tests and the A/B tool do); DESIGN.md 4.7 has the analysis.
+    ranked_one_call = False
+    # which form served the last `query_tensors` / `query` call: "fused" (sampled, `nlsh_query_batch`) | "ranked_one_call" | "two_step"
+    last_query_path = None
+
+    def _fuses_ranked(self, q, hash_times, algo, ranked=None):
+        """One `nlsh_query_batch_ranked` call serves a ranked batch (`ranked`: the call said so -- a candidate budget implies the mode --;
+        None = the hasher's `probes` attribute, which a call's `probes=` sets for its duration), with or without a budget, under the
+        conditions of `_fuses`: a device metric, a key table of one scan call, a bucket-major schedule on a non-empty index, a non-empty
+        batch, an LDS-resident encoder and no BatchNorm train-mode forward.  Everything else keeps the two-step path."""
+        if not self.ranked_one_call:
+            return False
+        h = self._hashing
+        if ranked is None:
+            ranked = getattr(h, "probes", "sampled") == "ranked"
+        needs_train = getattr(h, "_needs_train_forward", None)
+        streamed = getattr(h, "streamed", None)
+        return (ranked and self.metric in ("l2", "cosine") and 1 <= hash_times <= _capi.MAX_PROBES and algo != _capi.SCAN_QUERY_MAJOR
+                and self.n_buckets > 0 and q.shape[0] > 0 and not (needs_train is not None and needs_train())
+                and hasattr(h, "ranked_encode_args") and not (streamed is not None and streamed()))
+
+    def _ranked_scratch(self, m, dev):
+        """Fresh scratch of one `nlsh_query_batch_ranked` call of m rows (z, hard codes, the one-probe encode's own key table)."""
+        need = _capi.lib().nlsh_query_batch_ranked_scratch(m, self._hashing.output_dim)
+        if need == 0:
+            _capi.check(_capi.E_UNSUPPORTED)
+        return torch.empty((need,), dtype=torch.uint8, device=dev)
+
+    def _ranked_tensors(self, q, k, P, budget, want_keys, check, events, algo, n_multi, out=None):
+        """`_batch_tensors` of the ranked mode where `_fuses_ranked` holds: one `nlsh_query_batch_ranked` call with fresh outputs
+        (`budget` None = no budget); the retry after a task-table overflow repeats the scan part on the keys the first call left."""
+        Q, d = q.shape
+        if d != self.dim:
+            raise ValueError(f"query dim {d} != corpus dim {self.dim}")
+        L, h, dev = _capi.lib(), self._hashing, q.device
+        if out is not None:
+            keys, nkeys = out
+        else:
+            keys = torch.empty((Q, P), dtype=torch.int32, device=dev)
+            nkeys = torch.empty((Q,), dtype=torch.int32, device=dev)
+        out_dist, pack, out_idx, ncand, status, out_keys = self._outputs(Q, k, dev, want_keys)
+        enc = h.ranked_encode_args(P)               # (held to the end of the call: the descriptor names its dims array)
+        scratch = self._ranked_scratch(Q, dev)
+        stream = _stream(dev)
+        lookup_done = 0
+        while True:
+            tkey, window, max_tasks = self._task_table(algo, Q, P)
+            wkey, ws = self._workspace(dev, stream, True, L.nlsh_scan_workspace(Q, P, k, max_tasks, self.n_buckets, d))
+            desc = self._step_desc(self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws,
+                                                     window), enc, n_multi)
+            try:
+                _capi.check(L.nlsh_query_batch_ranked(ctypes.byref(desc), ctypes.sizeof(desc), q.data_ptr(), q.stride(0), lookup_done, budget or 0,
+                                                      scratch.data_ptr(), scratch.numel(), None, 0,
+                                                      events[0].cuda_event if events else None, events[1].cuda_event if events else None, stream))
+            except _capi.NlshHipError:
+                self._ws.pop(wkey, None)    # a call that failed part-way may have left the counters at the head non-zero
+                raise
+            if not check:
+                break
+            needed, overflow = status.cpu().tolist()
+            if self._settle(tkey, needed, overflow, max_tasks):
+                break
+            lookup_done = 1                 # task table too small, grown: repeat the scan part on the same keys
+        self._set_last(status, algo, window, pack, tkey, max_tasks)
+        self.last_query_path = "ranked_one_call"
+        return out_dist, out_idx, ncand, out_keys, keys, nkeys
+
     def _batch_tensors(self, query_vectors, k, hash_times, seed, want_keys=False, check=True, events=None, algo=None, row0=0,
                        n_multi=None, out=None):
         """hash + scan of one batch (or one row range of a batch: `row0`, `n_multi` = rows of the RANGE that are multi-probe, `out` =
@@ -671,7 +747,11 @@ class Indexer:
             algo = self.choose_algo(Q, hash_times)
         if n_multi is None:
             n_multi = self._n_multi_rows(Q)
-        if not self._fuses(q, hash_times, algo):
+        if self._fuses_ranked(q, hash_times, algo):
+            return self._ranked_tensors(q, k, hash_times, None, want_keys, check, events, algo, n_multi, out)
+        fuses = self._fuses(q, hash_times, algo)
+        self.last_query_path = "fused" if fuses else "two_step"
+        if not fuses:
             if row0 or out is not None:
                 keys, nkeys = self._hashing.hash_device(q, n=hash_times, n_multi_rows=n_multi, seed=seed, row0=row0, out=out)
             else:
@@ -736,11 +816,13 @@ class Indexer:
     # weight walk, argument tuples) was 0.08 ms per range = 0.2 ms of a 1.1-ms call (tools/query_host_profile.py).  `query_tensors`
     # hands its tensors to the caller and keeps allocating fresh ones.  Like the scan workspace (one per stream), the kept buffers
     # assume one `query()` at a time per indexer and stream.
-    def _range_plan(self, q, keys, nkeys, k, lo, hi, algo, n_multi, host=None):
+    def _range_plan(self, q, keys, nkeys, k, lo, hi, algo, n_multi, host=None, ranked=False):
+        """`ranked`: the plan of an `nlsh_query_batch_ranked` call -- the hasher's `ranked_encode_args` in the descriptor and the call's
+        scratch kept beside the other buffers."""
         Q_all, P = keys.shape
         dev, m = q.device, hi - lo
         stream = _stream(dev)
-        ckey = (stream, Q_all, lo, hi, P, k, algo, self.l2_form, keys.data_ptr(), q.shape[1])
+        ckey = (stream, Q_all, lo, hi, P, k, algo, self.l2_form, keys.data_ptr(), q.shape[1], ranked)
         plans = self.__dict__.setdefault("_range_plans", {})
         plan = plans.get(ckey)
         tkey, window, max_tasks = self._task_table(algo, m, P)
@@ -760,12 +842,15 @@ class Indexer:
         wkey, ws = self._workspace(dev, stream, True, _capi.lib().nlsh_scan_workspace(m, P, k, max_tasks, self.n_buckets, d))
         rk, rn = keys[lo:hi], nkeys[lo:hi]
         out_dist, pack, out_idx, ncand, status, _ = self._outputs(m, k, dev)
-        enc, _ = self._hashing.encode_args(P, rk, rn)
+        enc = self._hashing.ranked_encode_args(P) if ranked else self._hashing.encode_args(P, rk, rn)[0]
+        scratch = self._ranked_scratch(m, dev) if ranked else None
         desc = self._step_desc(self._scan_fields(m, d, rk, rn, k, algo, max_tasks, out_dist, out_idx, None, ncand, status, ws, window),
                                enc, min(max(n_multi - lo, 0), m))
         plan = plans[ckey] = dict(desc=desc, ref=ctypes.byref(desc), size=ctypes.sizeof(desc), dims_arr=enc[1], packed=self._hashing.packed_weights(), sig=sig,
                                   keys=rk, nkeys=rn, out_dist=out_dist, pack=pack, status=status, ws=ws, wkey=wkey, max_tasks=max_tasks, tkey=tkey,
-                                  window=window, stream=stream, host_ptr=host_ptr, host_words=0 if host is None else host.numel())
+                                  window=window, stream=stream, host_ptr=host_ptr, host_words=0 if host is None else host.numel(),
+                                  scratch=scratch, scratch_ptr=None if scratch is None else scratch.data_ptr(),
+                                  scratch_bytes=0 if scratch is None else scratch.numel())
         if len(plans) > 64:           # batch shapes come and go (a caller sweeping Q): keep the dictionary bounded
             for old_key in list(plans)[:-32]:
                 del plans[old_key]
@@ -779,8 +864,9 @@ class Indexer:
 
     def _range_tensors(self, q, keys, nkeys, k, lo, hi, algo, fused, host=None):
         """One row range of a `query()` batch on the stream: `fused` = (hash_times, seed, rows of the batch that are multi-probe) --
-        the range is hashed AND scanned by one `nlsh_query_batch` call into its slice of the batch's key table; None: the table was
-        filled by a whole-batch `hash_device` and the range is only scanned.  `host` (`_host_form`): the range's slice of the pinned
+        the range is hashed AND scanned by one `nlsh_query_batch` call into its slice of the batch's key table; ("ranked", budget or 0,
+        multi-probe rows): the same with one `nlsh_query_batch_ranked` call (no seed, no row offset: ranked keys are a function of the
+        row alone); None: the table was filled by a whole-batch `hash_device` and the range is only scanned.  `host` (`_host_form`): the range's slice of the pinned
         result block -- the call is `nlsh_query_batch_host`, whose merge kernel stores ids | counts | status | the short queries' key rows
         there, and nothing has to be copied afterwards."""
         if fused is None:
@@ -789,11 +875,15 @@ class Indexer:
             else:
                 self.scan_tensors(q[lo:hi], keys[lo:hi], nkeys[lo:hi], k=k, check=False, algo=algo)
             return
-        _, seed, n_multi = fused
-        plan = self._range_plan(q, keys, nkeys, k, lo, hi, algo, n_multi, host)
+        mode, seed, n_multi = fused
+        ranked = mode == "ranked"
+        plan = self._range_plan(q, keys, nkeys, k, lo, hi, algo, n_multi, host, ranked)
         qr = q[lo:hi]
         try:
-            if host is not None:
+            if ranked:          # `seed` holds the budget (0 = none); host_ptr None = the results stay on the device (wide k)
+                _capi.check(_capi.lib().nlsh_query_batch_ranked(plan["ref"], plan["size"], qr.data_ptr(), qr.stride(0), 0, seed, plan["scratch_ptr"],
+                                                                plan["scratch_bytes"], plan["host_ptr"], plan["host_words"], None, None, plan["stream"]))
+            elif host is not None:
                 _capi.check(_capi.lib().nlsh_query_batch_host(plan["ref"], plan["size"], qr.data_ptr(), qr.stride(0), seed, lo, 0, plan["host_ptr"],
                                                               plan["host_words"], plan["stream"]))
             else:
@@ -1013,6 +1103,7 @@ class Indexer:
             return self._keep(self._query(query_vectors, k, hash_times, seed))
 
     def _query(self, query_vectors, k, hash_times, seed, budget=None):
+        self.last_query_path = "two_step"
         if self.metric not in ("l2", "cosine"):
             return self._query_generic(query_vectors, k, hash_times)
         q = self._as_queries(query_vectors)
@@ -1020,9 +1111,22 @@ class Indexer:
         if hash_times < 1:
             raise ValueError(f"`n` should be positive integer, but got {hash_times}")
         fused = None
-        if budget is not None:              # ranked keys cut at the candidate budget: never fused, like every ranked call
+        if self._fuses_ranked(q, hash_times, self.choose_algo(Q, hash_times), ranked=True if budget is not None else None):
+            # every row range is ranked, looked up and scanned by ONE call (five launches) into its rows of the batch's key table, which is
+            # kept per (stream, batch shape): two streams never share one
+            tab = self.__dict__.setdefault("_ranked_key_tables", {})
+            tkey_ = (_stream(q.device), q.device, Q, hash_times)
+            if tkey_ not in tab:
+                if len(tab) > 8:
+                    tab.clear()
+                tab[tkey_] = (torch.empty((Q, hash_times), dtype=torch.int32, device=q.device), torch.empty((Q,), dtype=torch.int32, device=q.device))
+            keys, nkeys = tab[tkey_]
+            fused = ("ranked", budget or 0, self._n_multi_rows(Q))
+            self.last_query_path = "ranked_one_call"
+        elif budget is not None:            # ranked keys cut at the candidate budget, two steps
             keys, nkeys, _ = self._hash_budget(q, HASH_BATCH, hash_times, budget)
         elif self._fuses(q, hash_times, self.choose_algo(Q, hash_times)):
+            self.last_query_path = "fused"
             # every row range is hashed and scanned by ONE call (five launches); the ranges share the batch's key table, seed and the
             # Philox counters of its rows, so the split changes no key
             tab = self.__dict__.setdefault("_key_tables", {})
