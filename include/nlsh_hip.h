@@ -241,6 +241,35 @@ int nlsh_gather_rows(const float *corpus, int64_t src_stride, int d, const int32
                      float *sorted, int64_t dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
                      nlsh_stream_t stream);
 
+/* Index update: add rows to and remove rows from a built index without rebuilding it.  No reference counterpart (the reference's index
+ * is a dict built once, nlsh/indexer.py:6-24).  The result is, word for word, the index nlsh_build_csr + nlsh_gather_rows build from
+ * the kept rows in their order followed by the new rows in theirs: out of place, into caller-allocated arrays of n_kept + m_new rows.
+ *   old index [dev]: corpus_sorted [n_old, row_stride] (16-byte aligned, row_stride % 4 == 0), gid [n_old], inv_norm [n_old] (nullable:
+ *     needed when inv_norm_out is given), uniq_keys [n_buckets_old], offsets [n_buckets_old + 1] -- all in sorted order, as built;
+ *   keep [dev] uint8 [n_old] (nullable = every row kept), non-zero = the row at that SORTED position stays; n_kept = how many are set
+ *     (a wrong count never writes or reads out of bounds, it gives a wrong index);
+ *   new rows [dev]: rows_new fp32 [m_new, d] with row stride new_stride >= d (any alignment), keys_new int32 [m_new] their bucket keys,
+ *     ids_new int32 [m_new] their global row ids, all in the caller's order;
+ *   outputs [dev]: sorted_out [n_kept + m_new, stride_out] (16-byte aligned, stride_out % 4 == 0, >= d; columns >= d written as zero),
+ *     gid_out, inv_norm_out (nullable: kept rows' values copied, new rows' computed as nlsh_gather_rows computes them, the same bits),
+ *     src_out int32 [n_kept + m_new]: where each row came from -- the old sorted position, or ~j for new row j --, uniq_out
+ *     [n_kept + m_new] (first *n_buckets_out valid), offsets_out [n_kept + m_new + 1] (first *n_buckets_out + 1 valid), n_buckets_out [1].
+ * Placement (signed key order, as in the build): kept old rows keep their order and stand in front of the new rows of their own key;
+ * new rows of one key keep the caller's order.  n_kept + m_new <= 2^31 - 1.
+ * Every argument is checked on the host before anything is launched and before any pointer is read: a refusal -- a short workspace
+ * included -- is NLSH_E_INVALID with the argument's name in nlsh_last_error().  nlsh_csr_update_workspace is arithmetic on its
+ * arguments (0 = invalid: a negative count, a count >= 2^31, n_buckets_old > n_old), no device needed; it bounds what rocPRIM's sort
+ * of the m_new keys and its scans ask for, and nlsh_csr_update returns NLSH_E_WORKSPACE before launching anything if a device's
+ * rocPRIM ever asked for more. */
+size_t nlsh_csr_update_workspace(int64_t n_old, int64_t n_buckets_old, int64_t m_new);
+int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
+                    const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                    const uint8_t *keep, int64_t n_kept,
+                    const float *rows_new, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new, int64_t m_new,
+                    float *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                    int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out,
+                    void *workspace, size_t workspace_bytes, nlsh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Candidate scan + top-k.  Replaces the per-query loop of Indexer.query (nlsh/indexer.py:62-95):
  * bucket lookup (:68), gather (:77-82), distance (:84-87, nlsh/data.py:99-109,191-201),

@@ -5,6 +5,8 @@
 // nlsh/indexer.py:77-82.  The stable LSD radix sort of (key, row) pairs is rocPRIM's (a native
 // ROCm primitive; this step is SURVEY.md §8(f) row N1, outside the graded scan/encode kernels);
 // bucket heads, offsets and the row permutation/gather are hand-written.
+// Index update (nlsh_csr_update, no reference counterpart): new rows merged into and removed rows dropped from a built index in one
+// out-of-place pass, with the build's own bucket-table kernels and row helpers.
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -39,7 +41,48 @@ __global__ void emit_buckets_kernel(const int32_t *sk, const int32_t *flags, con
     }
 }
 
-// One group of LPR lanes per destination row; 16-byte loads when the source allows it.
+// float4 number c of a d-float row at `s`, columns >= d read as zero.  VEC: `s` is 16-byte aligned (one 16-byte load where the whole
+// float4 lies inside the row).
+template <bool VEC>
+__device__ __forceinline__ float4 load_row_chunk(const float *s, int c, int d) {
+    float4 v;
+    if (VEC) {
+        v = (c * 4 + 3 < d) ? *reinterpret_cast<const float4 *>(s + c * 4) : make_float4(0, 0, 0, 0);
+        if (!(c * 4 + 3 < d)) {
+            v.x = c * 4 + 0 < d ? s[c * 4 + 0] : 0.0f;
+            v.y = c * 4 + 1 < d ? s[c * 4 + 1] : 0.0f;
+            v.z = c * 4 + 2 < d ? s[c * 4 + 2] : 0.0f;
+            v.w = 0.0f;
+        }
+    } else {
+        v.x = c * 4 + 0 < d ? s[c * 4 + 0] : 0.0f;
+        v.y = c * 4 + 1 < d ? s[c * 4 + 1] : 0.0f;
+        v.z = c * 4 + 2 < d ? s[c * 4 + 2] : 0.0f;
+        v.w = c * 4 + 3 < d ? s[c * 4 + 3] : 0.0f;
+    }
+    return v;
+}
+
+// A row's sum of squares, the part of one lane: lane l of the row's lane group chains the float4s l, l + 64, l + 128, ... in that order.
+__device__ __forceinline__ float sumsq_chain(float4 v, float ss) {
+    ss = fmaf(v.x, v.x, ss); ss = fmaf(v.y, v.y, ss); ss = fmaf(v.z, v.z, ss); ss = fmaf(v.w, v.w, ss);
+    return ss;
+}
+
+// ... and the sum over the row's `lanes` lanes (a power of two, an aligned group of the wavefront): the xor butterfly from lanes / 2
+// down.  A row of at most `lanes` float4s summed over 64 lanes gives the same bits: the lanes past the row hold +0, a sum of squares
+// is never -0, so every butterfly step of 64 lanes above lanes / 2 adds +0 to it.  EVERY lane of the wavefront must call this.
+__device__ __forceinline__ float sumsq_lanes(float ss, int lanes) {
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float other = __shfl_xor(ss, m);
+        ss += m < lanes ? other : 0.0f;
+    }
+    return ss;
+}
+
+__device__ __forceinline__ float inv_norm_of(float ss) { return 1.0f / fmaxf(sqrtf(ss), 1e-8f); }  // cosine_similarity eps (nlsh/data.py:109)
+
+// One wavefront per destination row; 16-byte loads when the source allows it.
 template <bool VEC>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float *corpus, long long src_stride, int d, const int32_t *perm,
                                                            long long n, float *sorted, long long dst_stride, float *inv_norm,
@@ -54,27 +97,13 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float *corpus, l
         float4 *dst = reinterpret_cast<float4 *>(sorted + i * dst_stride);
         float ss = 0.0f;
         for (int c = lane; c < d4; c += 64) {
-            float4 v;
-            if (VEC) {
-                v = (c * 4 + 3 < d) ? *reinterpret_cast<const float4 *>(s + c * 4) : make_float4(0, 0, 0, 0);
-                if (!(c * 4 + 3 < d)) {
-                    v.x = c * 4 + 0 < d ? s[c * 4 + 0] : 0.0f;
-                    v.y = c * 4 + 1 < d ? s[c * 4 + 1] : 0.0f;
-                    v.z = c * 4 + 2 < d ? s[c * 4 + 2] : 0.0f;
-                    v.w = 0.0f;
-                }
-            } else {
-                v.x = c * 4 + 0 < d ? s[c * 4 + 0] : 0.0f;
-                v.y = c * 4 + 1 < d ? s[c * 4 + 1] : 0.0f;
-                v.z = c * 4 + 2 < d ? s[c * 4 + 2] : 0.0f;
-                v.w = c * 4 + 3 < d ? s[c * 4 + 3] : 0.0f;
-            }
+            const float4 v = load_row_chunk<VEC>(s, c, d);
             dst[c] = v;
-            ss = fmaf(v.x, v.x, ss); ss = fmaf(v.y, v.y, ss); ss = fmaf(v.z, v.z, ss); ss = fmaf(v.w, v.w, ss);
+            ss = sumsq_chain(v, ss);
         }
         if (inv_norm) {
-            for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m);
-            if (lane == 0) inv_norm[i] = 1.0f / fmaxf(sqrtf(ss), 1e-8f);  // cosine_similarity eps (nlsh/data.py:109)
+            ss = sumsq_lanes(ss, 64);
+            if (lane == 0) inv_norm[i] = inv_norm_of(ss);
         }
         if (gid && lane == 0) gid[i] = (int32_t)src + id_base;
     }
@@ -190,6 +219,208 @@ static int csr_layout(long long n, CsrWs *w, hipStream_t s) {
     return NLSH_OK;
 }
 
+// keys[n] (n >= 1) -> perm, uniq_keys, offsets, n_buckets with caller-placed scratch: sk, iota, flags, rank int32 [n] each, tmp for rocPRIM.
+static int build_csr_on(const int32_t *keys, long long n, int32_t *perm, int32_t *uniq_keys, int32_t *offsets, int32_t *n_buckets,
+                        int32_t *sk, int32_t *iota, int32_t *flags, int32_t *rank, void *tmp, size_t tmp_bytes, hipStream_t s) {
+    int grid = (int)((n + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(iota_kernel, dim3(grid), dim3(256), 0, s, iota, n);
+    size_t tb = tmp_bytes;
+    // stable: equal keys keep ascending row order (the insertion order of indexer.py:8-13)
+    NLSH_CHECK_HIP(rocprim::radix_sort_pairs(tmp, tb, keys, sk, iota, perm, (size_t)n, 0, 32, s));
+    hipLaunchKernelGGL(head_flags_kernel, dim3(grid), dim3(256), 0, s, sk, n, flags);
+    tb = tmp_bytes;
+    NLSH_CHECK_HIP(rocprim::inclusive_scan(tmp, tb, flags, rank, (size_t)n, rocprim::plus<int32_t>(), s));
+    hipLaunchKernelGGL(emit_buckets_kernel, dim3(grid), dim3(256), 0, s, sk, flags, rank, n, uniq_keys, offsets, n_buckets);
+    NLSH_CHECK_HIP(hipGetLastError());
+    return NLSH_OK;
+}
+
+// ---- index update: merge a sorted batch of new rows into the CSR index, drop removed rows (include/nlsh_hip.h, nlsh_csr_update) -------
+// Positions are int32 throughout (n_old, n_out < 2^31).  `kex` = exclusive prefix sum of `keep` with kex[n_old] = rows kept; NULL = every
+// old row is kept (kex[i] = i).
+
+__device__ __forceinline__ int kept_before(const int32_t *kex, int i) { return kex ? kex[i] : i; }
+
+// first index in [0, n) with a[index] >= v (lower) / > v (upper), signed order
+__device__ __forceinline__ int lower_bound_i32(const int32_t *a, int n, int32_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ int upper_bound_i32(const int32_t *a, int n, int32_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a[mid] <= v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Once per bucket of either side, the distance its rows move:
+//   shift_old[b] = new rows with a key below uniq_old[b]            (a kept old row i of bucket b lands at kex[i] + shift_old[b])
+//   shift_new[c] = kept old rows with a key up to uniq_new[c]       (the new row at new-sorted position t of bucket c lands at t + shift_new[c])
+__global__ void update_shifts_kernel(const int32_t *uniq_old, const int32_t *offs_old, int nb_old, int n_old, const int32_t *kex,
+                                     const int32_t *uniq_new, const int32_t *offs_new, const int32_t *nb_new_p, int m_new,
+                                     int32_t *shift_old, int32_t *shift_new) {
+    const int nb_new = m_new ? *nb_new_p : 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (long long)nb_old + nb_new; i += (long long)gridDim.x * blockDim.x) {
+        if (i < nb_old) {
+            const int b = (int)i;
+            shift_old[b] = m_new ? offs_new[lower_bound_i32(uniq_new, nb_new, uniq_old[b])] : 0;
+        } else {
+            const int c = (int)(i - nb_old);
+            const int rows = n_old ? offs_old[upper_bound_i32(uniq_old, nb_old, uniq_new[c])] : 0;
+            shift_new[c] = kept_before(kex, rows);
+        }
+    }
+}
+
+// Index pass: one thread per old row and per new row -> src, gid and key at its destination.  A destination outside [0, n_out) (only a
+// caller whose n_kept is not the number of set `keep` bytes produces one) is not written.
+__global__ void update_index_kernel(const int32_t *gid_old, const int32_t *uniq_old, const int32_t *offs_old, int nb_old, int n_old,
+                                    const uint8_t *keep, const int32_t *kex, const int32_t *shift_old,
+                                    const int32_t *perm_new, const int32_t *uniq_new, const int32_t *offs_new, const int32_t *nb_new_p,
+                                    const int32_t *ids_new, const int32_t *shift_new, int m_new, long long n_out,
+                                    int32_t *src_out, int32_t *gid_out, int32_t *key_out) {
+    const int nb_new = m_new ? *nb_new_p : 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (long long)n_old + m_new; i += (long long)gridDim.x * blockDim.x) {
+        long long dst;
+        int32_t src, id, key;
+        if (i < n_old) {
+            if (keep && !keep[i]) continue;
+            const int b = min(max(upper_bound_i32(offs_old, nb_old + 1, (int32_t)i) - 1, 0), nb_old - 1);     // offs_old[b] <= i < offs_old[b + 1]
+            dst = (long long)kept_before(kex, (int)i) + shift_old[b];
+            src = (int32_t)i;
+            id = gid_old[i];
+            key = uniq_old[b];
+        } else {
+            const int t = (int)(i - n_old);
+            const int c = min(max(upper_bound_i32(offs_new, nb_new + 1, t) - 1, 0), nb_new - 1);
+            const int j = perm_new[t];
+            dst = (long long)t + shift_new[c];
+            src = ~j;
+            id = ids_new[j];
+            key = uniq_new[c];
+        }
+        if (dst >= 0 && dst < n_out) {
+            src_out[dst] = src;
+            gid_out[dst] = id;
+            key_out[dst] = key;
+        }
+    }
+}
+
+// Row pass, output-driven: destination row p takes old sorted row src[p] (its inv_norm copied) or new row ~src[p] (zero-padded, its
+// inv_norm computed as gather_rows_kernel computes it).  A row has 2^lg lanes, the smallest power of two that covers its float4s (64
+// and the lane loop from 65 float4s on), so one wave-instruction moves 64 >> lg whole rows with 16 bytes per lane, and ROWS_IN_FLIGHT
+// instructions' loads are issued before the first store.  Destination rows of one instruction are consecutive: the stores are one
+// contiguous run, the old sources runs of a bucket's kept rows.
+constexpr int ROWS_IN_FLIGHT = 4;
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void update_rows_kernel(const float *sorted_old, long long stride_old, const float *inv_old, long long n_old,
+                                                           const float *rows_new, long long stride_new, long long m_new, int d,
+                                                           const int32_t *src, long long n_out, float *sorted_out, long long stride_out,
+                                                           float *inv_out, int lg) {
+    const int lane = threadIdx.x & 63;
+    const int lanes = 1 << lg, g = lane & (lanes - 1), rows_per_inst = 64 >> lg;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const int d4 = (int)(stride_out >> 2);
+    const long long step = (long long)rows_per_inst * ROWS_IN_FLIGHT;
+    for (long long base = wave * step; base < n_out; base += nwaves * step) {      // wave-uniform: every lane reaches the butterfly
+        const float *s[ROWS_IN_FLIGHT];
+        long long p[ROWS_IN_FLIGHT];
+        int32_t from[ROWS_IN_FLIGHT];
+        float ss[ROWS_IN_FLIGHT];
+#pragma unroll
+        for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
+            p[r] = base + (long long)r * rows_per_inst + (lane >> lg);
+            from[r] = p[r] < n_out ? src[p[r]] : 0;
+            // a source outside either side (a slot the index pass never wrote: see there) reads as an all-zero row
+            const bool is_old = from[r] >= 0;
+            const long long j = is_old ? (long long)from[r] : (long long)~from[r];
+            const bool ok = p[r] < n_out && j < (is_old ? n_old : m_new);
+            s[r] = !ok ? nullptr : is_old ? sorted_old + j * stride_old : rows_new + j * stride_new;
+            ss[r] = 0.0f;
+        }
+        for (int c = g; c < d4; c += 64) {
+            float4 v[ROWS_IN_FLIGHT];
+#pragma unroll
+            for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
+                if (!s[r]) v[r] = make_float4(0, 0, 0, 0);
+                else if (from[r] >= 0) v[r] = load_row_chunk<true>(s[r], c, d);
+                else v[r] = load_row_chunk<VEC>(s[r], c, d);
+            }
+#pragma unroll
+            for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
+                if (p[r] < n_out) reinterpret_cast<float4 *>(sorted_out + p[r] * stride_out)[c] = v[r];
+                ss[r] = sumsq_chain(v[r], ss[r]);
+            }
+        }
+        if (inv_out) {
+#pragma unroll
+            for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
+                const float total = sumsq_lanes(ss[r], lanes);
+                if (g == 0 && p[r] < n_out) inv_out[p[r]] = (from[r] >= 0 && s[r]) ? inv_old[from[r]] : inv_norm_of(total);
+            }
+        }
+    }
+}
+
+__global__ void keep_flags_kernel(const uint8_t *keep, long long n, int32_t *flags) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        flags[i] = keep[i] ? 1 : 0;
+}
+
+// The scratch rocPRIM asks for is only known on a device (its size queries read the device's properties); the workspace size must be
+// a pure function of the row counts (callers size buffers without one), so the region is BOUNDED here and nlsh_csr_update checks
+// the real queries against the bound before it launches anything.  Radix sort of n (key, value) pairs: a second copy of both arrays,
+// digit histograms and one look-back word per digit and block; scans: one look-back word per block.
+static size_t sort_tmp_bound(size_t n) { return align_up(24 * n + (256u << 10)); }
+static size_t scan_tmp_bound(size_t n) { return align_up(n / 4 + (64u << 10)); }
+
+struct UpdateWs {
+    size_t kex, shift_old, key_out, flags, rank;                             // old side and output: n_old + 1, nb_old, 3 x n_out
+    size_t perm_n, uniq_n, offs_n, nb_n, shift_new, sk, iota, flags_n, rank_n;   // new side: the CSR of the m_new keys and its scratch
+    size_t tmp, tmp_bytes, total;
+};
+
+static bool update_args_ok(long long n_old, long long nb_old, long long m_new) {
+    return n_old >= 0 && n_old < (1ll << 31) && m_new >= 0 && m_new < (1ll << 31) && nb_old >= 0 && nb_old <= n_old;
+}
+
+static void update_layout(long long n_old, long long nb_old, long long m_new, UpdateWs *w) {
+    long long n_out = n_old + m_new;         // rows written when nothing is removed
+    if (n_out > 0x7FFFFFFFll) n_out = 0x7FFFFFFFll;
+    const size_t a_old = align_up((size_t)(n_old + 1) * 4), a_nb = align_up((size_t)(nb_old + 1) * 4);
+    const size_t a_out = align_up((size_t)(n_out + 1) * 4), a_new = align_up((size_t)(m_new + 1) * 4);
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t here = at; at += bytes; return here; };
+    w->kex = take(a_old);
+    w->shift_old = take(a_nb);
+    w->key_out = take(a_out);
+    w->flags = take(a_out);
+    w->rank = take(a_out);
+    w->perm_n = take(a_new);
+    w->uniq_n = take(a_new);
+    w->offs_n = take(a_new);
+    w->nb_n = take(256);
+    w->shift_new = take(a_new);
+    w->sk = take(a_new);
+    w->iota = take(a_new);
+    w->flags_n = take(a_new);
+    w->rank_n = take(a_new);
+    const size_t t_sort = sort_tmp_bound((size_t)m_new), t_scan = scan_tmp_bound((size_t)(n_out > n_old ? n_out : n_old));
+    w->tmp = at;
+    w->tmp_bytes = t_sort > t_scan ? t_sort : t_scan;
+    w->total = w->tmp + w->tmp_bytes;
+}
+
 }  // namespace nlsh
 
 using namespace nlsh;
@@ -220,19 +451,7 @@ extern "C" int nlsh_build_csr(const int32_t *keys, int64_t n, int32_t *perm, int
     char *base = (char *)workspace;
     int32_t *sk = (int32_t *)(base + w.sk), *iota = (int32_t *)(base + w.iota);
     int32_t *flags = (int32_t *)(base + w.flags), *rank = (int32_t *)(base + w.rank);
-    void *tmp = base + w.tmp;
-    int grid = (int)((n + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(iota_kernel, dim3(grid), dim3(256), 0, s, iota, (long long)n);
-    size_t tb = w.tmp_bytes;
-    // stable: equal keys keep ascending row order (the insertion order of indexer.py:8-13)
-    NLSH_CHECK_HIP(rocprim::radix_sort_pairs(tmp, tb, keys, sk, iota, perm, (size_t)n, 0, 32, s));
-    hipLaunchKernelGGL(head_flags_kernel, dim3(grid), dim3(256), 0, s, sk, (long long)n, flags);
-    tb = w.tmp_bytes;
-    NLSH_CHECK_HIP(rocprim::inclusive_scan(tmp, tb, flags, rank, (size_t)n, rocprim::plus<int32_t>(), s));
-    hipLaunchKernelGGL(emit_buckets_kernel, dim3(grid), dim3(256), 0, s, sk, flags, rank, (long long)n, uniq_keys, offsets, n_buckets);
-    NLSH_CHECK_HIP(hipGetLastError());
-    return NLSH_OK;
+    return build_csr_on(keys, (long long)n, perm, uniq_keys, offsets, n_buckets, sk, iota, flags, rank, base + w.tmp, w.tmp_bytes, s);
 }
 
 extern "C" size_t nlsh_bucket_order_workspace(int64_t n_buckets) {
@@ -344,6 +563,118 @@ extern "C" int nlsh_gather_rows(const float *corpus, int64_t src_stride, int d, 
     else
         hipLaunchKernelGGL(gather_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, corpus, (long long)src_stride, d, perm,
                            (long long)n, sorted, (long long)dst_stride, inv_norm, gid, id_base);
+    NLSH_CHECK_HIP(hipGetLastError());
+    return NLSH_OK;
+}
+
+extern "C" size_t nlsh_csr_update_workspace(int64_t n_old, int64_t n_buckets_old, int64_t m_new) {
+    if (!update_args_ok(n_old, n_buckets_old, m_new)) {
+        set_error("csr_update_workspace: n_old=%lld n_buckets_old=%lld m_new=%lld", (long long)n_old, (long long)n_buckets_old, (long long)m_new);
+        return 0;
+    }
+    UpdateWs w;
+    update_layout(n_old, n_buckets_old, m_new, &w);
+    return w.total;
+}
+
+extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
+                               const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                               const uint8_t *keep, int64_t n_kept,
+                               const float *rows_new, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new, int64_t m_new,
+                               float *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                               int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out,
+                               void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+    // ---- host checks: nothing below them runs, and no pointer is read, unless all of them pass
+    NLSH_REQUIRE(d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "csr_update: d=%d not in [1, NLSH_MAX_DIM = %d]", d, NLSH_MAX_DIM);
+    NLSH_REQUIRE(n_old >= 0 && n_old < (1ll << 31), NLSH_E_INVALID, "csr_update: n_old=%lld not in [0, 2^31)", (long long)n_old);
+    NLSH_REQUIRE(n_buckets_old >= 0 && n_buckets_old <= n_old, NLSH_E_INVALID, "csr_update: n_buckets_old=%lld not in [0, n_old=%lld]",
+                 (long long)n_buckets_old, (long long)n_old);
+    NLSH_REQUIRE(m_new >= 0 && m_new < (1ll << 31), NLSH_E_INVALID, "csr_update: m_new=%lld not in [0, 2^31)", (long long)m_new);
+    NLSH_REQUIRE(n_kept >= 0 && n_kept <= n_old, NLSH_E_INVALID, "csr_update: n_kept=%lld not in [0, n_old=%lld]", (long long)n_kept, (long long)n_old);
+    NLSH_REQUIRE(keep || n_kept == n_old, NLSH_E_INVALID, "csr_update: keep is null (every row kept) but n_kept=%lld != n_old=%lld",
+                 (long long)n_kept, (long long)n_old);
+    const long long n_out = (long long)n_kept + (long long)m_new;
+    NLSH_REQUIRE(n_out <= 0x7FFFFFFFll, NLSH_E_INVALID, "csr_update: n_kept + m_new = %lld rows > 2^31 - 1 (int32 row positions)", n_out);
+    NLSH_REQUIRE(offsets_out && n_buckets_out, NLSH_E_INVALID, "csr_update: offsets_out / n_buckets_out is null");
+    if (n_old) {
+        NLSH_REQUIRE(row_stride >= d && (row_stride & 3) == 0, NLSH_E_INVALID, "csr_update: row_stride=%lld must be >= d=%d and a multiple of 4",
+                     (long long)row_stride, d);
+        NLSH_REQUIRE(corpus_sorted && gid && uniq_keys && offsets, NLSH_E_INVALID, "csr_update: corpus_sorted / gid / uniq_keys / offsets is null with n_old=%lld",
+                     (long long)n_old);
+        NLSH_REQUIRE(((uintptr_t)corpus_sorted & 15) == 0, NLSH_E_INVALID, "csr_update: corpus_sorted must be 16-byte aligned");
+        NLSH_REQUIRE(n_buckets_old >= 1, NLSH_E_INVALID, "csr_update: n_buckets_old=0 with n_old=%lld rows", (long long)n_old);
+    }
+    if (m_new) {
+        NLSH_REQUIRE(new_stride >= d, NLSH_E_INVALID, "csr_update: new_stride=%lld < d=%d", (long long)new_stride, d);
+        NLSH_REQUIRE(rows_new && keys_new && ids_new, NLSH_E_INVALID, "csr_update: rows_new / keys_new / ids_new is null with m_new=%lld", (long long)m_new);
+    }
+    UpdateWs w;
+    update_layout(n_old, n_buckets_old, m_new, &w);
+    if (n_out) {
+        NLSH_REQUIRE(stride_out >= d && (stride_out & 3) == 0, NLSH_E_INVALID, "csr_update: stride_out=%lld must be >= d=%d and a multiple of 4",
+                     (long long)stride_out, d);
+        NLSH_REQUIRE(sorted_out && gid_out && src_out && uniq_out, NLSH_E_INVALID, "csr_update: sorted_out / gid_out / src_out / uniq_out is null");
+        NLSH_REQUIRE(((uintptr_t)sorted_out & 15) == 0, NLSH_E_INVALID, "csr_update: sorted_out must be 16-byte aligned");
+        NLSH_REQUIRE(!inv_norm_out || inv_norm || n_kept == 0, NLSH_E_INVALID, "csr_update: inv_norm_out is wanted but inv_norm (the kept rows') is null");
+        NLSH_REQUIRE(workspace, NLSH_E_INVALID, "csr_update: workspace is null");
+        NLSH_REQUIRE(((uintptr_t)workspace & 15) == 0, NLSH_E_INVALID, "csr_update: the workspace must be 16-byte aligned");
+        NLSH_REQUIRE(workspace_bytes >= w.total, NLSH_E_INVALID, "csr_update: workspace_bytes=%zu < nlsh_csr_update_workspace = %zu", workspace_bytes, w.total);
+    }
+    // ---- device work
+    hipStream_t s = (hipStream_t)stream;
+    if (n_out == 0) {
+        NLSH_CHECK_HIP(hipMemsetAsync(offsets_out, 0, sizeof(int32_t), s));
+        NLSH_CHECK_HIP(hipMemsetAsync(n_buckets_out, 0, sizeof(int32_t), s));
+        return NLSH_OK;
+    }
+    char *base = (char *)workspace;
+    int32_t *kex = keep ? (int32_t *)(base + w.kex) : nullptr, *shift_old = (int32_t *)(base + w.shift_old);
+    int32_t *key_out = (int32_t *)(base + w.key_out), *flags = (int32_t *)(base + w.flags), *rank = (int32_t *)(base + w.rank);
+    int32_t *perm_n = (int32_t *)(base + w.perm_n), *uniq_n = (int32_t *)(base + w.uniq_n), *offs_n = (int32_t *)(base + w.offs_n);
+    int32_t *nb_n = (int32_t *)(base + w.nb_n), *shift_new = (int32_t *)(base + w.shift_new);
+    void *tmp = base + w.tmp;
+    int32_t *nul = nullptr;
+    const size_t n_scan = (size_t)(n_out > n_old ? n_out : n_old);
+    size_t t_sort = 0, t_scan = 0;      // what rocPRIM really asks for on this device, against the bound the workspace was sized by
+    if (m_new) NLSH_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, t_sort, nul, nul, nul, nul, (size_t)m_new, 0, 32, s));
+    NLSH_CHECK_HIP(rocprim::inclusive_scan(nullptr, t_scan, nul, nul, n_scan, rocprim::plus<int32_t>(), s));
+    NLSH_REQUIRE(t_sort <= w.tmp_bytes && t_scan <= w.tmp_bytes, NLSH_E_WORKSPACE, "csr_update: rocPRIM scratch (sort %zu, scan %zu bytes) exceeds the %zu bytes "
+                 "the workspace formula reserves for it", t_sort, t_scan, w.tmp_bytes);
+    auto grid_of = [](long long n) { long long g = (n + 255) / 256; return dim3((unsigned)(g < 1 ? 1 : g > 2048 ? 2048 : g)); };
+    if (m_new) {
+        int rc = build_csr_on(keys_new, (long long)m_new, perm_n, uniq_n, offs_n, nb_n, (int32_t *)(base + w.sk), (int32_t *)(base + w.iota),
+                              (int32_t *)(base + w.flags_n), (int32_t *)(base + w.rank_n), tmp, w.tmp_bytes, s);
+        if (rc != NLSH_OK) return rc;
+    }
+    if (keep) {         // kex[0] = 0, kex[i + 1] = keep[0] + ... + keep[i]
+        hipLaunchKernelGGL(keep_flags_kernel, grid_of(n_old), dim3(256), 0, s, keep, (long long)n_old, flags);
+        NLSH_CHECK_HIP(hipMemsetAsync(kex, 0, sizeof(int32_t), s));
+        size_t tb = w.tmp_bytes;
+        NLSH_CHECK_HIP(rocprim::inclusive_scan(tmp, tb, flags, kex + 1, (size_t)n_old, rocprim::plus<int32_t>(), s));
+    }
+    hipLaunchKernelGGL(update_shifts_kernel, grid_of(n_buckets_old + m_new), dim3(256), 0, s, uniq_keys, offsets, (int)n_buckets_old, (int)n_old, kex,
+                       uniq_n, offs_n, nb_n, (int)m_new, shift_old, shift_new);
+    hipLaunchKernelGGL(update_index_kernel, grid_of(n_old + m_new), dim3(256), 0, s, gid, uniq_keys, offsets, (int)n_buckets_old, (int)n_old, keep, kex,
+                       shift_old, perm_n, uniq_n, offs_n, nb_n, ids_new, shift_new, (int)m_new, n_out, src_out, gid_out, key_out);
+    // the bucket table of the result: the run-length encoding of the keys at their destinations (emptied buckets vanish, new ones appear)
+    hipLaunchKernelGGL(head_flags_kernel, grid_of(n_out), dim3(256), 0, s, key_out, n_out, flags);
+    size_t tb = w.tmp_bytes;
+    NLSH_CHECK_HIP(rocprim::inclusive_scan(tmp, tb, flags, rank, (size_t)n_out, rocprim::plus<int32_t>(), s));
+    hipLaunchKernelGGL(emit_buckets_kernel, grid_of(n_out), dim3(256), 0, s, key_out, flags, rank, n_out, uniq_out, offsets_out, n_buckets_out);
+    // the rows
+    const int d4 = (int)(stride_out >> 2);
+    int lg = 0;
+    while ((1 << lg) < d4 && lg < 6) ++lg;
+    const long long rows_per_wave = (long long)(64 >> lg) * ROWS_IN_FLIGHT;
+    long long blocks = ((n_out + rows_per_wave - 1) / rows_per_wave + 3) / 4;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    const bool vec = ((new_stride & 3) == 0) && (((uintptr_t)rows_new & 15) == 0);
+    if (vec)
+        hipLaunchKernelGGL(update_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, corpus_sorted, (long long)row_stride, inv_norm, (long long)n_old,
+                           rows_new, (long long)new_stride, (long long)m_new, d, src_out, n_out, sorted_out, (long long)stride_out, inv_norm_out, lg);
+    else
+        hipLaunchKernelGGL(update_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, corpus_sorted, (long long)row_stride, inv_norm, (long long)n_old,
+                           rows_new, (long long)new_stride, (long long)m_new, d, src_out, n_out, sorted_out, (long long)stride_out, inv_norm_out, lg);
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
 }

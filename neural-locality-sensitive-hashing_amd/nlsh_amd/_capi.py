@@ -39,6 +39,7 @@ SYMBOLS = (
     "nlsh_exact_workspace", "nlsh_exact_topk",
     "nlsh_probe_ranked", "nlsh_probe_ranked_budget",
     "nlsh_query_batch_ranked_scratch", "nlsh_query_batch_ranked",
+    "nlsh_csr_update_workspace", "nlsh_csr_update",
 )
 
 
@@ -121,6 +122,11 @@ def lib():
     L.nlsh_build_cells.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, sz, vp]
     L.nlsh_gather_rows.restype = i32
     L.nlsh_gather_rows.argtypes = [vp, i64, i32, vp, i64, vp, i64, vp, vp, ctypes.c_int32, vp]
+    L.nlsh_csr_update_workspace.restype = sz
+    L.nlsh_csr_update_workspace.argtypes = [i64, i64, i64]
+    L.nlsh_csr_update.restype = i32     # old index (9) | keep, n_kept | new rows (5) | outputs (8) | workspace, bytes, stream
+    L.nlsh_csr_update.argtypes = [vp, i64, i32, vp, vp, vp, vp, i64, i64,  vp, i64,  vp, i64, vp, vp, i64,
+                                  vp, i64, vp, vp, vp, vp, vp, vp,  vp, sz, vp]
     L.nlsh_scan_workspace.restype = sz
     L.nlsh_scan_workspace.argtypes = [i64, i32, i32, i64, i64, i32]
     L.nlsh_scan_workspace_layout.restype = i32

@@ -210,7 +210,10 @@ class Indexer:
         self._pin = None            # pinned host staging of query()'s single device->host copy
         self._ws = {}               # scan workspace per stream (concurrent query batches on different HIP streams)
         self._max_tasks = {}
+        self.generation = 0         # +1 per effective `update` / `add` / `remove`: what was built on the arrays of an older one is stale
         self._build_index()
+        # the id `add` gives its first row when the caller names none: only ever grows, so a removed row's id is never handed out again
+        self.next_id = self.id_base + int(self.gid.shape[0])
 
     # ------------------------------------------------------------------ build
     def _build_index(self):
@@ -245,6 +248,11 @@ class Indexer:
             if self.row_ids.shape[0] != N or self.row_ids.dtype != torch.int32:
                 raise ValueError("row_ids must be int32 [N]")
             self.gid = self.row_ids[self.perm.long()].contiguous()
+        self._refresh_bucket_tables()
+
+    def _refresh_bucket_tables(self):
+        """What follows from `offsets` / `uniq_keys` alone: the schedule order of the buckets and the host copies of the CSR arrays."""
+        L, dev = _capi.lib(), self.offsets.device
         # schedule order of the buckets (largest first) for the bucket-major scans: static per index
         self.bucket_order = torch.empty((max(self.n_buckets, 1),), dtype=torch.int32, device=dev)
         if self.n_buckets:
@@ -257,6 +265,166 @@ class Indexer:
         self._uniq_host = self.uniq_keys.cpu().numpy()
         self._offs_host = self.offsets.cpu().numpy().astype(np.int64)
         self.bucket_sizes = np.diff(self._offs_host)
+
+    # ------------------------------------------------------------------ mutation
+    # After any sequence of these calls every array of the index equals, word for word, what the constructor builds from the index's
+    # rows in local order -- the constructor's corpus, then every added batch, minus the removed rows -- with `row_ids=` their ids and
+    # `corpus_keys=` their keys.  One pass over the sorted corpus (`nlsh_csr_update`), no sort of the old keys.
+    def add(self, vectors, ids=None, keys=None) -> torch.Tensor:
+        """Add float32 rows [M, d] (device; strided row views allowed) -> their int32 ids (device).  `ids` (int32 [M], new and distinct)
+        default to `next_id ..`; an index built with `row_ids=` has no default.  `keys` (int32 [M]) default to the hasher's keys,
+        as `corpus_keys=` does in the constructor."""
+        return self.update(add=vectors, add_ids=ids, add_keys=keys)[0]
+
+    def remove(self, ids) -> int:
+        """Remove the rows with these ids (int tensor or sequence) -> how many rows went.  Unknown ids are ignored, duplicates count once."""
+        return self.update(remove=ids)[1]
+
+    def update(self, add=None, add_ids=None, add_keys=None, remove=None) -> Tuple[torch.Tensor, int]:
+        """`remove` and `add` in ONE pass over the corpus -> (ids of the added rows, number of rows removed).  Removal applies to the
+        rows the index held before the call.  A build-path call: it runs on the current stream after the device has drained, and
+        synchronises.  Out of place: the new sorted corpus is written beside the old one, which is released afterwards (peak memory:
+        twice the sorted corpus).  Everything built on the old arrays -- plans, workspaces, cells, a `QueryPipeline` -- is stale
+        afterwards (`generation`)."""
+        if self.metric not in ("l2", "cosine"):
+            raise NotImplementedError("update / add / remove need metric 'l2' or 'cosine': the generic-metric query reads the caller's "
+                                      "corpus, which a mutated index no longer mirrors")
+        dev, N = self.corpus_sorted.device, int(self.gid.shape[0])
+        vectors, new_ids, new_keys = self._new_rows(add, add_ids, add_keys, dev)
+        M = 0 if vectors is None else int(vectors.shape[0])
+        keep, n_kept = None, N
+        if remove is not None:
+            rem = torch.as_tensor(remove, device=dev).reshape(-1)
+            if rem.numel() and (rem.dtype.is_floating_point or rem.dtype.is_complex or rem.dtype == torch.bool):
+                raise ValueError("remove must hold integer ids")
+            if rem.numel() and N:
+                # ~isin(gid, remove) in sorted order -- as a binary search of every gid in the SORTED removal list: `torch.isin` sorts
+                # both sides, and the 10^6 gids of a SIFT1M-sized index cost it 0.4 ms per call (profiles/index_update.txt)
+                rem = torch.sort(rem.long()).values
+                gid64 = self.gid.long()
+                keep = rem[torch.searchsorted(rem, gid64).clamp_(max=rem.numel() - 1)] != gid64
+                n_kept = int(keep.sum().item())
+                if n_kept == N:
+                    keep = None
+        if M == 0 and keep is None:
+            return torch.empty((0,), dtype=torch.int32, device=dev), 0
+        n_out = n_kept + M
+        if n_out > 0x7FFFFFFF:
+            raise ValueError(f"{n_out} rows: the index addresses its rows with int32")
+        torch.cuda.synchronize(dev)         # batches in flight (other streams, pipelines) still read the arrays about to be released
+        L, stride = _capi.lib(), self.row_stride
+        sorted_out = torch.empty((n_out, stride), dtype=torch.float32, device=dev)
+        gid_out = torch.empty((n_out,), dtype=torch.int32, device=dev)
+        inv_out = torch.empty((n_out,), dtype=torch.float32, device=dev) if self.metric == "cosine" else None
+        src_out = torch.empty((n_out,), dtype=torch.int32, device=dev)
+        nb_cap = max(n_out, 1)
+        uniq_out = torch.empty((nb_cap,), dtype=torch.int32, device=dev)
+        offs_out = torch.empty((nb_cap + 1,), dtype=torch.int32, device=dev)
+        nb_out = torch.zeros((1,), dtype=torch.int32, device=dev)
+        ws_bytes = L.nlsh_csr_update_workspace(N, self.n_buckets, M)
+        if ws_bytes == 0:
+            _capi.check(_capi.E_INVALID)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        keep_u8 = None if keep is None else keep.to(torch.uint8)
+        _capi.check(L.nlsh_csr_update(
+            _capi.ptr(self.corpus_sorted), stride, self.dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
+            _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
+            _capi.ptr(vectors), vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
+            _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
+            _capi.ptr(nb_out), _capi.ptr(ws), ws_bytes, _stream(dev)))
+        n_buckets = int(nb_out.item())
+        # the int32 side arrays in LOCAL order, from where every sorted row came from (`src_out`): torch plumbing, 4 bytes per row
+        src = src_out.long()
+        if N:
+            local = self.perm.long()
+            keep_local = None
+            if keep is not None:
+                keep_local = torch.empty((N,), dtype=torch.bool, device=dev)
+                keep_local[local] = keep
+                local = (torch.cumsum(keep_local, 0) - 1)[local]        # new local row of the old row at each old sorted position
+            perm = torch.where(src >= 0, local[src.clamp(min=0)], n_kept + ~src)
+            old_keys = self.corpus_keys if keep_local is None else self.corpus_keys[keep_local]
+            old_ids = None if self.row_ids is None else (self.row_ids if keep_local is None else self.row_ids[keep_local])
+        else:
+            perm, old_keys = ~src, self.corpus_keys
+            old_ids = None if self.row_ids is None else self.row_ids
+        self.perm = perm.to(torch.int32)
+        self.corpus_keys = torch.cat([old_keys, new_keys]) if M else old_keys.contiguous()
+        if self.row_ids is not None:
+            self.row_ids = torch.cat([old_ids, new_ids]) if M else old_ids.contiguous()
+        self.corpus_sorted, self.gid, self.inv_norm = sorted_out, gid_out, inv_out
+        self.uniq_keys, self.offsets, self.n_buckets = uniq_out[:n_buckets], offs_out[:n_buckets + 1], n_buckets
+        self._refresh_bucket_tables()
+        if M:
+            self.next_id = max(self.next_id, int(new_ids.max().item()) + 1)
+        self._drop_derived()
+        self._candidate_vectors_gpu = None      # the index owns its rows now
+        self.generation += 1
+        return (new_ids if M else torch.empty((0,), dtype=torch.int32, device=dev)), N - n_kept
+
+    def _new_rows(self, add, add_ids, add_keys, dev):
+        """`update`'s new rows, checked before anything changes -> (vectors fp32 [M, d] unit column stride, ids int32 [M], keys int32 [M]),
+        all None for no rows."""
+        if add is None:
+            if add_ids is not None or add_keys is not None:
+                raise ValueError("add_ids / add_keys without rows to add")
+            return None, None, None
+        if not isinstance(add, torch.Tensor) or add.device.type != "cuda":
+            raise _capi.NlshHipError(_capi.E_INVALID, "added rows must be a device-resident tensor; there is no CPU path")
+        if add.device != dev:
+            raise ValueError(f"added rows are on {add.device}, the index on {dev}")
+        if add.dim() != 2 or add.shape[1] != self.dim:
+            raise ValueError(f"added rows must be [M, {self.dim}], got {tuple(add.shape)}")
+        if add.dtype != torch.float32:
+            raise ValueError(f"added rows must be float32, got {add.dtype}")
+        M = int(add.shape[0])
+        if M == 0:
+            return None, None, None
+        vectors = add if add.stride(1) == 1 else add.contiguous()
+        if add_keys is not None:
+            keys = add_keys
+            if not isinstance(keys, torch.Tensor) or keys.shape != (M,) or keys.dtype != torch.int32 or keys.device != dev:
+                raise ValueError("keys must be int32 [M] on the index's device")
+            keys = keys.contiguous()
+        else:
+            needs_train = getattr(self._hashing, "_needs_train_forward", None)
+            if needs_train is not None and needs_train():
+                raise _capi.NlshHipError(_capi.E_UNSUPPORTED, "add() needs eval mode for BatchNorm encoders (train_mode(False)): batch statistics "
+                                                              "would make a row's key depend on the batch it arrived in; or pass keys=")
+            keys = self.hash_device(vectors, hash_times=1)[0].reshape(-1).contiguous()    # the call `_build_index` makes
+        if add_ids is None:
+            if self.row_ids is not None:
+                raise ValueError("an index built with row_ids= has no default ids: pass ids=")
+            if self.next_id + M - 1 > 0x7FFFFFFF:
+                raise ValueError("row ids are int32: next_id + M exceeds 2^31 - 1")
+            ids = torch.arange(self.next_id, self.next_id + M, dtype=torch.int32, device=dev)
+        else:
+            ids = torch.as_tensor(add_ids, device=dev)
+            if ids.shape != (M,) or ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+                raise ValueError("ids must be M integers")
+            if ids.dtype != torch.int32:
+                if int(ids.min().item()) < -(1 << 31) or int(ids.max().item()) > 0x7FFFFFFF:
+                    raise ValueError("row ids are int32")
+                ids = ids.to(torch.int32)
+            ids = ids.contiguous()
+            if int(torch.unique(ids).numel()) != M:
+                raise ValueError("ids must be distinct")
+            if bool(torch.isin(ids, self.gid).any().item()):
+                raise ValueError("ids must be new: some are in the index already")
+        return vectors, ids, keys
+
+    def _drop_derived(self):
+        """Everything derived from the index arrays of the previous generation.  The kept range plans hold raw pointers (a new tensor
+        can land on an old address, so an equal `data_ptr` proves nothing) and the bucket-major PLAN phase keeps one counter per
+        bucket at the head of each workspace -- `n_buckets` has changed."""
+        self._cells = {}
+        self._index2row = None
+        self._perm_host = None
+        self._e_sb = None
+        self._ws = {}
+        self._max_tasks = {}
+        for name in ("_range_plans", "_ranked_key_tables", "_key_tables", "_held", "_bucket_dir"):
+            self.__dict__.pop(name, None)
 
     @property
     def index2row(self) -> Dict[int, torch.Tensor]:

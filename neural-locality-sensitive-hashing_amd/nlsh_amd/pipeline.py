@@ -69,6 +69,8 @@ class QueryPipeline:
         if depth < 2:
             raise ValueError("depth must be >= 2 (3 keeps all three stages busy)")
         self.indexer, self.k, self.P, self.exchange = indexer, k, hash_times, exchange
+        # the slots' descriptors name the index arrays of THIS generation by address (`Indexer.update` releases them)
+        self.generation = getattr(indexer, "generation", 0)
         q = sample_queries
         if q.dtype != torch.float32 or q.stride(1) != 1:
             raise ValueError("pipelined batches must be float32 row-major device tensors")
@@ -200,6 +202,10 @@ class QueryPipeline:
         if queries.shape != (self.Q, self.d) or queries.dtype != torch.float32 or queries.stride(1) != 1:
             raise ValueError("batch shape/dtype differs from the pipeline's sample batch")
         ix, L = self.indexer, self._lib
+        if getattr(ix, "generation", 0) != self.generation:
+            raise _capi.NlshHipError(_capi.E_INVALID, f"the pipeline was built on generation {self.generation} of the index, which is at "
+                                                      f"generation {ix.generation} now (update / add / remove released the arrays its slots "
+                                                      "name): build a new QueryPipeline")
         if ix._hashing._needs_train_forward():
             # the pipeline launches the fused kernel on folded eval-mode weights; a BatchNorm encoder in train mode needs the module's
             # own batch-statistics forward (hashings._run_train_mode), which `Indexer.query` / `hash_device` route to
