@@ -52,6 +52,13 @@ enum { NLSH_METRIC_L2_EPS = 0, NLSH_METRIC_COSINE = 1, NLSH_METRIC_L2_EPS_FOLDED
  * one workgroup per (bucket segment, <= 16 queries) with the row tile staged through LDS.  0 and 1 give
  * bit-identical results; 2 sums each distance in k order (bit-identical to the oracle), ids agree except fp32 near-ties. */
 enum { NLSH_SCAN_QUERY_MAJOR = 0, NLSH_SCAN_BUCKET_MAJOR = 1, NLSH_SCAN_BUCKET_TILED = 2 };
+/* Element type of a bucket-sorted corpus copy (the *_typed entry points; every other call takes float32).  No reference counterpart.
+ * float16 -> float32 and uint8 -> float32 are exact, so a typed index IS the float32 index over its dequantised rows: every output
+ * word of the typed calls equals what the float32 calls give on those rows.  A row's pitch is a multiple of 16 bytes in every storage
+ * (4 / 8 / 16 elements), the base 16-byte aligned, columns >= d stored as zero. */
+#define NLSH_STORE_F32 0
+#define NLSH_STORE_F16 1
+#define NLSH_STORE_U8 2
 
 #define NLSH_MAX_LAYERS 8   /* Linear layers incl. the output layer */
 #define NLSH_MAX_HASH_BITS 32
@@ -241,6 +248,18 @@ int nlsh_gather_rows(const float *corpus, int64_t src_stride, int d, const int32
                      float *sorted, int64_t dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
                      nlsh_stream_t stream);
 
+/* nlsh_gather_rows between storages: corpus [dev] holds src_storage elements (row stride src_stride elements, any alignment), sorted
+ * [dev, 16-byte aligned] receives dst_storage elements, dst_stride (elements) >= d with dst_stride * element size a multiple of 16.
+ * float32 -> float16 rounds to nearest even; a value goes to uint8 only if it is integral and in [0, 255].  A source value that does
+ * not survive the conversion -- a finite value that float16 turns into an infinity, anything else than an integer in [0, 255] for
+ * uint8 -- is reported, not clamped: first_bad [dev] int32 [1] (nullable when src_storage == dst_storage) receives the smallest SOURCE
+ * row (perm value) holding one, -1 for none; what `sorted` holds then is unspecified.  inv_norm is computed from the dequantised values
+ * in nlsh_gather_rows' operation order: the bits nlsh_gather_rows gives on the dequantised rows.  Everything is checked on the host
+ * before anything is launched (NLSH_E_INVALID with the argument's name). */
+int nlsh_gather_rows_typed(const void *corpus, int src_storage, int64_t src_stride, int d, const int32_t *perm, int64_t n,
+                           void *sorted, int dst_storage, int64_t dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
+                           int32_t *first_bad, nlsh_stream_t stream);
+
 /* Index update: add rows to and remove rows from a built index without rebuilding it.  No reference counterpart (the reference's index
  * is a dict built once, nlsh/indexer.py:6-24).  The result is, word for word, the index nlsh_build_csr + nlsh_gather_rows build from
  * the kept rows in their order followed by the new rows in theirs: out of place, into caller-allocated arrays of n_kept + m_new rows.
@@ -269,6 +288,22 @@ int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, int d, const
                     float *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
                     int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out,
                     void *workspace, size_t workspace_bytes, nlsh_stream_t stream);
+
+/* nlsh_csr_update on an index whose sorted corpus holds `storage` elements (corpus_sorted and sorted_out; row_stride and stride_out in
+ * elements, each pitch a multiple of 16 bytes), with new rows of new_storage elements (new_stride elements, any alignment).  Kept
+ * rows are moved as bytes; new rows are converted on the way in by nlsh_gather_rows_typed's rule and reported the same way: first_bad
+ * [dev] int32 [1] (nullable when new_storage == storage) receives the smallest new row j that does not survive the conversion, -1 for
+ * none -- the outputs are then not an index and the caller drops them (the old index is untouched: the update is out of place).  New
+ * rows' inv_norm as nlsh_gather_rows_typed computes it.  NLSH_STORE_F32 / NLSH_STORE_F32 is nlsh_csr_update.  The workspace is
+ * nlsh_csr_update_workspace's (it holds int32 side arrays only).  Host checks as nlsh_csr_update. */
+int nlsh_csr_update_typed(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
+                          const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                          const uint8_t *keep, int64_t n_kept,
+                          const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new,
+                          int64_t m_new,
+                          void *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                          int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad,
+                          void *workspace, size_t workspace_bytes, nlsh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Candidate scan + top-k.  Replaces the per-query loop of Indexer.query (nlsh/indexer.py:62-95):
@@ -354,6 +389,22 @@ int nlsh_scan_topk_cells_phase(const float *corpus_sorted, int64_t row_stride, i
                                float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand,
                                int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
                                void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases);
+
+/* nlsh_scan_topk_cells_phase on a corpus copy of `storage` elements (NLSH_STORE_*): corpus_sorted [dev, 16-byte aligned] [N, row_stride]
+ * with row_stride in ELEMENTS, >= d, its pitch in bytes a multiple of 16, columns >= d zero (nlsh_gather_rows_typed writes such a copy).
+ * NLSH_STORE_F32 is nlsh_scan_topk_cells_phase, argument for argument.  NLSH_STORE_F16 and NLSH_STORE_U8 exist in the tiled schedule
+ * only: algo NLSH_SCAN_BUCKET_TILED, every metric, k <= NLSH_MAX_K_TILED; the other two schedules answer NLSH_E_UNSUPPORTED with the
+ * reason in nlsh_last_error().  The rows are widened to float32 as they are staged (exact conversions) and scored by the float32
+ * code: every output equals, bit for bit, what nlsh_scan_topk_cells_phase gives on the dequantised corpus.  Queries are float32.
+ * The step, batch and graph entry points below take float32 indexes only. */
+int nlsh_scan_topk_cells_phase_typed(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
+                                     const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                                     const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                                     const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
+                                     const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows,
+                                     float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand,
+                                     int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
+                                     void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases);
 
 /* ---------------------------------------------------------------------------------------------
  * One pipelined query batch per call.  Replaces, for a caller that streams batches, the whole body of Indexer.query

@@ -372,6 +372,218 @@ __global__ __launch_bounds__(256) void update_rows_kernel(const float *sorted_ol
     }
 }
 
+// ---- typed storage (NLSH_STORE_*): rows of float32 / float16 / uint8 elements in, rows of any of the three out -------------------------
+// The unit is the 4-element chunk of the float32 kernels above -- one float4 of the dequantised row, 16 / 8 / 4 bytes stored -- dealt to
+// the lanes as there (chunk c to lane c % 64, or to lane c of the row's lane group), so a row's sum of squares is the same fmaf chain and
+// the same butterfly over the same values: inv_norm has the bits the float32 kernels give on the dequantised rows.  A wider pitch only
+// appends chunks of zeros to a lane's chain (fmaf(0, 0, ss) == ss: a sum of squares is never -0).
+template <int STORE> struct StoreElem;
+template <> struct StoreElem<NLSH_STORE_F32> { typedef float elem; typedef float4 word; };
+template <> struct StoreElem<NLSH_STORE_F16> { typedef _Float16 elem; typedef uint2 word; };
+template <> struct StoreElem<NLSH_STORE_U8> { typedef uint8_t elem; typedef uint32_t word; };
+
+static int store_per16(int storage) { return storage == NLSH_STORE_F32 ? 4 : storage == NLSH_STORE_F16 ? 8 : 16; }   // elements per 16 bytes
+// rows of `storage` elements at `base` with this stride: does every row start on a 4-element chunk boundary (16 / 8 / 4 bytes)?
+static int store_vec_ok(const void *base, int storage, long long stride) {
+    const uintptr_t chunk = storage == NLSH_STORE_F32 ? 16 : storage == NLSH_STORE_F16 ? 8 : 4;
+    return ((stride & 3) == 0 && ((uintptr_t)base & (chunk - 1)) == 0) ? 1 : 0;
+}
+static bool store_ok(int storage) { return storage == NLSH_STORE_F32 || storage == NLSH_STORE_F16 || storage == NLSH_STORE_U8; }
+
+// a stored chunk, dequantised (exact)
+template <int DST> __device__ __forceinline__ float4 unpack_chunk(typename StoreElem<DST>::word w);
+template <> __device__ __forceinline__ float4 unpack_chunk<NLSH_STORE_F32>(float4 w) { return w; }
+template <> __device__ __forceinline__ float4 unpack_chunk<NLSH_STORE_F16>(uint2 w) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const h2 lo = __builtin_bit_cast(h2, w.x), hi = __builtin_bit_cast(h2, w.y);
+    return make_float4((float)lo.x, (float)lo.y, (float)hi.x, (float)hi.y);
+}
+template <> __device__ __forceinline__ float4 unpack_chunk<NLSH_STORE_U8>(uint32_t w) {
+    return make_float4((float)(w & 0xFFu), (float)((w >> 8) & 0xFFu), (float)((w >> 16) & 0xFFu), (float)(w >> 24));
+}
+
+// chunk c of a d-element row at `s` as float32 (exact), columns >= d zero.  `vec` (wave-uniform, decided on the host): the row starts on
+// a chunk boundary of its own storage (16 / 8 / 4 bytes) and its stride is whole chunks, so a chunk that lies inside the row is ONE load
+// of its stored word -- what gather_rows_kernel<true> does for float32; otherwise element loads, any alignment of the source.
+template <int SRC>
+__device__ __forceinline__ float4 load_chunk_as_f32(const void *row, int c, int d, bool vec) {
+    const typename StoreElem<SRC>::elem *s = static_cast<const typename StoreElem<SRC>::elem *>(row);
+    if (vec && c * 4 + 3 < d) return unpack_chunk<SRC>(*reinterpret_cast<const typename StoreElem<SRC>::word *>(s + c * 4));
+    float4 v;
+    v.x = c * 4 + 0 < d ? (float)s[c * 4 + 0] : 0.0f;
+    v.y = c * 4 + 1 < d ? (float)s[c * 4 + 1] : 0.0f;
+    v.z = c * 4 + 2 < d ? (float)s[c * 4 + 2] : 0.0f;
+    v.w = c * 4 + 3 < d ? (float)s[c * 4 + 3] : 0.0f;
+    return v;
+}
+
+// One value as storage DST holds it, dequantised again; `bad` is set when the value does not survive: float16 -- round to nearest even,
+// a FINITE value that becomes an infinity is refused (infinities and NaNs pass as themselves); uint8 -- integers in [0, 255] only.
+template <int DST>
+__device__ __forceinline__ float requantise(float x, bool &bad) {
+    if (DST == NLSH_STORE_F16) {
+        const float y = (float)(_Float16)x;
+        bad = bad || (__builtin_isinf(y) && !__builtin_isinf(x));
+        return y;
+    }
+    if (DST == NLSH_STORE_U8) {
+        const bool ok = x >= 0.0f && x <= 255.0f && x == truncf(x);   // a NaN fails the comparisons
+        bad = bad || !ok;
+        return ok ? fabsf(x) : 0.0f;                                  // -0 is stored as 0
+    }
+    return x;
+}
+template <int DST>
+__device__ __forceinline__ float4 requantise4(float4 v, bool &bad) {
+    return make_float4(requantise<DST>(v.x, bad), requantise<DST>(v.y, bad), requantise<DST>(v.z, bad), requantise<DST>(v.w, bad));
+}
+
+// a chunk of representable values as its stored word
+template <int DST> __device__ __forceinline__ typename StoreElem<DST>::word pack_chunk(float4 v);
+template <> __device__ __forceinline__ float4 pack_chunk<NLSH_STORE_F32>(float4 v) { return v; }
+template <> __device__ __forceinline__ uint2 pack_chunk<NLSH_STORE_F16>(float4 v) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    h2 lo, hi;
+    lo.x = (_Float16)v.x; lo.y = (_Float16)v.y; hi.x = (_Float16)v.z; hi.y = (_Float16)v.w;
+    return make_uint2(__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi));
+}
+template <> __device__ __forceinline__ uint32_t pack_chunk<NLSH_STORE_U8>(float4 v) {
+    return (uint32_t)v.x | ((uint32_t)v.y << 8) | ((uint32_t)v.z << 16) | ((uint32_t)v.w << 24);
+}
+
+// the smallest row that held a value the destination storage cannot take (first_bad starts at -1 = 0xFFFFFFFF: unsigned minimum)
+__device__ __forceinline__ void report_bad_row(int32_t *first_bad, bool bad, long long row) {
+    if (first_bad && bad) atomicMin(reinterpret_cast<unsigned int *>(first_bad), (unsigned int)row);
+}
+
+// gather_rows_kernel between storages: one wavefront per destination row, chunk c of the row on lane c % 64.
+template <int SRC, int DST>
+__global__ __launch_bounds__(256) void gather_rows_typed_kernel(const void *corpus, long long src_stride, int d, const int32_t *perm, long long n,
+                                                                 void *sorted, long long dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
+                                                                 int32_t *first_bad, int vec) {
+    typedef typename StoreElem<SRC>::elem src_t;
+    typedef typename StoreElem<DST>::word word_t;
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const int d4 = (int)(dst_stride >> 2);
+    for (long long i = wave; i < n; i += nwaves) {
+        const long long src = perm[i];
+        const src_t *s = static_cast<const src_t *>(corpus) + src * src_stride;
+        word_t *dst = static_cast<word_t *>(sorted) + i * (long long)d4;
+        float ss = 0.0f;
+        bool bad = false;
+        for (int c = lane; c < d4; c += 64) {
+            const float4 v = requantise4<DST>(load_chunk_as_f32<SRC>(s, c, d, vec != 0), bad);
+            dst[c] = pack_chunk<DST>(v);
+            ss = sumsq_chain(v, ss);
+        }
+        if (inv_norm) {
+            ss = sumsq_lanes(ss, 64);
+            if (lane == 0) inv_norm[i] = inv_norm_of(ss);
+        }
+        if (gid && lane == 0) gid[i] = (int32_t)src + id_base;
+        report_bad_row(first_bad, bad, src);
+    }
+}
+
+// One 16-byte unit of a new row (E = 4 / 8 / 16 elements of storage DST = E / 4 chunks), converted from NEW elements.
+template <int NEW, int DST>
+__device__ __forceinline__ uint4 convert_unit(const void *row, int u, int d, bool vec, bool &bad) {
+    if (DST == NLSH_STORE_F32) {
+        const float4 v = requantise4<NLSH_STORE_F32>(load_chunk_as_f32<NEW>(row, u, d, vec), bad);
+        return __builtin_bit_cast(uint4, v);
+    } else if (DST == NLSH_STORE_F16) {
+        const uint2 a = pack_chunk<NLSH_STORE_F16>(requantise4<NLSH_STORE_F16>(load_chunk_as_f32<NEW>(row, 2 * u, d, vec), bad));
+        const uint2 b = pack_chunk<NLSH_STORE_F16>(requantise4<NLSH_STORE_F16>(load_chunk_as_f32<NEW>(row, 2 * u + 1, d, vec), bad));
+        return make_uint4(a.x, a.y, b.x, b.y);
+    } else {
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = pack_chunk<NLSH_STORE_U8>(requantise4<NLSH_STORE_U8>(load_chunk_as_f32<NEW>(row, 4 * u + j, d, vec), bad));
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// update_rows_kernel on a typed index, generalised from "d floats" to "row bytes": the unit is 16 bytes of the stored row (strides in
+// 16-byte units), a row has 2^lg lanes covering its units.  Kept rows are moved as bytes; new rows (NEW elements, any alignment) are
+// converted on the way in (columns >= d zero) and the smallest new row that does not survive is reported.  inv_norm is not this
+// kernel's: a lane holds one, two or four chunks of a new row here, which is not the lane assignment the sum of squares is defined
+// on -- update_inv_norm_typed_kernel computes it from the rows this kernel wrote.
+template <int NEW, int DST>
+__global__ __launch_bounds__(256) void update_rows_typed_kernel(const uint4 *sorted_old, long long units_old, long long n_old,
+                                                                 const void *rows_new, long long stride_new, long long m_new, int d,
+                                                                 const int32_t *src, long long n_out, uint4 *sorted_out, long long units_out,
+                                                                 int lg, int32_t *first_bad, int vec) {
+    typedef typename StoreElem<NEW>::elem new_t;
+    const int lane = threadIdx.x & 63;
+    const int lanes = 1 << lg, g = lane & (lanes - 1), rows_per_inst = 64 >> lg;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const long long step = (long long)rows_per_inst * ROWS_IN_FLIGHT;
+    for (long long base = wave * step; base < n_out; base += nwaves * step) {
+        const uint4 *so[ROWS_IN_FLIGHT];
+        const new_t *sn[ROWS_IN_FLIGHT];
+        long long p[ROWS_IN_FLIGHT];
+        int32_t from[ROWS_IN_FLIGHT];
+        bool bad[ROWS_IN_FLIGHT];
+#pragma unroll
+        for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
+            p[r] = base + (long long)r * rows_per_inst + (lane >> lg);
+            from[r] = p[r] < n_out ? src[p[r]] : 0;
+            // a source outside either side (a slot the index pass never wrote: see there) reads as an all-zero row
+            const bool is_old = from[r] >= 0;
+            const long long j = is_old ? (long long)from[r] : (long long)~from[r];
+            const bool ok = p[r] < n_out && j < (is_old ? n_old : m_new);
+            so[r] = (ok && is_old) ? sorted_old + j * units_old : nullptr;
+            sn[r] = (ok && !is_old) ? static_cast<const new_t *>(rows_new) + j * stride_new : nullptr;
+            bad[r] = false;
+        }
+        for (int u = g; u < units_out; u += 64) {
+            uint4 w[ROWS_IN_FLIGHT];
+#pragma unroll
+            for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
+                if (so[r]) w[r] = u < units_old ? so[r][u] : make_uint4(0u, 0u, 0u, 0u);
+                else if (sn[r]) w[r] = convert_unit<NEW, DST>(sn[r], u, d, vec != 0, bad[r]);
+                else w[r] = make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (int r = 0; r < ROWS_IN_FLIGHT; ++r)
+                if (p[r] < n_out) sorted_out[p[r] * units_out + u] = w[r];
+        }
+#pragma unroll
+        for (int r = 0; r < ROWS_IN_FLIGHT; ++r) report_bad_row(first_bad, bad[r], (long long)~from[r]);
+    }
+}
+
+// inv_norm of the updated typed index: a kept row's value is copied (one lane per row, 64 consecutive rows per wave), a new row's is
+// computed from the row update_rows_typed_kernel stored -- by the whole wave, chunk c on lane c % 64, the 64-lane butterfly: the chain
+// and the bits of gather_rows_typed_kernel (and of the float32 kernels on the dequantised row).
+template <int DST>
+__global__ __launch_bounds__(256) void update_inv_norm_typed_kernel(const void *sorted_out, long long stride_out, const float *inv_old, long long n_old,
+                                                                     const int32_t *src, long long n_out, float *inv_out) {
+    typedef typename StoreElem<DST>::word word_t;
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const int d4 = (int)(stride_out >> 2);
+    for (long long p0 = wave * 64; p0 < n_out; p0 += nwaves * 64) {     // wave-uniform
+        const long long p = p0 + lane;
+        const int32_t from = p < n_out ? src[p] : 0;
+        if (p < n_out && from >= 0) inv_out[p] = from < n_old ? inv_old[from] : inv_norm_of(0.0f);
+        unsigned long long todo = __ballot(p < n_out && from < 0);
+        while (todo) {                                                   // wave-uniform: every lane reaches the butterfly
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const word_t *row = static_cast<const word_t *>(sorted_out) + (p0 + l) * (long long)d4;
+            float ss = 0.0f;
+            for (int c = lane; c < d4; c += 64) ss = sumsq_chain(unpack_chunk<DST>(row[c]), ss);
+            ss = sumsq_lanes(ss, 64);
+            if (lane == 0) inv_out[p0 + l] = inv_norm_of(ss);
+        }
+    }
+}
+
 __global__ void keep_flags_kernel(const uint8_t *keep, long long n, int32_t *flags) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         flags[i] = keep[i] ? 1 : 0;
@@ -577,14 +789,19 @@ extern "C" size_t nlsh_csr_update_workspace(int64_t n_old, int64_t n_buckets_old
     return w.total;
 }
 
-extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
-                               const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
-                               const uint8_t *keep, int64_t n_kept,
-                               const float *rows_new, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new, int64_t m_new,
-                               float *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
-                               int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out,
-                               void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+// nlsh_csr_update and nlsh_csr_update_typed: `storage` = elements of corpus_sorted and sorted_out (strides in elements), `new_storage` =
+// elements of rows_new; float32 on both sides is the float32 row kernel, untouched.
+static int csr_update_impl(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
+                           const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                           const uint8_t *keep, int64_t n_kept,
+                           const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new, int64_t m_new,
+                           void *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                           int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad,
+                           void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
     // ---- host checks: nothing below them runs, and no pointer is read, unless all of them pass
+    NLSH_REQUIRE(store_ok(storage) && store_ok(new_storage), NLSH_E_INVALID, "csr_update: storage=%d / new_storage=%d is none of NLSH_STORE_F32 / F16 / U8",
+                 storage, new_storage);
+    const int per16 = store_per16(storage);
     NLSH_REQUIRE(d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "csr_update: d=%d not in [1, NLSH_MAX_DIM = %d]", d, NLSH_MAX_DIM);
     NLSH_REQUIRE(n_old >= 0 && n_old < (1ll << 31), NLSH_E_INVALID, "csr_update: n_old=%lld not in [0, 2^31)", (long long)n_old);
     NLSH_REQUIRE(n_buckets_old >= 0 && n_buckets_old <= n_old, NLSH_E_INVALID, "csr_update: n_buckets_old=%lld not in [0, n_old=%lld]",
@@ -597,8 +814,8 @@ extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, i
     NLSH_REQUIRE(n_out <= 0x7FFFFFFFll, NLSH_E_INVALID, "csr_update: n_kept + m_new = %lld rows > 2^31 - 1 (int32 row positions)", n_out);
     NLSH_REQUIRE(offsets_out && n_buckets_out, NLSH_E_INVALID, "csr_update: offsets_out / n_buckets_out is null");
     if (n_old) {
-        NLSH_REQUIRE(row_stride >= d && (row_stride & 3) == 0, NLSH_E_INVALID, "csr_update: row_stride=%lld must be >= d=%d and a multiple of 4",
-                     (long long)row_stride, d);
+        NLSH_REQUIRE(row_stride >= d && row_stride % per16 == 0, NLSH_E_INVALID, "csr_update: row_stride=%lld must be >= d=%d and a multiple of %d",
+                     (long long)row_stride, d, per16);
         NLSH_REQUIRE(corpus_sorted && gid && uniq_keys && offsets, NLSH_E_INVALID, "csr_update: corpus_sorted / gid / uniq_keys / offsets is null with n_old=%lld",
                      (long long)n_old);
         NLSH_REQUIRE(((uintptr_t)corpus_sorted & 15) == 0, NLSH_E_INVALID, "csr_update: corpus_sorted must be 16-byte aligned");
@@ -607,12 +824,14 @@ extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, i
     if (m_new) {
         NLSH_REQUIRE(new_stride >= d, NLSH_E_INVALID, "csr_update: new_stride=%lld < d=%d", (long long)new_stride, d);
         NLSH_REQUIRE(rows_new && keys_new && ids_new, NLSH_E_INVALID, "csr_update: rows_new / keys_new / ids_new is null with m_new=%lld", (long long)m_new);
+        NLSH_REQUIRE(first_bad || new_storage == storage, NLSH_E_INVALID, "csr_update: first_bad is null but the new rows (new_storage=%d) are converted to storage=%d",
+                     new_storage, storage);
     }
     UpdateWs w;
     update_layout(n_old, n_buckets_old, m_new, &w);
     if (n_out) {
-        NLSH_REQUIRE(stride_out >= d && (stride_out & 3) == 0, NLSH_E_INVALID, "csr_update: stride_out=%lld must be >= d=%d and a multiple of 4",
-                     (long long)stride_out, d);
+        NLSH_REQUIRE(stride_out >= d && stride_out % per16 == 0, NLSH_E_INVALID, "csr_update: stride_out=%lld must be >= d=%d and a multiple of %d",
+                     (long long)stride_out, d, per16);
         NLSH_REQUIRE(sorted_out && gid_out && src_out && uniq_out, NLSH_E_INVALID, "csr_update: sorted_out / gid_out / src_out / uniq_out is null");
         NLSH_REQUIRE(((uintptr_t)sorted_out & 15) == 0, NLSH_E_INVALID, "csr_update: sorted_out must be 16-byte aligned");
         NLSH_REQUIRE(!inv_norm_out || inv_norm || n_kept == 0, NLSH_E_INVALID, "csr_update: inv_norm_out is wanted but inv_norm (the kept rows') is null");
@@ -622,6 +841,7 @@ extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, i
     }
     // ---- device work
     hipStream_t s = (hipStream_t)stream;
+    if (first_bad) NLSH_CHECK_HIP(hipMemsetAsync(first_bad, 0xFF, sizeof(int32_t), s));   // -1: every new row survived its conversion
     if (n_out == 0) {
         NLSH_CHECK_HIP(hipMemsetAsync(offsets_out, 0, sizeof(int32_t), s));
         NLSH_CHECK_HIP(hipMemsetAsync(n_buckets_out, 0, sizeof(int32_t), s));
@@ -668,13 +888,109 @@ extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, i
     const long long rows_per_wave = (long long)(64 >> lg) * ROWS_IN_FLIGHT;
     long long blocks = ((n_out + rows_per_wave - 1) / rows_per_wave + 3) / 4;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    const bool vec = ((new_stride & 3) == 0) && (((uintptr_t)rows_new & 15) == 0);
-    if (vec)
-        hipLaunchKernelGGL(update_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, corpus_sorted, (long long)row_stride, inv_norm, (long long)n_old,
-                           rows_new, (long long)new_stride, (long long)m_new, d, src_out, n_out, sorted_out, (long long)stride_out, inv_norm_out, lg);
-    else
-        hipLaunchKernelGGL(update_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, corpus_sorted, (long long)row_stride, inv_norm, (long long)n_old,
-                           rows_new, (long long)new_stride, (long long)m_new, d, src_out, n_out, sorted_out, (long long)stride_out, inv_norm_out, lg);
+    if (storage == NLSH_STORE_F32 && new_storage == NLSH_STORE_F32) {
+        const float *old_f = (const float *)corpus_sorted, *new_f = (const float *)rows_new;
+        float *out_f = (float *)sorted_out;
+        const bool vec = ((new_stride & 3) == 0) && (((uintptr_t)rows_new & 15) == 0);
+        if (vec)
+            hipLaunchKernelGGL(update_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, old_f, (long long)row_stride, inv_norm, (long long)n_old,
+                               new_f, (long long)new_stride, (long long)m_new, d, src_out, n_out, out_f, (long long)stride_out, inv_norm_out, lg);
+        else
+            hipLaunchKernelGGL(update_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, old_f, (long long)row_stride, inv_norm, (long long)n_old,
+                               new_f, (long long)new_stride, (long long)m_new, d, src_out, n_out, out_f, (long long)stride_out, inv_norm_out, lg);
+    } else {
+        // typed storage: the row pass in 16-byte units, then the inv_norm pass over what it wrote
+        const long long units_old = row_stride / per16, units_out = stride_out / per16;
+        int lgu = 0;
+        while ((1 << lgu) < units_out && lgu < 6) ++lgu;
+        const long long rows_per_wave_u = (long long)(64 >> lgu) * ROWS_IN_FLIGHT;
+        long long ublocks = ((n_out + rows_per_wave_u - 1) / rows_per_wave_u + 3) / 4;
+        if (ublocks > 256 * 8) ublocks = 256 * 8;
+        const void *fn = nullptr;
+#define NLSH_UPD(N, D) if (new_storage == N && storage == D) fn = (const void *)update_rows_typed_kernel<N, D>;
+        NLSH_UPD(NLSH_STORE_F16, NLSH_STORE_F32) NLSH_UPD(NLSH_STORE_U8, NLSH_STORE_F32)
+        NLSH_UPD(NLSH_STORE_F32, NLSH_STORE_F16) NLSH_UPD(NLSH_STORE_F16, NLSH_STORE_F16) NLSH_UPD(NLSH_STORE_U8, NLSH_STORE_F16)
+        NLSH_UPD(NLSH_STORE_F32, NLSH_STORE_U8) NLSH_UPD(NLSH_STORE_F16, NLSH_STORE_U8) NLSH_UPD(NLSH_STORE_U8, NLSH_STORE_U8)
+#undef NLSH_UPD
+        long long uo = units_old, nold = n_old, sn = new_stride, mn = m_new, no = n_out, ut = units_out, sto = stride_out;
+        int vecn = store_vec_ok(rows_new, new_storage, new_stride);      // new rows on chunk boundaries of their storage: one load per chunk
+        void *argv[] = {&corpus_sorted, &uo, &nold, &rows_new, &sn, &mn, &d, &src_out, &no, &sorted_out, &ut, &lgu, &first_bad, &vecn};
+        NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)ublocks), dim3(256), argv, 0, s));
+        if (inv_norm_out) {
+            const void *fi = storage == NLSH_STORE_F32 ? (const void *)update_inv_norm_typed_kernel<NLSH_STORE_F32>
+                           : storage == NLSH_STORE_F16 ? (const void *)update_inv_norm_typed_kernel<NLSH_STORE_F16>
+                                                       : (const void *)update_inv_norm_typed_kernel<NLSH_STORE_U8>;
+            long long iblocks = ((n_out + 63) / 64 + 3) / 4;
+            if (iblocks > 256 * 8) iblocks = 256 * 8;
+            void *argi[] = {&sorted_out, &sto, &inv_norm, &nold, &src_out, &no, &inv_norm_out};
+            NLSH_CHECK_HIP(hipLaunchKernel(fi, dim3((unsigned)iblocks), dim3(256), argi, 0, s));
+        }
+    }
+    NLSH_CHECK_HIP(hipGetLastError());
+    return NLSH_OK;
+}
+
+extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
+                               const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                               const uint8_t *keep, int64_t n_kept,
+                               const float *rows_new, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new, int64_t m_new,
+                               float *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                               int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out,
+                               void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+    return csr_update_impl(corpus_sorted, NLSH_STORE_F32, row_stride, d, gid, inv_norm, uniq_keys, offsets, n_old, n_buckets_old, keep, n_kept,
+                           rows_new, NLSH_STORE_F32, new_stride, keys_new, ids_new, m_new, sorted_out, stride_out, gid_out, inv_norm_out, src_out,
+                           uniq_out, offsets_out, n_buckets_out, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nlsh_csr_update_typed(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
+                                     const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                                     const uint8_t *keep, int64_t n_kept,
+                                     const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new,
+                                     int64_t m_new,
+                                     void *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                                     int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad,
+                                     void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+    return csr_update_impl(corpus_sorted, storage, row_stride, d, gid, inv_norm, uniq_keys, offsets, n_old, n_buckets_old, keep, n_kept,
+                           rows_new, new_storage, new_stride, keys_new, ids_new, m_new, sorted_out, stride_out, gid_out, inv_norm_out, src_out,
+                           uniq_out, offsets_out, n_buckets_out, first_bad, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nlsh_gather_rows_typed(const void *corpus, int src_storage, int64_t src_stride, int d, const int32_t *perm, int64_t n,
+                                      void *sorted, int dst_storage, int64_t dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
+                                      int32_t *first_bad, nlsh_stream_t stream) {
+    NLSH_REQUIRE(store_ok(src_storage) && store_ok(dst_storage), NLSH_E_INVALID,
+                 "gather_rows_typed: src_storage=%d / dst_storage=%d is none of NLSH_STORE_F32 / F16 / U8", src_storage, dst_storage);
+    NLSH_REQUIRE(n >= 0 && d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "gather_rows_typed: n=%lld d=%d", (long long)n, d);
+    NLSH_REQUIRE(first_bad || src_storage == dst_storage, NLSH_E_INVALID,
+                 "gather_rows_typed: first_bad is null but the rows are converted (src_storage=%d, dst_storage=%d)", src_storage, dst_storage);
+    if (n) {
+        NLSH_REQUIRE(corpus && perm && sorted, NLSH_E_INVALID, "gather_rows_typed: corpus / perm / sorted is null");
+        NLSH_REQUIRE(dst_stride >= d && dst_stride % store_per16(dst_storage) == 0, NLSH_E_INVALID,
+                     "gather_rows_typed: dst_stride=%lld must be >= d=%d and a multiple of %d elements (a pitch of 16-byte units) for dst_storage=%d",
+                     (long long)dst_stride, d, store_per16(dst_storage), dst_storage);
+        NLSH_REQUIRE(((uintptr_t)sorted & 15) == 0, NLSH_E_INVALID, "gather_rows_typed: sorted must be 16-byte aligned");
+        NLSH_REQUIRE(src_stride >= d, NLSH_E_INVALID, "gather_rows_typed: src_stride=%lld < d=%d", (long long)src_stride, d);
+        // an element pointer is read with element loads: it must be aligned to its element
+        NLSH_REQUIRE(((uintptr_t)corpus & (src_storage == NLSH_STORE_F32 ? 3 : src_storage == NLSH_STORE_F16 ? 1 : 0)) == 0, NLSH_E_INVALID,
+                     "gather_rows_typed: corpus is not aligned to its element size");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (first_bad) NLSH_CHECK_HIP(hipMemsetAsync(first_bad, 0xFF, sizeof(int32_t), s));   // -1: every row survived its conversion
+    if (n == 0) return NLSH_OK;
+    if (src_storage == NLSH_STORE_F32 && dst_storage == NLSH_STORE_F32)
+        return nlsh_gather_rows((const float *)corpus, src_stride, d, perm, n, (float *)sorted, dst_stride, inv_norm, gid, id_base, stream);
+    long long blocks = (n + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    const void *fn = nullptr;
+#define NLSH_GAT(S, D) if (src_storage == S && dst_storage == D) fn = (const void *)gather_rows_typed_kernel<S, D>;
+    NLSH_GAT(NLSH_STORE_F16, NLSH_STORE_F32) NLSH_GAT(NLSH_STORE_U8, NLSH_STORE_F32)
+    NLSH_GAT(NLSH_STORE_F32, NLSH_STORE_F16) NLSH_GAT(NLSH_STORE_F16, NLSH_STORE_F16) NLSH_GAT(NLSH_STORE_U8, NLSH_STORE_F16)
+    NLSH_GAT(NLSH_STORE_F32, NLSH_STORE_U8) NLSH_GAT(NLSH_STORE_F16, NLSH_STORE_U8) NLSH_GAT(NLSH_STORE_U8, NLSH_STORE_U8)
+#undef NLSH_GAT
+    long long ss = src_stride, nn = n, ds = dst_stride;
+    int vec = store_vec_ok(corpus, src_storage, src_stride);             // rows on chunk boundaries of their storage: one load per chunk
+    void *argv[] = {&corpus, &ss, &d, &perm, &nn, &sorted, &ds, &inv_norm, &gid, &id_base, &first_bad, &vec};
+    NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, 0, s));
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
 }

@@ -1,6 +1,7 @@
-// Bucket-major scan, LDS-tiled schedule (part of the translation unit scan_bucket.hip, which defines BArgs in front of this file):
+// Bucket-major scan, LDS-tiled schedule (included by two translation units behind scan_bucket_args.h, which defines BArgs: scan_bucket.hip
+// instantiates the float32 kernels, scan_bucket_typed.hip the float16 / uint8 ones):
 // the hand-scheduled k-blocks, the task bodies built from them (l2_task*), one task start to finish (tiled_task_body) and the kernels
-// bscan3_kernel (k <= 64) and bscanw_kernel (k up to NLSH_MAX_K_TILED).
+// bscan3_kernel (k <= 64) and bscanw_kernel (k up to NLSH_MAX_K_TILED) over a float32 corpus, bscant_kernel over a float16 / uint8 one.
 #pragma once
 
 // Diagnostic build only (make EXTRA=-DNLSH_SCAN_TRACE, tools/scan_trace.py): wave 0 of every bscan3 workgroup
@@ -272,6 +273,36 @@ __device__ __forceinline__ void warm_query_lines_done(float &sink) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(sink)::"memory");
 }
 
+// ---- corpus storage (NLSH_STORE_*, nlsh_scan_topk_cells_phase_typed) ------------------------------------------------------------
+// A 16-byte LDS slot -- one float4 chunk of a row -- is 16 / 8 / 4 bytes of a float32 / float16 / uint8 corpus in memory.  The staging
+// code loads the chunk's `word`, keeps it narrow in the staging registers while the load is in flight and converts it to float4 when the
+// tile is written (`widen`: exact conversions, plain C++ -- v_cvt_f32_f16 / v_cvt_f32_ubyte0..3 as compiled).  Everything behind the
+// tile -- the k-blocks, the query side, the epilogues -- is the same code on the same float32 values: a typed index answers with the
+// bits of the float32 index over the dequantised rows, and the conversion is paid per (task, row element), never per query.
+// The float32 form is the identity on float4: the float32 kernels are the instantiations they were.
+template <int STORE> struct Stored;
+template <> struct Stored<NLSH_STORE_F32> {
+    typedef float4 word;
+    static __device__ __forceinline__ float4 widen(float4 w) { return w; }
+    static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+};
+template <> struct Stored<NLSH_STORE_F16> {
+    typedef uint2 word;     // four halves
+    static __device__ __forceinline__ float4 widen(uint2 w) {
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        const h2 lo = __builtin_bit_cast(h2, w.x), hi = __builtin_bit_cast(h2, w.y);
+        return make_float4((float)lo.x, (float)lo.y, (float)hi.x, (float)hi.y);
+    }
+    static __device__ __forceinline__ uint2 zero() { return make_uint2(0u, 0u); }
+};
+template <> struct Stored<NLSH_STORE_U8> {
+    typedef uint32_t word;  // four bytes
+    static __device__ __forceinline__ float4 widen(uint32_t w) {
+        return make_float4((float)(w & 0xFFu), (float)((w >> 8) & 0xFFu), (float)((w >> 16) & 0xFFu), (float)(w >> 24));
+    }
+    static __device__ __forceinline__ uint32_t zero() { return 0u; }
+};
+
 // All k-blocks of one L2 task for a wave that holds NQ (0..4) of its queries, NTL = tiles of the task (1..4): staging
 // (global -> registers -> LDS, next k-block's loads in flight during the current one) + the hand-scheduled k-blocks.
 // The (NQ, NTL) pair is chosen ONCE per task, outside the k-block loop: chosen per k-block, the 16 accumulators crossed
@@ -280,8 +311,9 @@ __device__ __forceinline__ void warm_query_lines_done(float &sink) {
 // (WIDEK changes nothing in here: it gives the wide-k kernels instantiations of their own.  The stage_load lambda below is an ordinary
 // function that the compiler inlines by its own judgement, and with a second kernel calling the SAME instantiation it judged differently:
 // the k <= 64 kernels' staging code changed and took three more VGPRs.)
-template <int NW, int NQ, int NTL, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false>
-__device__ __forceinline__ void l2_task(float4 *tile, const float4 *corpus4, long long stride4, int d4, int row0, int nrows,
+// (STORE: the corpus storage, see Stored above; a typed kernel's task bodies are instantiations of their own for the same reason.)
+template <int NW, int NQ, int NTL, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false, int STORE = NLSH_STORE_F32>
+__device__ __forceinline__ void l2_task(float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
                                         const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4],
                                         [[maybe_unused]] unsigned long long (&tr)[3]) {
     constexpr int NTH = 64 * NW, KB = NLSH_TILED_KB;
@@ -293,19 +325,19 @@ __device__ __forceinline__ void l2_task(float4 *tile, const float4 *corpus4, lon
     constexpr int KBt = KB << kshift, RSt = KBt + 1, RPPt = (NTH / KB) >> kshift, SPT = 256 * KB / NTH;
     const int nkb = (d4 + KBt - 1) / KBt;
     const int sc = tid & (KBt - 1), sr = tid / KBt;   // staging map: KBt threads cover 16*KBt contiguous bytes of a row
-    float4 stg[SPT];
+    typename Stored<STORE>::word stg[SPT];
     // Rows past the end of the segment and chunks past the end of a row are CLAMPED, not zero-filled: the clamped loads read valid
     // memory, rows >= nrows are masked at the epilogue (`valid`) and a k-block only evaluates its `nchunk` real chunks.  Guarded,
     // every staged word sat behind its own exec mask + branch + zero fill: ~22 VALU, 12 SALU and 4 branches per stage and wave.
     // (r04: a SECOND register set -- two k-blocks of a wave's rows in flight, for the waves that hold <= 0 / 1 / 2 / 4 of the task's
     // queries -- measured equal on all three workloads at 76 / 80 VGPRs and 3-6 % slower at 88: DESIGN.md appendix A.)
-    const float4 *rowp[SPT];
+    const typename Stored<STORE>::word *rowp[SPT];
 #pragma unroll
     for (int i = 0; i < SPT; ++i) rowp[i] = corpus4 + (long long)(row0 + min(sr + RPPt * i, nrows - 1)) * stride4;
     auto stage_load = [&](int kb) {
         const int gc = min(kb * KBt + sc, d4 - 1);
 #pragma unroll
-        for (int i = 0; i < SPT; ++i) stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? rowp[i][gc] : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int i = 0; i < SPT; ++i) stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? rowp[i][gc] : Stored<STORE>::zero();
     };
     stage_load(0);
     float qsink = 0.0f;
@@ -316,7 +348,7 @@ __device__ __forceinline__ void l2_task(float4 *tile, const float4 *corpus4, lon
         NLSH_STAGE_SYNC();  // everyone has finished reading the previous k-block
         [[maybe_unused]] const unsigned long long tb = SCAN_NOW();
 #pragma unroll
-        for (int i = 0; i < SPT; ++i) tile[(sr + RPPt * i) * RSt + sc] = stg[i];
+        for (int i = 0; i < SPT; ++i) tile[(sr + RPPt * i) * RSt + sc] = Stored<STORE>::widen(stg[i]);
         NLSH_STAGE_SYNC();
         if (kb + 1 < nkb) stage_load(kb + 1);  // in flight while this k-block is computed
         // (r05: the queries' published bounds requested HERE in front of the last k-block, whose staging registers are free, instead of
@@ -352,8 +384,8 @@ __device__ __forceinline__ void l2_task(float4 *tile, const float4 *corpus4, lon
 // 0.12 ms), the counters saw 1.33x the bytes the task table accounts for (profiles/r05_traffic_tally.txt).  Here every line of the task
 // is requested once, and the task has one exposed round trip less.  Same k-ascending fmaf chain per (row, query): same bits.
 constexpr int SINGLE_STAGE_SLOTS = 1024;   // float4 slots one pass of the 256 threads stages (4 each)
-template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS>
-__device__ __forceinline__ void l2_task_single(float4 *tile, const float4 *corpus4, long long stride4, int d4, int row0, int nrows,
+template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS, int STORE = NLSH_STORE_F32>
+__device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
                                                const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4]) {
     constexpr int NTH = 64 * NW, SPT = SINGLE_STAGE_SLOTS / NTH;
     const int RS = d4 | 1;                   // odd LDS row stride (16-byte slots): conflict-free column reads
@@ -361,7 +393,7 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const float4 *corpu
     const float inv = 1.0f / (float)d4;
     // (r05: the pass started at the 128-byte line below the task's first byte, so that every wave-load covered whole lines of the L2: the
     // counters did not move -- 289.6 against 289.5 K FETCH_SIZE units per GloVe launch -- and the shift was removed; DESIGN.md appendix A.)
-    float4 stg[SPT];
+    typename Stored<STORE>::word stg[SPT];
     int dst[SPT];
 #pragma unroll
     for (int i = 0; i < SPT; ++i) {
@@ -370,7 +402,7 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const float4 *corpu
         r -= (r * d4 > idx) ? 1 : 0;
         r += ((r + 1) * d4 <= idx) ? 1 : 0;
         const int c = idx - r * d4;
-        stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? corpus4[(long long)(row0 + r) * stride4 + c] : make_float4(0.f, 0.f, 0.f, 0.f);
+        stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? corpus4[(long long)(row0 + r) * stride4 + c] : Stored<STORE>::zero();
         dst[i] = r * RS + c;
     }
     float qsink = 0.0f;
@@ -379,7 +411,7 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const float4 *corpu
     // one task per workgroup: nobody has read the tile before, so the writes need no barrier in front of them
 #pragma unroll
     for (int i = 0; i < SPT; ++i)
-        if (tid + NTH * i < total) tile[dst[i]] = stg[i];
+        if (tid + NTH * i < total) tile[dst[i]] = Stored<STORE>::widen(stg[i]);
     NLSH_STAGE_SYNC();
     if (NQ > 0) {
         warm_query_lines_done(qsink);
@@ -393,15 +425,15 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const float4 *corpu
     }
 }
 
-template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false>
-__device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const float4 *corpus4, long long stride4, int d4, int row0, int nrows,
+template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false, int STORE = NLSH_STORE_F32>
+__device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
                                            const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4], unsigned long long (&tr)[3]) {
     switch (ntile) {
-        case 0: l2_task_single<NW, NQ, METRIC>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc); break;   // "0 tiles": the single-stage body
-        case 1: l2_task<NW, NQ, 1, METRIC, WIDEK>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
-        case 2: l2_task<NW, NQ, 2, METRIC, WIDEK>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
-        case 3: l2_task<NW, NQ, 3, METRIC, WIDEK>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
-        default: l2_task<NW, NQ, 4, METRIC, WIDEK>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
+        case 0: l2_task_single<NW, NQ, METRIC, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc); break;   // "0 tiles": the single-stage body
+        case 1: l2_task<NW, NQ, 1, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
+        case 2: l2_task<NW, NQ, 2, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
+        case 3: l2_task<NW, NQ, 3, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
+        default: l2_task<NW, NQ, 4, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
     }
 }
 
@@ -415,7 +447,7 @@ __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const float4
 // the wave's query ids).  `tile` = the workgroup's LDS stage.
 // WIDEK (compile time): k in 65..NLSH_MAX_K_TILED -- the epilogue's selection pads its k-key list with a lane-strided loop; everything in
 // front of the epilogue is the same code, so every distance keeps its bits.
-template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false>
+template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = NLSH_STORE_F32>
 __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, long long t, const int4 desc, const int2 qr_all, int tid, int lane,
                                                 int wave, [[maybe_unused]] unsigned long long ts_entry) {
     static_assert(QW == 4 && TPS == 4 && NW == 4, "the hand-scheduled task bodies (l2_task_nt) are written for 4 waves x 4 queries x 4 row tiles");
@@ -450,8 +482,8 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
         qs[jq] = (const_f32p)(a.qpad + (long long)qid[jq] * a.qpad_stride);
     }
 
-    const float4 *corpus4 = reinterpret_cast<const float4 *>(a.corpus);
-    const long long stride4 = a.row_stride >> 2;
+    const typename Stored<STORE>::word *corpus4 = reinterpret_cast<const typename Stored<STORE>::word *>(a.corpus);
+    const long long stride4 = a.row_stride >> 2;   // row pitch in 4-element chunks, whatever the storage
     const int d4 = a.d4p;
     const int ntile = (nrows + 63) >> 6;
     float acc[TPS][QW];
@@ -478,11 +510,11 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
     const int nt_sel = (nrows * d4 <= SINGLE_STAGE_SLOTS && nrows <= 64) ? 0 : ntile;   // wave-uniform (task shape)
     // the hand-scheduled form, specialised per (queries of this wave, tiles of the task); same barrier count on every path
     switch (nqw) {
-        case 0: l2_task_nt<NW, 0, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-        case 1: l2_task_nt<NW, 1, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-        case 2: l2_task_nt<NW, 2, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-        case 3: l2_task_nt<NW, 3, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-        default: l2_task_nt<NW, 4, METRIC, WIDEK>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+        case 0: l2_task_nt<NW, 0, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+        case 1: l2_task_nt<NW, 1, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+        case 2: l2_task_nt<NW, 2, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+        case 3: l2_task_nt<NW, 3, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+        default: l2_task_nt<NW, 4, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
     }
     if (nqw == 0) return;
     if (NLSH_ABLATE == 5 || NLSH_ABLATE == 6 || NLSH_ABLATE == 12 || NLSH_ABLATE == 13) {   // diagnostic: no epilogue at all (the accumulators are kept alive)
@@ -644,6 +676,33 @@ __global__ __launch_bounds__(64 * NW, 1) void bscanw_kernel(BArgs a) {
     const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
     if (t >= ntasks) return;
     tiled_task_body<METRIC, QW, NW, TPS, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry);
+}
+
+// The tiled scan over a float16 / uint8 corpus (STORE: NLSH_STORE_F16 | NLSH_STORE_U8; nlsh_scan_topk_cells_phase_typed), k <= 64 (WIDEK
+// false) and k in 65..NLSH_MAX_K_TILED (true).  Kernels of their own name with task bodies of their own instantiation (STORE), so that
+// bscan3_kernel and bscanw_kernel -- what every float32 index runs -- keep their code: profiles/corpus_storage.txt compares them with
+// the build before the typed forms existed.  The task pick is bscan3_kernel's, line for line (see the comments there), written out
+// again for the reason given at bscanw_kernel.
+template <int METRIC, int QW, int NW, int TPS, int STORE, bool WIDEK>
+__global__ __launch_bounds__(64 * NW, 1) void bscant_kernel(BArgs a) {
+    static_assert(STORE == NLSH_STORE_F16 || STORE == NLSH_STORE_U8, "the float32 corpus has bscan3_kernel / bscanw_kernel");
+    constexpr int RS = NLSH_TILED_KB + 1;
+    __shared__ float4 tile[64 * TPS * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
+    long long ntasks = a.status[0];
+    if (ntasks > a.max_tasks) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
+        ntasks = a.max_tasks;
+    }
+    constexpr int XC = 16;
+    const long long j = blockIdx.x >> 3;
+    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
+    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
+    const int4 desc = a.task[tc];
+    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
+    if (t >= ntasks) return;
+    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry);
 }
 
 }  // namespace nlsh

@@ -429,6 +429,8 @@ struct BucketScanCall {
     int plan_blocks;              // NLSH_PHASE_PLAN_REST: workgroups of the encode_hash launch that did the lookup (entries of `hits`)
     int32_t *host_out;            // nlsh_query_batch_host: the MERGE phase (k <= NLSH_MAX_K) stores its results into this host-visible block
                                   // (layout: bmerge_host_kernel) instead of out_dist / out_idx / out_ncand; nullptr everywhere else
+    int storage;                  // NLSH_STORE_*: what `corpus` really points to (row_stride in elements); anything but F32 is the tiled
+                                  // schedule's alone and set by nlsh_scan_topk_cells_phase_typed only (0 = F32 everywhere else)
 };
 // internal phase bit (not part of the C ABI's phase mask): the PLAN phase WITHOUT the bucket lookup, which the batch's encode_hash
 // launch already did in its epilogue (scan_plan.h, encode_plan_fuse_lookup): bscan + bscatter only
@@ -437,6 +439,8 @@ struct PlanArgs;
 size_t bucket_scan_workspace(long long Q, int P, int k, long long max_tasks, long long n_buckets, int d);
 int bucket_scan_run(const BucketScanCall &c);
 int bucket_scan_plan_args(const BucketScanCall &c, PlanArgs *pa);   // the lookup's arguments for this call's workspace
+// the tiled scan kernel over a float16 / uint8 corpus (scan_bucket_typed.hip): storage NLSH_STORE_F16 | NLSH_STORE_U8, wide = k > NLSH_MAX_K
+const void *typed_scan_kernel_of(int storage, int metric, bool wide);
 
 // nlsh_scan_topk_cells_phase after argument validation, with the internal phase bit allowed; `call_out` (nullable) receives the
 // bucket-major call descriptor instead of running it (step.hip builds the fused lookup's arguments from it)

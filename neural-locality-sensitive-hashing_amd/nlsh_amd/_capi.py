@@ -16,6 +16,7 @@ ACT_SIGMOID, ACT_TANH = 0, 1
 KEY_REF_INT16, KEY_FULL = 0, 1
 METRIC_L2_EPS, METRIC_COSINE, METRIC_L2_EPS_FOLDED = 0, 1, 2
 SCAN_QUERY_MAJOR, SCAN_BUCKET_MAJOR, SCAN_BUCKET_TILED = 0, 1, 2
+STORE_F32, STORE_F16, STORE_U8 = 0, 1, 2   # NLSH_STORE_*: element type of a bucket-sorted corpus copy (the *_typed entry points)
 MAX_LAYERS, MAX_HASH_BITS, MAX_PROBES, MAX_K, MAX_DIM, MAX_WIDTH = 8, 32, 64, 64, 1024, 632
 MAX_K_TILED = 256  # k of the tiled schedule and of nlsh_merge_topk (NLSH_MAX_K_TILED); MAX_K is what every schedule takes
 PHASE_PLAN, PHASE_SCAN, PHASE_MERGE = 1, 2, 4
@@ -40,6 +41,7 @@ SYMBOLS = (
     "nlsh_probe_ranked", "nlsh_probe_ranked_budget",
     "nlsh_query_batch_ranked_scratch", "nlsh_query_batch_ranked",
     "nlsh_csr_update_workspace", "nlsh_csr_update",
+    "nlsh_scan_topk_cells_phase_typed", "nlsh_gather_rows_typed", "nlsh_csr_update_typed",
 )
 
 
@@ -127,6 +129,11 @@ def lib():
     L.nlsh_csr_update.restype = i32     # old index (9) | keep, n_kept | new rows (5) | outputs (8) | workspace, bytes, stream
     L.nlsh_csr_update.argtypes = [vp, i64, i32, vp, vp, vp, vp, i64, i64,  vp, i64,  vp, i64, vp, vp, i64,
                                   vp, i64, vp, vp, vp, vp, vp, vp,  vp, sz, vp]
+    L.nlsh_gather_rows_typed.restype = i32     # (corpus, storage) ... (sorted, storage) ... first_bad, stream
+    L.nlsh_gather_rows_typed.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, i64, vp, vp, ctypes.c_int32, vp, vp]
+    L.nlsh_csr_update_typed.restype = i32      # nlsh_csr_update with a storage behind corpus_sorted and rows_new, first_bad behind the outputs
+    L.nlsh_csr_update_typed.argtypes = [vp, i32, i64, i32, vp, vp, vp, vp, i64, i64,  vp, i64,  vp, i32, i64, vp, vp, i64,
+                                        vp, i64, vp, vp, vp, vp, vp, vp, vp,  vp, sz, vp]
     L.nlsh_scan_workspace.restype = sz
     L.nlsh_scan_workspace.argtypes = [i64, i32, i32, i64, i64, i32]
     L.nlsh_scan_workspace_layout.restype = i32
@@ -138,6 +145,8 @@ def lib():
     L.nlsh_scan_topk_phase.argtypes = list(L.nlsh_scan_topk.argtypes) + [i32]
     L.nlsh_scan_topk_cells_phase.restype = i32     # cell_of, cell_offsets, n_cells follow n_buckets
     L.nlsh_scan_topk_cells_phase.argtypes = L.nlsh_scan_topk_phase.argtypes[:8] + [vp, vp, ctypes.c_int32] + L.nlsh_scan_topk_phase.argtypes[8:]
+    L.nlsh_scan_topk_cells_phase_typed.restype = i32     # storage follows corpus_sorted
+    L.nlsh_scan_topk_cells_phase_typed.argtypes = L.nlsh_scan_topk_cells_phase.argtypes[:1] + [i32] + L.nlsh_scan_topk_cells_phase.argtypes[1:]
     L.nlsh_merge_topk.restype = i32
     L.nlsh_merge_topk.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, vp, vp]
     L.nlsh_step_create.restype = i32

@@ -241,6 +241,9 @@ class ShardedIndexer:
         from .indexer import Indexer
         if shard not in ("buckets", "rows"):
             raise ValueError("shard must be 'buckets' or 'rows'")
+        if kw.get("storage") not in (None, "float32"):
+            raise NotImplementedError(f"a sharded index takes float32 storage only, not storage={kw['storage']!r}: the row exchange and the "
+                                      "pipelined batches behind it move float32 rows")
         self.group = group
         self.shard = shard
         world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -160,13 +160,31 @@ def build_index(indexes, cuda=True) -> Dict[int, torch.Tensor]:
     return {int(k): chunk for k, chunk in zip(names, torch.split(grouped, sizes))}
 
 
+# `storage=`: element type of the bucket-sorted corpus copy -> (torch dtype, NLSH_STORE_* code, elements per 16 bytes)
+_STORAGES = {"float32": (torch.float32, _capi.STORE_F32, 4), "float16": (torch.float16, _capi.STORE_F16, 8), "uint8": (torch.uint8, _capi.STORE_U8, 16)}
+_STORE_CODE_OF_DTYPE = {dt: code for dt, code, _ in _STORAGES.values()}
+
+
 class Indexer:
+
+    # "float32" | "float16" | "uint8": what `corpus_sorted` holds.  A compressed index (the last two) is, by definition,
+    # the float32 index over its dequantised rows: both conversions to float32 are exact, the rows are widened as the tiled scan stages
+    # them, and every array and every query result has the float32 index's bits.
+    storage = "float32"
 
     def __init__(self, hashing, candidate_vectors_gpu, distance_func, compat=True, metric: Optional[str] = None,
                  seg_rows: int = 0, id_base: int = 0, algo: Optional[str] = None,
                  row_ids: Optional[torch.Tensor] = None, schedule_stats: Optional[Tuple[float, float]] = None,
                  corpus_keys: Optional[torch.Tensor] = None, l2_form: str = "exact", window_rows: Optional[int] = None,
-                 row_align: int = 4):
+                 row_align: int = 4, storage: Optional[str] = None):
+        # storage: None / "float32" = the float32 copy (any other corpus dtype is converted with `.float()`, as ever); "float16" /
+        # "uint8" = a compressed copy, read by the tiled schedule only (checked before anything touches a device)
+        if storage is not None and storage not in _STORAGES:
+            raise ValueError(f"storage must be None or one of {tuple(_STORAGES)}, got {storage!r}")
+        self.storage = storage or "float32"
+        if self.compressed and algo in ("query", "bucket"):
+            raise ValueError(f"algo={algo!r} cannot read storage={self.storage!r}: a compressed index is scanned by the tiled schedule only "
+                             "(algo=None or 'tiled')")
         self._hashing = hashing
         self._candidate_vectors_gpu = candidate_vectors_gpu
         self._distance_func = distance_func
@@ -215,8 +233,80 @@ class Indexer:
         # the id `add` gives its first row when the caller names none: only ever grows, so a removed row's id is never handed out again
         self.next_id = self.id_base + int(self.gid.shape[0])
 
+    @property
+    def compressed(self):
+        return self.storage != "float32"
+
+    def _dequantised(self, rows):
+        """Rows as the index holds them, in float32: `rows.to(storage).float()` (both steps exact on representable values)."""
+        dtype = _STORAGES[self.storage][0]
+        return (rows if rows.dtype == dtype else rows.to(dtype)).float()
+
+    @staticmethod
+    def _raise_unrepresentable(bad_row, storage, what):
+        rule = ("a finite value that float16 rounds to an infinity" if storage == "float16"
+                else "a value that is not an integer in [0, 255]")
+        raise ValueError(f"{what} row {bad_row} holds {rule}: it cannot be stored as storage={storage!r} (nothing was changed)")
+
     # ------------------------------------------------------------------ build
+    def _build_index_compressed(self):
+        """`_build_index` with a float16 / uint8 sorted copy and no float32 copy of the corpus: the keys come from encoding the
+        dequantised rows HASH_BATCH at a time (so they are the keys of `S.float()`, not of the caller's un-rounded float32), the typed
+        gather reads the caller's tensor in its own dtype.  Peak extra memory: the sorted copy, the int32 arrays and O(HASH_BATCH) rows."""
+        corpus = self._candidate_vectors_gpu
+        if corpus.device.type != "cuda":
+            raise _capi.NlshHipError(_capi.E_INVALID, "Indexer needs a device-resident corpus; there is no CPU path")
+        L = _capi.lib()
+        N, d = corpus.shape
+        dtype, code, per16 = _STORAGES[self.storage]
+        if corpus.dtype not in _STORE_CODE_OF_DTYPE:
+            corpus = corpus.float()
+        if corpus.stride(1) != 1:
+            corpus = corpus.contiguous()
+        dev = corpus.device
+        if self._given_keys is not None:
+            keys = self._given_keys
+            if keys.shape != (N,) or keys.dtype != torch.int32 or keys.device != dev:
+                raise ValueError("corpus_keys must be int32 [N] on the corpus device")
+            keys = keys.contiguous()
+        elif N <= HASH_BATCH:
+            keys, _ = self.hash_device(self._dequantised(corpus), hash_times=1)
+        else:
+            # One probe per row is the hard key: no draw is made, so the chunks need no seeds of their own.  The first call takes the
+            # hasher's next seed as the float32 build's single call does (the call counter ends where that build leaves it); a BatchNorm
+            # encoder in train mode sees the same HASH_BATCH-row batches `hash_device` would cut.
+            needs_train = getattr(self._hashing, "_needs_train_forward", None)
+            per_batch = needs_train is not None and needs_train()
+            keys = torch.empty((N, 1), dtype=torch.int32, device=dev)
+            for lo in range(0, N, HASH_BATCH):
+                part = self._dequantised(corpus[lo:lo + HASH_BATCH])
+                keys[lo:lo + HASH_BATCH] = self.hash_device(part, hash_times=1, seed=None if (lo == 0 or per_batch) else 0)[0]
+        self.corpus_keys = keys.view(-1)
+        self.perm, self.uniq_keys, self.offsets = build_csr_device(self.corpus_keys)
+        self.n_buckets = int(self.uniq_keys.shape[0])
+        self.dim = d
+        align = max(4, int(self.row_align))
+        align = align * per16 // np.gcd(align, per16)       # elements: a pitch of whole 16-byte units (4 / 8 / 16 elements at the least)
+        self.row_stride = int((d + align - 1) // align * align)
+        self.corpus_sorted = torch.empty((N, self.row_stride), dtype=dtype, device=dev)
+        self.gid = torch.empty((N,), dtype=torch.int32, device=dev)
+        self.inv_norm = torch.empty((N,), dtype=torch.float32, device=dev) if self.metric == "cosine" else None
+        first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
+        _capi.check(L.nlsh_gather_rows_typed(_capi.ptr(corpus), _STORE_CODE_OF_DTYPE[corpus.dtype], corpus.stride(0) if N else d, d,
+                                             _capi.ptr(self.perm), N, _capi.ptr(self.corpus_sorted), code, self.row_stride,
+                                             _capi.ptr(self.inv_norm), _capi.ptr(self.gid), self.id_base, _capi.ptr(first_bad), _stream(dev)))
+        bad = int(first_bad.item())
+        if bad >= 0:
+            self._raise_unrepresentable(bad, self.storage, "corpus")
+        if self.row_ids is not None:
+            if self.row_ids.shape[0] != N or self.row_ids.dtype != torch.int32:
+                raise ValueError("row_ids must be int32 [N]")
+            self.gid = self.row_ids[self.perm.long()].contiguous()
+        self._refresh_bucket_tables()
+
     def _build_index(self):
+        if self.compressed:
+            return self._build_index_compressed()
         corpus = self._candidate_vectors_gpu
         if corpus.device.type != "cuda":
             raise _capi.NlshHipError(_capi.E_INVALID, "Indexer needs a device-resident corpus; there is no CPU path")
@@ -271,7 +361,8 @@ class Indexer:
     # rows in local order -- the constructor's corpus, then every added batch, minus the removed rows -- with `row_ids=` their ids and
     # `corpus_keys=` their keys.  One pass over the sorted corpus (`nlsh_csr_update`), no sort of the old keys.
     def add(self, vectors, ids=None, keys=None) -> torch.Tensor:
-        """Add float32 rows [M, d] (device; strided row views allowed) -> their int32 ids (device).  `ids` (int32 [M], new and distinct)
+        """Add float32 rows [M, d] (device; strided row views allowed; a compressed index also takes rows of its own dtype and refuses
+        float32 values its storage cannot hold with a ValueError, nothing changed) -> their int32 ids (device).  `ids` (int32 [M], new and distinct)
         default to `next_id ..`; an index built with `row_ids=` has no default.  `keys` (int32 [M]) default to the hasher's keys,
         as `corpus_keys=` does in the constructor."""
         return self.update(add=vectors, add_ids=ids, add_keys=keys)[0]
@@ -313,7 +404,7 @@ class Indexer:
             raise ValueError(f"{n_out} rows: the index addresses its rows with int32")
         torch.cuda.synchronize(dev)         # batches in flight (other streams, pipelines) still read the arrays about to be released
         L, stride = _capi.lib(), self.row_stride
-        sorted_out = torch.empty((n_out, stride), dtype=torch.float32, device=dev)
+        sorted_out = torch.empty((n_out, stride), dtype=_STORAGES[self.storage][0], device=dev)
         gid_out = torch.empty((n_out,), dtype=torch.int32, device=dev)
         inv_out = torch.empty((n_out,), dtype=torch.float32, device=dev) if self.metric == "cosine" else None
         src_out = torch.empty((n_out,), dtype=torch.int32, device=dev)
@@ -326,12 +417,29 @@ class Indexer:
             _capi.check(_capi.E_INVALID)
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         keep_u8 = None if keep is None else keep.to(torch.uint8)
-        _capi.check(L.nlsh_csr_update(
-            _capi.ptr(self.corpus_sorted), stride, self.dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
-            _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
-            _capi.ptr(vectors), vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
-            _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
-            _capi.ptr(nb_out), _capi.ptr(ws), ws_bytes, _stream(dev)))
+        if not self.compressed:
+            _capi.check(L.nlsh_csr_update(
+                _capi.ptr(self.corpus_sorted), stride, self.dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
+                _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
+                _capi.ptr(vectors), vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
+                _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
+                _capi.ptr(nb_out), _capi.ptr(ws), ws_bytes, _stream(dev)))
+        else:
+            # kept rows move as bytes; the new rows arrive in the storage's dtype (`_new_rows` has converted and checked float32 ones).  The
+            # call itself also converts -- C callers hand it rows of another storage -- and reports through `first_bad`; out of place, so
+            # a refusal leaves every array of the index the old one
+            code = _STORAGES[self.storage][1]
+            first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
+            _capi.check(L.nlsh_csr_update_typed(
+                _capi.ptr(self.corpus_sorted), code, stride, self.dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
+                _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
+                _capi.ptr(vectors), _STORE_CODE_OF_DTYPE[vectors.dtype] if M else code, vectors.stride(0) if M else self.dim, _capi.ptr(new_keys),
+                _capi.ptr(new_ids), M,
+                _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
+                _capi.ptr(nb_out), _capi.ptr(first_bad), _capi.ptr(ws), ws_bytes, _stream(dev)))
+            bad = int(first_bad.item())
+            if bad >= 0:
+                self._raise_unrepresentable(bad, self.storage, "added")
         n_buckets = int(nb_out.item())
         # the int32 side arrays in LOCAL order, from where every sorted row came from (`src_out`): torch plumbing, 4 bytes per row
         src = src_out.long()
@@ -375,12 +483,26 @@ class Indexer:
             raise ValueError(f"added rows are on {add.device}, the index on {dev}")
         if add.dim() != 2 or add.shape[1] != self.dim:
             raise ValueError(f"added rows must be [M, {self.dim}], got {tuple(add.shape)}")
-        if add.dtype != torch.float32:
-            raise ValueError(f"added rows must be float32, got {add.dtype}")
+        if add.dtype != torch.float32 and not (self.compressed and add.dtype == _STORAGES[self.storage][0]):
+            raise ValueError(f"added rows must be float32{' or ' + self.storage if self.compressed else ''}, got {add.dtype}")
         M = int(add.shape[0])
         if M == 0:
             return None, None, None
         vectors = add if add.stride(1) == 1 else add.contiguous()
+        if self.compressed and vectors.dtype == torch.float32:
+            # float32 rows into a compressed index are converted and checked FIRST (the typed gather with the identity permutation: the
+            # one conversion rule, one device flag): a refusal comes before the hasher is touched, and what is hashed and merged below
+            # is the rows as the index will hold them
+            dtype, code, _ = _STORAGES[self.storage]
+            held = torch.empty((M, self.row_stride), dtype=dtype, device=dev)
+            first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
+            _capi.check(_capi.lib().nlsh_gather_rows_typed(
+                _capi.ptr(vectors), _capi.STORE_F32, vectors.stride(0), self.dim, _capi.ptr(torch.arange(M, dtype=torch.int32, device=dev)), M,
+                _capi.ptr(held), code, self.row_stride, None, None, 0, _capi.ptr(first_bad), _stream(dev)))
+            bad = int(first_bad.item())
+            if bad >= 0:
+                self._raise_unrepresentable(bad, self.storage, "added")
+            vectors = held[:, :self.dim]
         if add_keys is not None:
             keys = add_keys
             if not isinstance(keys, torch.Tensor) or keys.shape != (M,) or keys.dtype != torch.int32 or keys.device != dev:
@@ -391,7 +513,8 @@ class Indexer:
             if needs_train is not None and needs_train():
                 raise _capi.NlshHipError(_capi.E_UNSUPPORTED, "add() needs eval mode for BatchNorm encoders (train_mode(False)): batch statistics "
                                                               "would make a row's key depend on the batch it arrived in; or pass keys=")
-            keys = self.hash_device(vectors, hash_times=1)[0].reshape(-1).contiguous()    # the call `_build_index` makes
+            # the call `_build_index` makes (a compressed index hashes the rows as it will hold them)
+            keys = self.hash_device(self._dequantised(vectors) if self.compressed else vectors, hash_times=1)[0].reshape(-1).contiguous()
         if add_ids is None:
             if self.row_ids is not None:
                 raise ValueError("an index built with row_ids= has no default ids: pass ids=")
@@ -568,6 +691,8 @@ class Indexer:
         batch of a handful of queries still prefers the query-major schedule's shorter PLAN phase (one kernel instead of four).
         The rule depends on the batch shape alone, so every shard count picks the same arithmetic (`schedule_stats` is kept for the
         sharded builds' interface and no longer enters)."""
+        if self.compressed:         # float16 / uint8 rows are read by the tiled schedule only, whatever the batch shape
+            return _capi.SCAN_BUCKET_TILED
         if self.algo is not None:
             return {"query": _capi.SCAN_QUERY_MAJOR, "bucket": _capi.SCAN_BUCKET_MAJOR, "tiled": _capi.SCAN_BUCKET_TILED}[self.algo]
         return _capi.SCAN_BUCKET_TILED if Q * P >= 64 else _capi.SCAN_QUERY_MAJOR
@@ -768,8 +893,13 @@ class Indexer:
         with caller-owned buffers (any subset of the phases)."""
         Q, d = q.shape
         f = self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window)
-        _capi.check(_capi.lib().nlsh_scan_topk_cells_phase(
-            *_SCAN_ARGS_BEFORE_QUERIES(f), q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
+        before = _SCAN_ARGS_BEFORE_QUERIES(f)
+        if self.compressed:         # the typed form of the same call: the storage code follows the corpus pointer
+            call, before = _capi.lib().nlsh_scan_topk_cells_phase_typed, before[:1] + (_STORAGES[self.storage][1],) + before[1:]
+        else:
+            call = _capi.lib().nlsh_scan_topk_cells_phase
+        _capi.check(call(
+            *before, q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
             events[0].cuda_event if events else None, events[1].cuda_event if events else None,
             _stream(q.device) if stream is None else stream, phases))
 
@@ -822,6 +952,8 @@ class Indexer:
         is a bucket-major one (the query-major stream's PLAN phase is a single kernel of its own).  A streamed encoder (hidden layer
         wider than `_capi.MAX_WIDTH`) has no fused encode launch: `hash_device` + `scan_tensors`, the same results by design.  Neither
         has a ranked hasher (`probes="ranked"`): its keys come from `nlsh_probe_ranked` behind the encode."""
+        if self.compressed:         # the step descriptor has no storage field: a compressed index hashes, then calls the typed scan
+            return False
         needs_train = getattr(self._hashing, "_needs_train_forward", None)
         streamed = getattr(self._hashing, "streamed", None)
         if getattr(self._hashing, "probes", "sampled") == "ranked":
@@ -845,7 +977,7 @@ class Indexer:
         None = the hasher's `probes` attribute, which a call's `probes=` sets for its duration), with or without a budget, under the
         conditions of `_fuses`: a device metric, a key table of one scan call, a bucket-major schedule on a non-empty index, a non-empty
         batch, an LDS-resident encoder and no BatchNorm train-mode forward.  Everything else keeps the two-step path."""
-        if not self.ranked_one_call:
+        if self.compressed or not self.ranked_one_call:
             return False
         h = self._hashing
         if ranked is None:
@@ -1377,7 +1509,8 @@ class Indexer:
             rows = torch.cat(chunks) if chunks else torch.zeros((0,), dtype=torch.int64, device=corpus.device)
             n_candidates.append(int(rows.numel()))
             if rows.numel() >= k:
-                dist = self._distance_func(query_vectors[qi], corpus[rows])
+                # a compressed index answers from the rows as it holds them (the caller's corpus may be un-rounded float32)
+                dist = self._distance_func(query_vectors[qi], self._dequantised(corpus[rows]) if self.compressed else corpus[rows])
                 results.append(self._global_ids(rows[dist.topk(k, largest=False)[1]]).tolist())
             elif self.compat:
                 results.append([] if last is None else self._global_ids(last).tolist())

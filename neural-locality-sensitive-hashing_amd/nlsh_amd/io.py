@@ -43,9 +43,11 @@ def read_ivecs(path, max_rows=None) -> np.ndarray:
     return _read_vecs(path, np.int32, max_rows)
 
 
-def read_bvecs(path, max_rows=None) -> np.ndarray:
-    """uint8 components (BIGANN / SIFT1B); returned as float32, the dtype the hot path computes in."""
-    return _read_vecs(path, np.uint8, max_rows).astype(np.float32)
+def read_bvecs(path, max_rows=None, raw=False) -> np.ndarray:
+    """uint8 components (BIGANN / SIFT1B); returned as float32, the dtype the hot path computes in -- or, raw=True, as the uint8 they
+    are on disk, for `Indexer(..., storage="uint8")` (a quarter of the bytes, the same index bit for bit)."""
+    vecs = _read_vecs(path, np.uint8, max_rows)
+    return vecs if raw else vecs.astype(np.float32)
 
 
 def write_vecs(path, array) -> None:

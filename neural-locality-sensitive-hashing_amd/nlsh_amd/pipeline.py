@@ -57,6 +57,9 @@ class QueryPipeline:
         (`nlsh_step_create_graph`): batches overlap because the slots' streams do, and a submit costs the host one graph launch + two
         node updates instead of the staged slots' five launches + eight to ten event calls.  False = the three / four stage streams of
         r03-r05.  None = graph slots whenever the schedule is a bucket-major one (`QueryPipeline.default_graph`)."""
+        if getattr(indexer, "storage", "float32") != "float32":
+            raise NotImplementedError(f"pipelined batches (staged and graph slots) take float32 indexes only, not storage={indexer.storage!r}: "
+                                      "the step descriptor has no storage field")
         streamed = getattr(indexer._hashing, "streamed", None)
         if streamed is not None and streamed():
             raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"pipelined batches take encoders with hidden layers <= {_capi.MAX_WIDTH} wide, "

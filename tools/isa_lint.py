@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ISA lint of the hand-scheduled scan kernels (CPU only: hipcc cross-compiles gfx950 without a GPU).
 
-The tiled scan issues `s_load_dword*` from inline asm (`load_qset`, `warm_query_lines` in csrc/scan_bucket_tiled.h, part of the translation unit scan_bucket.hip).  The
+The tiled scan issues `s_load_dword*` from inline asm (`load_qset`, `warm_query_lines` in csrc/scan_bucket_tiled.h, included by the translation units scan_bucket.hip -- the float32 kernels -- and scan_bucket_typed.hip).  The
 compiler believes their outputs are written when the asm statement ends; the data lands later, at a hand-placed
 `s_waitcnt lgkmcnt(0)`.  That is correct only while nothing reads, copies or reassigns those SGPRs in between -- r02 hit
 exactly this (a throw-away destination was reused, the late write corrupted a live value, the kernel faulted).  This

@@ -1,0 +1,163 @@
+#!/usr/bin/env python3
+"""Corpus storage A/B: the same corpus as a float32, a float16 and a uint8 index, timed in ONE process with the storages
+interleaved round by round -- the scan kernel alone (HIP events around it, `events=`) and the device-resident batch
+(`Indexer.query_tensors`, host clock around `steps` batches ending in a synchronise).  GPU only; reads nothing outside the repository.
+
+Workloads (the generators bench.py uses, the learned hashes of checkpoints/):
+  sift1m    synth.sift_manifold, 10^6 x 128, L2, 16-bit hash.  The generator's rows are integers in [0, 218]: they are indexed RAW, so all
+            three storages hold identical values; the standardisation the hash was trained behind is folded into its first layer.
+  clusters  synth.sift_like (SURVEY 8(d)'s generator), 10^6 x 128, L2, 16-bit hash; raw integers, as above.
+  glove     synth.glove_manifold, 1,183,514 x 100, cosine, 24-bit hash.  Real-valued: float16 holds the rounded rows, float32 holds the SAME
+            rounded rows (dequantised), uint8 does not apply.
+Every storage of a workload gets the same `corpus_keys=` and the same query key table, so the task tables are identical and the results
+are compared bit for bit before anything is timed.
+
+    python tools/storage_bench.py [--workloads sift1m,clusters,glove] [--rounds 7] [--iters 10] [--steps 20] [--out FILE]
+
+Prints one JSON line per workload and a table; `--out` also writes the table to a file (profiles/corpus_storage.txt is made from it).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "neural-locality-sensitive-hashing_amd")):
+    sys.path.insert(0, p)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from nlsh_amd import io, synth  # noqa: E402
+from nlsh_amd.data import Glove, SIFT  # noqa: E402
+from nlsh_amd.indexer import Indexer  # noqa: E402
+
+HBM_PEAK_GBPS = 8000.0      # bench.py's figure (MI355X: 8.0 TB/s spec)
+K, P = 10, 10
+WORKLOADS = {
+    "sift1m": dict(gen="sift_manifold", N=1_000_000, d=128, ckpt="sift1m_manifold_h16.npz", metric="l2", compat=True, storages=("float32", "float16", "uint8")),
+    "clusters": dict(gen="sift_like", N=1_000_000, d=128, ckpt="sift1m_clusters_h16.npz", metric="l2", compat=True, storages=("float32", "float16", "uint8")),
+    "glove": dict(gen="glove_manifold", N=1_183_514, d=100, ckpt="glove_manifold_h24.npz", metric="cosine", compat=False, storages=("float32", "float16")),
+}
+DTYPE = {"float32": torch.float32, "float16": torch.float16, "uint8": torch.uint8}
+
+
+def build(tag, n_rows, Q, dev):
+    """-> ({storage: Indexer}, query batch, key table, (distinct candidate rows, candidates) of the batch)."""
+    w = WORKLOADS[tag]
+    N, d = n_rows or w["N"], w["d"]
+    gen = getattr(synth, w["gen"])
+    corpus_h, queries_h = gen(N, d, seed=synth.SEED_DATA), gen(Q, d, seed=synth.SEED_QUERY)
+    Ws, bs = io.load_hasher_weights(os.path.join(ROOT, "neural-locality-sensitive-hashing_amd", "checkpoints", w["ckpt"]))
+    Ws, bs = [np.asarray(W, np.float32) for W in Ws], [np.asarray(b, np.float32) for b in bs]
+    if w["metric"] == "l2":     # raw integral rows: the hash's standardisation moves into its first layer, W (x - m) / s + b = (W / s) x + (b - (W / s) m)
+        _, mean, std = synth.standardise(corpus_h)
+        Ws[0] = (Ws[0] / std[None, :]).astype(np.float32)
+        bs[0] = (bs[0] - Ws[0] @ mean).astype(np.float32)
+        assert np.array_equal(corpus_h, np.rint(corpus_h)) and corpus_h.min() >= 0 and corpus_h.max() <= 255
+        stored = torch.from_numpy(corpus_h).to(dev)
+    else:                       # real-valued rows: every storage holds the float16-rounded values
+        stored = torch.from_numpy(corpus_h).to(dev).half().float()
+    hashing = io.hashing_from_weights(Ws, bs, compat=w["compat"])
+    dist = SIFT.distance if w["metric"] == "l2" else Glove.distance
+    q = torch.from_numpy(queries_h).to(dev)
+    ixs, keys_of_rows = {}, None
+    for storage in w["storages"]:
+        src = stored if storage == "float32" else stored.to(DTYPE[storage])
+        ix = Indexer(hashing, src, dist, compat=w["compat"], storage=storage, algo="tiled" if storage == "float32" else None, corpus_keys=keys_of_rows)
+        keys_of_rows = ix.corpus_keys
+        ixs[storage] = ix
+        del src
+    keys, nkeys = ixs["float32"].hash_device(q, hash_times=P, seed=7)
+    ref = None
+    for storage, ix in ixs.items():                 # sizes the task tables (checked calls) and holds every storage to the float32 bits
+        out = ix.scan_tensors(q, keys, nkeys, k=K)
+        if ref is None:
+            ref = out
+        assert torch.equal(out[0].view(torch.int32), ref[0].view(torch.int32)) and torch.equal(out[1], ref[1]) and torch.equal(out[2], ref[2]), storage
+        ix.query_tensors(q, k=K, hash_times=P, seed=7)
+    ix = ixs["float32"]
+    pos = torch.searchsorted(ix.uniq_keys, keys.clamp(min=int(ix.uniq_keys[0]), max=int(ix.uniq_keys[-1]))).clamp(max=ix.n_buckets - 1)
+    hit = (ix.uniq_keys[pos] == keys) & (torch.arange(keys.shape[1], device=dev)[None, :] < nkeys[:, None])
+    rows = (ix.offsets[1:] - ix.offsets[:-1]).long()
+    return ixs, q, keys, nkeys, (int(rows[torch.unique(pos[hit])].sum().item()), int(ref[2].long().sum().item()))
+
+
+def time_round(ix, q, keys, nkeys, iters, steps):
+    """(mean scan-kernel ms over `iters` launches, ms per device-resident batch over `steps` batches)."""
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for a, b in evs:            # (`events=` takes events that have been recorded once: the library re-records their handles)
+        a.record(); b.record()
+    for ev in evs:
+        ix.scan_tensors(q, keys, nkeys, k=K, check=False, events=ev)
+    torch.cuda.synchronize()
+    scan_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+    t0 = time.perf_counter()
+    for i in range(steps):
+        ix.query_tensors(q, k=K, hash_times=P, seed=100 + i, check=False)
+    torch.cuda.synchronize()
+    batch_ms = 1e3 * (time.perf_counter() - t0) / steps
+    assert int(ix.last_status.cpu()[1]) == 0, "task table overflow inside a timed region"
+    return scan_ms, batch_ms
+
+
+def spread(xs):
+    xs = sorted(xs)
+    return {"median": float(np.median(xs)), "min": xs[0], "max": xs[-1]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="sift1m,clusters,glove")
+    ap.add_argument("--rows", type=int, default=0, help="rows of every workload (default: its own size)")
+    ap.add_argument("--queries", type=int, default=10_000)
+    ap.add_argument("--rounds", type=int, default=7, help="interleaved rounds (A B C A B C ...): medians and the min..max spread are over the rounds")
+    ap.add_argument("--iters", type=int, default=10, help="scan launches per storage and round")
+    ap.add_argument("--steps", type=int, default=20, help="device-resident batches per storage and round")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("storage_bench needs a GPU: a CPU run says nothing about these times")
+    dev = torch.device("cuda", 0)
+    lines = []
+    for tag in args.workloads.split(","):
+        ixs, q, keys, nkeys, (uniq_rows, sum_c) = build(tag, args.rows, args.queries, dev)
+        d = ixs["float32"].dim
+        for ix in ixs.values():     # warm-up round, untimed
+            time_round(ix, q, keys, nkeys, 3, 3)
+        rounds = {s: [] for s in ixs}
+        for _ in range(args.rounds):
+            for s, ix in ixs.items():
+                rounds[s].append(time_round(ix, q, keys, nkeys, args.iters, args.steps))
+        res = {"workload": tag, "N": int(ixs["float32"].gid.shape[0]), "d": d, "Q": args.queries, "k": K, "hash_times": P, "rounds": args.rounds,
+               "distinct_candidate_rows": uniq_rows, "candidates": sum_c, "n_buckets": ixs["float32"].n_buckets, "storages": {}}
+        base = None
+        for s, ix in ixs.items():
+            scan, batch = spread([r[0] for r in rounds[s]]), spread([r[1] for r in rounds[s]])
+            elem = ix.corpus_sorted.element_size()
+            row_bytes = d * elem                    # the bytes of a row the scan needs (the pitch may pad)
+            base = base or scan["median"]
+            res["storages"][s] = {"index_bytes": int(ix.corpus_sorted.numel() * elem), "row_pitch_bytes": int(ix.row_stride * elem), "scan_ms": scan,
+                                  "batch_ms": batch, "route": ix.last_query_path, "scan_vs_float32": scan["median"] / base,
+                                  "hbm_frac_of_distinct_candidate_rows": uniq_rows * row_bytes / (scan["median"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+        print(json.dumps(res), flush=True)
+        lines.append(f"{tag}: N={res['N']} d={d} Q={args.queries} k={K} hash_times={P}, {res['n_buckets']} buckets, {uniq_rows} distinct candidate rows, "
+                     f"{sum_c} candidates per batch; {args.rounds} interleaved rounds x ({args.iters} scans, {args.steps} batches)")
+        lines.append(f"  {'storage':8} {'index MiB':>10} {'pitch B':>8} {'scan ms median (min..max)':>28} {'x float32':>10} {'HBM frac':>9} "
+                     f"{'ms/batch median (min..max)':>28}  route")
+        for s, r in res["storages"].items():
+            lines.append(f"  {s:8} {r['index_bytes'] / 2 ** 20:10.1f} {r['row_pitch_bytes']:8d} "
+                         f"{r['scan_ms']['median']:10.4f} ({r['scan_ms']['min']:.4f}..{r['scan_ms']['max']:.4f}) {r['scan_vs_float32']:10.3f} "
+                         f"{r['hbm_frac_of_distinct_candidate_rows']:9.3f} {r['batch_ms']['median']:10.4f} ({r['batch_ms']['min']:.4f}..{r['batch_ms']['max']:.4f})  {r['route']}")
+        del ixs, q, keys, nkeys
+        torch.cuda.empty_cache()
+    table = "\n".join(lines)
+    print(table)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(table + "\n")
+
+
+if __name__ == "__main__":
+    main()
