@@ -407,6 +407,54 @@ int nlsh_scan_topk_cells_phase_typed(const void *corpus_sorted, int storage, int
                                      void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases);
 
 /* ---------------------------------------------------------------------------------------------
+ * Filtered queries: a per-call row allow/deny filter inside the tiled scan.  No reference counterpart.
+ *
+ * A row filter is a bitset over the SORTED rows: row_filter [dev, 4-byte aligned] uint32 [2 * ceil(N / 64)] words, bit p & 31 of word
+ * p >> 5 set iff sorted row p -- the row at position p of corpus_sorted / gid -- may be returned; bits at positions >= N are zero;
+ * N = 0 is valid (no words).  Position order, not id order: the scan reads word prow >> 5 with the row position it already has
+ * (coalesced, no load that depends on gid), and ids may be any int32, negative and sparse, so a bitset indexed by id is not an option.
+ * A filter belongs to one state of one index: nlsh_csr_update moves rows, and every filter built before it is meaningless afterwards.
+ *
+ * Definition: the filtered result of a call on an index I with filter F is the result of the same call on the index I_F built from the
+ * allowed rows alone, with the same ids, the same bucket keys and the same query key table.  out_idx, out_dist (bits) and out_keys
+ * equal I_F's in every word, padding (-1, +inf, ~0 behind a list shorter than k) included: a denied row is dropped in front of the
+ * top-k selection, it can never push an allowed row out of a list, and no distance bit changes (a distance is one accumulation chain
+ * along d whatever task the row is scored in).  Two things are counted BEFORE the filter, because the kernels that count do not know
+ * it: out_ncand stays "rows of the probed buckets" -- the work the scan did -- and equals the unfiltered call's value, NOT I_F's; and
+ * nlsh_probe_ranked_budget's candidate budget counts bucket rows, allowed or not.  A filter that allows every row gives the
+ * unfiltered call's outputs in every word, out_ncand included; one that allows nothing gives all-padding lists.
+ *
+ * nlsh_row_filter_words: the number of uint32 words of a filter over n_rows rows, 2 * ceil(n_rows / 64) (host arithmetic only;
+ * 0 and a message for n_rows < 0).
+ *
+ * nlsh_row_filter_build: one wavefront per 64 consecutive sorted rows decides, per lane, whether gid[p] is a member of the source --
+ * EXACTLY ONE of ids [dev] int32 [n_ids], strictly ascending (binary search; n_ids = 0 with a non-null pointer is the empty list), and
+ * dense [dev] uint8 [n_dense], indexed by id - id_base (non-zero = member; ids outside the array are not members) -- and writes the
+ * wave's ballot as two words; allowed = member, or NOT member with invert = 1 (a deny list).  n_allowed [dev] int32 [1] receives the
+ * number of allowed rows (zeroed by the call, then one atomic add per wave).  Every word of the filter is written; nothing else is
+ * read or written.  NLSH_E_INVALID with the argument's name in nlsh_last_error(), before anything is launched, for: n_rows or the
+ * source's size negative, both sources or neither, invert not 0 / 1, a null gid / row_filter with n_rows > 0, a null n_allowed,
+ * a misaligned row_filter / n_allowed.
+ *
+ * nlsh_scan_topk_cells_phase_filtered: nlsh_scan_topk_cells_phase_typed with a row filter behind its last argument.  row_filter NULL is
+ * the typed call, argument for argument.  A non-null filter is read by the tiled schedule only (algo NLSH_SCAN_BUCKET_TILED; every
+ * storage, every metric, k <= NLSH_MAX_K_TILED): the other two schedules answer NLSH_E_UNSUPPORTED and name row_filter; a filter that
+ * is not 4-byte aligned is NLSH_E_INVALID.  The call cannot check the filter's size: it must hold nlsh_row_filter_words of the
+ * index's row count.  Only the SCAN phase reads the filter.  The step, graph-slot and one-call batch entry points take no filter. */
+size_t nlsh_row_filter_words(int64_t n_rows);
+int nlsh_row_filter_build(const int32_t *gid, int64_t n_rows, const int32_t *ids, int64_t n_ids, const uint8_t *dense, int64_t n_dense,
+                          int32_t id_base, int invert, uint32_t *row_filter, int32_t *n_allowed, nlsh_stream_t stream);
+int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
+                                        const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                                        const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                                        const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
+                                        const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows,
+                                        float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand,
+                                        int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
+                                        void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                                        const uint32_t *row_filter);
+
+/* ---------------------------------------------------------------------------------------------
  * One pipelined query batch per call.  Replaces, for a caller that streams batches, the whole body of Indexer.query
  * (nlsh/indexer.py:56-96: hashing.hash on the batch :59 via Indexer.hash :40-54, then the per-query loop :62-95) by ONE
  * enqueue: nlsh_encode_hash + the PLAN, SCAN and MERGE phases of nlsh_scan_topk_cells_phase (five launches since r06: the bucket

@@ -230,7 +230,12 @@ int bucket_scan_run(const BucketScanCall &c) {
         const void *fn;
         dim3 grid, block;
         scan_kernel_of(c, metric, d4, &fn, &grid, &block);
-        void *argv[1] = {&a};
+        const uint32_t *row_filter = c.row_filter;
+        void *argv[2] = {&a, &row_filter};   // the second parameter is the filtered kernels' alone
+        if (row_filter) {   // same grid and block: the filtered kernels are the tiled kernels with one more term in the epilogue
+            NLSH_REQUIRE(c.tiled, NLSH_E_UNSUPPORTED, "scan_topk(bucket-major): row_filter is read by the tiled schedule only");
+            fn = filtered_scan_kernel_of(c.storage, metric, c.k > NLSH_MAX_K);
+        }
         NLSH_CHECK_HIP(hipLaunchKernel(fn, grid, block, argv, 0, s));
         if (c.ev_end) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)c.ev_end, s));
     }

@@ -1,7 +1,8 @@
 // Bucket-major scan, LDS-tiled schedule (included by two translation units behind scan_bucket_args.h, which defines BArgs: scan_bucket.hip
 // instantiates the float32 kernels, scan_bucket_typed.hip the float16 / uint8 ones):
 // the hand-scheduled k-blocks, the task bodies built from them (l2_task*), one task start to finish (tiled_task_body) and the kernels
-// bscan3_kernel (k <= 64) and bscanw_kernel (k up to NLSH_MAX_K_TILED) over a float32 corpus, bscant_kernel over a float16 / uint8 one.
+// bscan3_kernel (k <= 64) and bscanw_kernel (k up to NLSH_MAX_K_TILED) over a float32 corpus, bscant_kernel over a float16 / uint8 one,
+// bscanf_kernel behind a row filter (scan_bucket_filtered.hip instantiates it).
 #pragma once
 
 // Diagnostic build only (make EXTRA=-DNLSH_SCAN_TRACE, tools/scan_trace.py): wave 0 of every bscan3 workgroup
@@ -447,9 +448,14 @@ __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const typena
 // the wave's query ids).  `tile` = the workgroup's LDS stage.
 // WIDEK (compile time): k in 65..NLSH_MAX_K_TILED -- the epilogue's selection pads its k-key list with a lane-strided loop; everything in
 // front of the epilogue is the same code, so every distance keeps its bits.
-template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = NLSH_STORE_F32>
+// FILT (compile time; nlsh_scan_topk_cells_phase_filtered): `row_filter` is a bitset over the sorted rows (bit p & 31 of word p >> 5: row p
+// may be returned).  The lane's word of every tile is requested beside its row id at the top of the task and its bit enters `mine` in
+// the epilogue: a denied row is dropped in front of the selection and changes nothing in staging, in the k-blocks or in a distance.
+// Off (the default), neither the parameter nor the words exist in the code.
+template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = NLSH_STORE_F32, bool FILT = false>
 __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, long long t, const int4 desc, const int2 qr_all, int tid, int lane,
-                                                int wave, [[maybe_unused]] unsigned long long ts_entry) {
+                                                int wave, [[maybe_unused]] unsigned long long ts_entry,
+                                                [[maybe_unused]] const uint32_t *row_filter = nullptr) {
     static_assert(QW == 4 && TPS == 4 && NW == 4, "the hand-scheduled task bodies (l2_task_nt) are written for 4 waves x 4 queries x 4 row tiles");
 #ifdef NLSH_SCAN_TRACE_CLOCK
     const unsigned long long ts0 = SCAN_NOW();
@@ -497,12 +503,14 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
     int32_t mygid[TPS];
     float myinv[TPS];
     bool valid[TPS];
+    [[maybe_unused]] uint32_t myfw[TPS];   // FILT: the filter word that holds the row's bit (lanes past the task's last row: the word of row0, in range)
 #pragma unroll
     for (int tl = 0; tl < TPS; ++tl) {
         valid[tl] = tl * 64 + lane < nrows;
         const int prow = row0 + (valid[tl] ? tl * 64 + lane : 0);
         mygid[tl] = valid[tl] ? a.gid[prow] : -1;
         myinv[tl] = (METRIC == NLSH_METRIC_COSINE && valid[tl]) ? a.inv_norm[prow] : 0.0f;
+        if (FILT) myfw[tl] = row_filter[prow >> 5];
     }
     [[maybe_unused]] unsigned long long trl[3] = {0, 0, 0};
     [[maybe_unused]] const unsigned long long ts_in = SCAN_NOW();
@@ -549,6 +557,8 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
             // LEAN: every accumulator of the list at or above 2^-96 (wave-uniform test; NaN compares false and takes the general path)
             // -> square roots without the range scaling, and a non-negative distance's order-preserving word is its bits with the sign set
             bool lean = LEAN;
+            // (FILT: the test stays over the task's rows, denied ones included, as it already covers the rows of a shared window's other
+            // buckets: it only picks between two correctly rounded square roots, sqrt_rn_unscaled and finish_distance's sqrtf -- same bits)
             if (LEAN) {   // tiles the task does not have hold zeros and lanes past its last row another row's (or nobody's) sums: neither is asked
                 bool ok = true;
 #pragma unroll
@@ -557,7 +567,8 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
             }
 #pragma unroll
             for (int tl = 0; tl < TPS; ++tl) {
-                const bool mine = valid[tl] && (unsigned)(tl * 64 + lane) - r_lo < r_n;
+                bool mine = valid[tl] && (unsigned)(tl * 64 + lane) - r_lo < r_n;
+                if (FILT) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
                 uint64_t kk;
                 if (lean) {
                     const float dist = sqrt_rn_unscaled(acc[tl][jq]);
@@ -703,6 +714,32 @@ __global__ __launch_bounds__(64 * NW, 1) void bscant_kernel(BArgs a) {
     const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
     if (t >= ntasks) return;
     tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry);
+}
+
+// The tiled scan behind a row filter (FILT of tiled_task_body; nlsh_scan_topk_cells_phase_filtered), every storage, k <= 64 (WIDEK false)
+// and k in 65..NLSH_MAX_K_TILED (true).  The filter is a SECOND kernel parameter: BArgs, and with it every kernel above, keeps its
+// layout and its code (profiles/row_filter.txt compares them with the build before the filter existed).  Instantiated in
+// scan_bucket_filtered.hip, a translation unit of its own.  The task pick is bscan3_kernel's, line for line (see the comments there),
+// written out again for the reason given at bscanw_kernel.
+template <int METRIC, int QW, int NW, int TPS, int STORE, bool WIDEK>
+__global__ __launch_bounds__(64 * NW, 1) void bscanf_kernel(BArgs a, const uint32_t *row_filter) {
+    constexpr int RS = NLSH_TILED_KB + 1;
+    __shared__ float4 tile[64 * TPS * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
+    long long ntasks = a.status[0];
+    if (ntasks > a.max_tasks) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
+        ntasks = a.max_tasks;
+    }
+    constexpr int XC = 16;
+    const long long j = blockIdx.x >> 3;
+    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
+    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
+    const int4 desc = a.task[tc];
+    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
+    if (t >= ntasks) return;
+    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, row_filter);
 }
 
 }  // namespace nlsh

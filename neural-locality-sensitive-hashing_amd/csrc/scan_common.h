@@ -431,6 +431,9 @@ struct BucketScanCall {
                                   // (layout: bmerge_host_kernel) instead of out_dist / out_idx / out_ncand; nullptr everywhere else
     int storage;                  // NLSH_STORE_*: what `corpus` really points to (row_stride in elements); anything but F32 is the tiled
                                   // schedule's alone and set by nlsh_scan_topk_cells_phase_typed only (0 = F32 everywhere else)
+    const uint32_t *row_filter;   // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: the tiled schedule's alone, set by
+                                  // nlsh_scan_topk_cells_phase_filtered only; the SCAN phase then launches a filtered kernel, which takes
+                                  // the pointer as a second parameter (BArgs does not hold it)
 };
 // internal phase bit (not part of the C ABI's phase mask): the PLAN phase WITHOUT the bucket lookup, which the batch's encode_hash
 // launch already did in its epilogue (scan_plan.h, encode_plan_fuse_lookup): bscan + bscatter only
@@ -441,6 +444,8 @@ int bucket_scan_run(const BucketScanCall &c);
 int bucket_scan_plan_args(const BucketScanCall &c, PlanArgs *pa);   // the lookup's arguments for this call's workspace
 // the tiled scan kernel over a float16 / uint8 corpus (scan_bucket_typed.hip): storage NLSH_STORE_F16 | NLSH_STORE_U8, wide = k > NLSH_MAX_K
 const void *typed_scan_kernel_of(int storage, int metric, bool wide);
+// the tiled scan kernel behind a row filter (scan_bucket_filtered.hip): any storage; its parameters are (BArgs, const uint32_t *row_filter)
+const void *filtered_scan_kernel_of(int storage, int metric, bool wide);
 
 // nlsh_scan_topk_cells_phase after argument validation, with the internal phase bit allowed; `call_out` (nullable) receives the
 // bucket-major call descriptor instead of running it (step.hip builds the fused lookup's arguments from it)

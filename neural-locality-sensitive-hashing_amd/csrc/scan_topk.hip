@@ -452,6 +452,45 @@ extern "C" int nlsh_scan_topk_cells_phase_typed(const void *corpus_sorted, int s
     return bucket_scan_run(c);
 }
 
+extern "C" int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
+                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
+                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
+                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
+                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                              const uint32_t *row_filter) {
+    if (!row_filter)   // no filter: the typed call, argument for argument
+        return nlsh_scan_topk_cells_phase_typed(corpus_sorted, storage, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of,
+                                                cell_offsets, n_cells, inv_norm, queries, q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows,
+                                                out_dist, out_idx, out_keys, out_ncand, status, workspace, workspace_bytes, max_tasks,
+                                                ev_scan_begin, ev_scan_end, stream, phases);
+    NLSH_REQUIRE(storage == NLSH_STORE_F32 || storage == NLSH_STORE_F16 || storage == NLSH_STORE_U8, NLSH_E_INVALID,
+                 "scan_topk_filtered: storage=%d is none of NLSH_STORE_F32 / F16 / U8", storage);
+    NLSH_REQUIRE(phases >= 1 && phases <= (NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE), NLSH_E_INVALID, "scan_topk_filtered: phases=%d", phases);
+    NLSH_REQUIRE(algo == NLSH_SCAN_QUERY_MAJOR || algo == NLSH_SCAN_BUCKET_MAJOR || algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_INVALID,
+                 "scan_topk_filtered: algo=%d", algo);
+    NLSH_REQUIRE(algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_UNSUPPORTED,
+                 "scan_topk_filtered: row_filter is read by the tiled schedule only (NLSH_SCAN_BUCKET_TILED), not by algo=%d", algo);
+    NLSH_REQUIRE(((uintptr_t)row_filter & 3) == 0, NLSH_E_INVALID, "scan_topk_filtered: row_filter must be 4-byte aligned");
+    if (storage != NLSH_STORE_F32) {   // the typed call's checks of a compressed copy (the float32 pitch is held against d and 4 below)
+        const int per16 = storage == NLSH_STORE_F16 ? 8 : 16;
+        NLSH_REQUIRE(row_stride >= d && row_stride % per16 == 0, NLSH_E_INVALID,
+                     "scan_topk_filtered: row_stride=%lld must be >= d=%d and a multiple of %d elements (a pitch of 16-byte units) for storage=%d",
+                     (long long)row_stride, d, per16, storage);
+        NLSH_REQUIRE(((uintptr_t)corpus_sorted & 15) == 0, NLSH_E_INVALID, "scan_topk_filtered: corpus_sorted must be 16-byte aligned");
+    }
+    BucketScanCall c;
+    const int rc = nlsh::scan_topk_cells_phase_checked((const float *)corpus_sorted, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of,
+                                                       cell_offsets, n_cells, inv_norm, queries, q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows,
+                                                       out_dist, out_idx, out_keys, out_ncand, status, workspace, workspace_bytes, max_tasks,
+                                                       ev_scan_begin, ev_scan_end, stream, phases, 0, &c);
+    if (rc != NLSH_OK || Q == 0) return rc;
+    c.storage = storage;
+    c.row_filter = row_filter;
+    return bucket_scan_run(c);
+}
+
 extern "C" int nlsh_scan_topk_phase(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid,
                               const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
                               const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,

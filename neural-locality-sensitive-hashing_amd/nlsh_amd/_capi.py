@@ -42,6 +42,7 @@ SYMBOLS = (
     "nlsh_query_batch_ranked_scratch", "nlsh_query_batch_ranked",
     "nlsh_csr_update_workspace", "nlsh_csr_update",
     "nlsh_scan_topk_cells_phase_typed", "nlsh_gather_rows_typed", "nlsh_csr_update_typed",
+    "nlsh_row_filter_words", "nlsh_row_filter_build", "nlsh_scan_topk_cells_phase_filtered",
 )
 
 
@@ -147,6 +148,12 @@ def lib():
     L.nlsh_scan_topk_cells_phase.argtypes = L.nlsh_scan_topk_phase.argtypes[:8] + [vp, vp, ctypes.c_int32] + L.nlsh_scan_topk_phase.argtypes[8:]
     L.nlsh_scan_topk_cells_phase_typed.restype = i32     # storage follows corpus_sorted
     L.nlsh_scan_topk_cells_phase_typed.argtypes = L.nlsh_scan_topk_cells_phase.argtypes[:1] + [i32] + L.nlsh_scan_topk_cells_phase.argtypes[1:]
+    L.nlsh_scan_topk_cells_phase_filtered.restype = i32     # the typed call, row_filter behind phases
+    L.nlsh_scan_topk_cells_phase_filtered.argtypes = L.nlsh_scan_topk_cells_phase_typed.argtypes + [vp]
+    L.nlsh_row_filter_words.restype = sz
+    L.nlsh_row_filter_words.argtypes = [i64]
+    L.nlsh_row_filter_build.restype = i32      # gid, n_rows | ids, n_ids | dense, n_dense, id_base | invert | row_filter, n_allowed, stream
+    L.nlsh_row_filter_build.argtypes = [vp, i64, vp, i64, vp, i64, ctypes.c_int32, i32, vp, vp, vp]
     L.nlsh_merge_topk.restype = i32
     L.nlsh_merge_topk.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, vp, vp]
     L.nlsh_step_create.restype = i32

@@ -17,6 +17,7 @@ import gc
 import numbers
 import operator
 import threading
+import weakref
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
@@ -163,6 +164,32 @@ def build_index(indexes, cuda=True) -> Dict[int, torch.Tensor]:
 # `storage=`: element type of the bucket-sorted corpus copy -> (torch dtype, NLSH_STORE_* code, elements per 16 bytes)
 _STORAGES = {"float32": (torch.float32, _capi.STORE_F32, 4), "float16": (torch.float16, _capi.STORE_F16, 8), "uint8": (torch.uint8, _capi.STORE_U8, 16)}
 _STORE_CODE_OF_DTYPE = {dt: code for dt, code, _ in _STORAGES.values()}
+
+
+class RowFilter:
+    """A row allow/deny filter of ONE index in ONE generation (`Indexer.row_filter` builds it): `words`, the device
+    bitset over the index's bucket-sorted rows (int32 tensor holding the uint32 words of include/nlsh_hip.h: bit p & 31 of word p >> 5
+    = sorted row p may be returned), `n_allowed`, how many rows it allows, and `generation`, the index's when it was built.  Reusable
+    across calls (`filter=`); stale after an effective `add` / `remove` / `update`, which move rows: build a new one."""
+
+    __slots__ = ("words", "n_allowed", "generation", "_index")
+
+    def __init__(self, index, words, n_allowed, generation):
+        self.words, self.n_allowed, self.generation = words, int(n_allowed), int(generation)
+        self._index = weakref.ref(index)
+
+    def __repr__(self):
+        return f"RowFilter(n_allowed={self.n_allowed}, generation={self.generation})"
+
+
+def pack_row_filter(allowed) -> np.ndarray:
+    """Host statement of the filter layout: bool [N] in sorted-row order -> uint32 [2 * ceil(N / 64)] words (what
+    `nlsh_row_filter_build` writes on the device; the tests hold one against the other)."""
+    allowed = np.asarray(allowed, dtype=bool).reshape(-1)
+    n_words = 2 * ((allowed.shape[0] + 63) // 64)
+    bits = np.zeros((n_words * 32,), dtype=np.uint8)
+    bits[:allowed.shape[0]] = allowed
+    return np.packbits(bits.reshape(n_words, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
 
 
 class Indexer:
@@ -549,6 +576,76 @@ class Indexer:
         for name in ("_range_plans", "_ranked_key_tables", "_key_tables", "_held", "_bucket_dir"):
             self.__dict__.pop(name, None)
 
+    # ------------------------------------------------------------------ row filters
+    def row_filter(self, allow=None, deny=None, mask=None) -> RowFilter:
+        """A per-call row filter of this index (`filter=` of `scan_tensors` / `query_tensors` / `query_with_keys` / `query`): EXACTLY ONE
+        of `allow` (only rows with these ids may be returned), `deny` (every row but these) and `mask` (a bool or uint8 DEVICE tensor
+        indexed by `id - id_base`, non-zero = allowed; ids outside it are denied).  `allow` / `deny` hold integer ids, as a tensor or a
+        sequence; unknown ids are ignored and duplicates count once, as in `remove` (they are sorted and de-duplicated here).  The
+        bitset is built on the device (`nlsh_row_filter_build`, one pass over the row ids); the call synchronises to read
+        `n_allowed`.  The filter is this index's, in this `generation`: after an effective `add` / `remove` / `update` it is stale
+        and a call that is given it raises ValueError -- build a new one."""
+        if (allow is not None) + (deny is not None) + (mask is not None) != 1:
+            raise ValueError("row_filter takes exactly one of allow=, deny= and mask=")
+        if self.metric not in ("l2", "cosine"):
+            raise NotImplementedError("row filters need metric 'l2' or 'cosine': the filter is read by the tiled scan kernel")
+        ids = None
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1:
+                raise ValueError("mask must be a 1-d bool or uint8 tensor indexed by id - id_base")
+            if mask.device.type != "cuda":
+                raise _capi.NlshHipError(_capi.E_INVALID, "mask must be device-resident; there is no CPU path")
+        else:
+            given = allow if allow is not None else deny
+            name = "allow" if allow is not None else "deny"
+            if isinstance(given, torch.Tensor):
+                ids = given
+                if ids.numel() and (ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool):
+                    raise ValueError(f"{name} must hold integer ids")
+            else:
+                arr = np.asarray(list(given))
+                if arr.size and arr.dtype.kind not in "iu":
+                    raise ValueError(f"{name} must hold integer ids")
+                ids = torch.as_tensor(arr.astype(np.int64).reshape(-1))
+        dev, N = self.gid.device, int(self.gid.shape[0])
+        L = _capi.lib()
+        words = torch.empty((L.nlsh_row_filter_words(N),), dtype=torch.int32, device=dev)
+        n_allowed = torch.empty((1,), dtype=torch.int32, device=dev)
+        if ids is not None:
+            ids = ids.to(dev).reshape(-1).long()
+            ids = torch.unique(ids[(ids >= -(1 << 31)) & (ids <= 0x7FFFFFFF)]).to(torch.int32)      # ascending, distinct; no row has an id outside int32
+            src = ids if ids.numel() else torch.zeros((1,), dtype=torch.int32, device=dev)          # the empty list still names its source
+            args = (src.data_ptr(), int(ids.numel()), None, 0, 0)
+        else:
+            if mask.device != dev:
+                raise ValueError(f"mask is on {mask.device}, the index on {dev}")
+            src = mask.contiguous().view(torch.uint8)
+            n_dense = int(src.numel())
+            if n_dense == 0:
+                src = torch.zeros((1,), dtype=torch.uint8, device=dev)
+            args = (None, 0, src.data_ptr(), n_dense, self.id_base)
+        _capi.check(L.nlsh_row_filter_build(self.gid.data_ptr() if N else None, N, *args, int(deny is not None),
+                                            words.data_ptr() if N else None, n_allowed.data_ptr(), _stream(dev)))
+        return RowFilter(self, words, int(n_allowed.item()), self.generation)
+
+    def _checked_filter(self, filter, algo=None):
+        """`filter=` of a call, checked before anything is launched -> the RowFilter or None."""
+        if filter is None:
+            return None
+        if not isinstance(filter, RowFilter):
+            raise ValueError(f"filter must be None or a RowFilter built by this index's row_filter(), got {type(filter).__name__}")
+        if filter._index() is not self:
+            raise ValueError("filter was built by another index: a RowFilter addresses the sorted rows of the index that built it")
+        if filter.generation != self.generation:
+            raise ValueError(f"stale filter: built at generation {filter.generation}, the index is at {self.generation} "
+                             "(add / remove / update move rows); build a new one with row_filter()")
+        if self.metric not in ("l2", "cosine"):
+            raise NotImplementedError("filter= needs metric 'l2' or 'cosine': the filter is read by the tiled scan kernel")
+        if self.algo in ("query", "bucket") or algo in (_capi.SCAN_QUERY_MAJOR, _capi.SCAN_BUCKET_MAJOR):
+            raise ValueError("a filtered call is scanned by the tiled schedule only: algo='query' / 'bucket' cannot read a row filter "
+                             "(algo=None or 'tiled')")
+        return filter
+
     @property
     def index2row(self) -> Dict[int, torch.Tensor]:
         """Reference attribute (indexer.py:38; read by trainers/base.py:87-89): materialised lazily
@@ -787,8 +884,13 @@ class Indexer:
         self.last_algo, self.last_window = algo, window
         self._last_pack, self._last_tkey, self._last_max_tasks = pack, tkey, max_tasks
 
-    def scan_tensors(self, query_vectors, keys, nkeys, k=10, want_keys=False, check=True, events=None, algo=None):
-        """Scan stage on a device key table -> (dist [Q,k], idx [Q,k], ncand [Q], keys64 | None)."""
+    def scan_tensors(self, query_vectors, keys, nkeys, k=10, want_keys=False, check=True, events=None, algo=None, filter=None):
+        """Scan stage on a device key table -> (dist [Q,k], idx [Q,k], ncand [Q], keys64 | None).
+        filter (a `RowFilter` of this index, `row_filter()`; None = off): the result is, word for word, that of the index built from the
+        allowed rows alone (same ids, same bucket keys, same key table) -- ids, distance bits and keys64, with -1 / +inf / ~0 behind a
+        list shorter than k.  `ncand` stays the rows of the probed buckets, counted BEFORE the filter: the work the scan did, equal to
+        the unfiltered call's.  A filtered call takes the tiled schedule whatever the batch shape, as a compressed index does."""
+        filter = self._checked_filter(filter, algo)
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("fused scan needs metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
         q = self._as_queries(query_vectors)
@@ -797,12 +899,14 @@ class Indexer:
             raise ValueError(f"query dim {d} != corpus dim {self.dim}")
         dev = q.device
         if keys.shape[1] > _capi.MAX_PROBES:
-            return self._scan_sliced(q, keys, nkeys, k, want_keys, check)
+            return self._scan_sliced(q, keys, nkeys, k, want_keys, check, filter)
         keys = keys.contiguous()
         nkeys = nkeys.contiguous()
         P = keys.shape[1]
         out_dist, pack, out_idx, ncand, status, out_keys = self._outputs(Q, k, dev, want_keys)
-        if algo is None:
+        if filter is not None:
+            algo = _capi.SCAN_BUCKET_TILED
+        elif algo is None:
             algo = self.choose_algo(Q, P)
         stream = _stream(dev)
         while True:
@@ -811,7 +915,7 @@ class Indexer:
                                        _capi.lib().nlsh_scan_workspace(Q, P, k, max_tasks, self.n_buckets, d))
             try:
                 self._scan_launch(q, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws,
-                                  _capi.PHASE_ALL, events, window, stream)
+                                  _capi.PHASE_ALL, events, window, stream, filter)
             except _capi.NlshHipError:
                 self._ws.pop(wkey, None)    # a call that failed part-way may have left the counters at the head non-zero
                 raise
@@ -888,22 +992,26 @@ class Indexer:
                               n_multi_rows=int(n_multi_rows), hold_done=int(hold_done), front=front, plan=plan, mid=mid, tail=tail, **fields)
 
     def _scan_launch(self, q, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, phases, events=None,
-                     window=None, stream=None):
+                     window=None, stream=None, filter=None):
         """One `nlsh_scan_topk_cells_phase` call on the current stream (`stream`: its handle, when the caller has already looked it up)
-        with caller-owned buffers (any subset of the phases)."""
+        with caller-owned buffers (any subset of the phases).  `filter` (a checked RowFilter): the filtered form of the call."""
         Q, d = q.shape
         f = self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window)
         before = _SCAN_ARGS_BEFORE_QUERIES(f)
-        if self.compressed:         # the typed form of the same call: the storage code follows the corpus pointer
+        tail = ()
+        if filter is not None:      # the typed call's arguments for every storage, the filter's words behind them
+            call, before = _capi.lib().nlsh_scan_topk_cells_phase_filtered, before[:1] + (_STORAGES[self.storage][1],) + before[1:]
+            tail = (filter.words.data_ptr(),)
+        elif self.compressed:       # the typed form of the same call: the storage code follows the corpus pointer
             call, before = _capi.lib().nlsh_scan_topk_cells_phase_typed, before[:1] + (_STORAGES[self.storage][1],) + before[1:]
         else:
             call = _capi.lib().nlsh_scan_topk_cells_phase
         _capi.check(call(
             *before, q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
             events[0].cuda_event if events else None, events[1].cuda_event if events else None,
-            _stream(q.device) if stream is None else stream, phases))
+            _stream(q.device) if stream is None else stream, phases, *tail))
 
-    def _scan_sliced(self, q, keys, nkeys, k, want_keys, check):
+    def _scan_sliced(self, q, keys, nkeys, k, want_keys, check, filter=None):
         """hash_times > 64 (eval.py:148 sweeps n_samples up to 100): the key table is scanned in column slices of
         64.  A row's keys are distinct (encode_hash de-duplicates across all probes) and buckets are disjoint (F9),
         so the slices see disjoint candidates: merging their top-k lists with the (distance, id) comparator and
@@ -913,7 +1021,7 @@ class Indexer:
         for c0 in range(0, keys.shape[1], _capi.MAX_PROBES):
             kc = keys[:, c0:c0 + _capi.MAX_PROBES].contiguous()
             nk = (nkeys - c0).clamp(0, kc.shape[1]).to(torch.int32)
-            _, _, nc, k64 = self.scan_tensors(q, kc, nk, k=k, want_keys=True, check=check)
+            _, _, nc, k64 = self.scan_tensors(q, kc, nk, k=k, want_keys=True, check=check, filter=filter)
             parts.append(k64)
             counts.append(nc)
         packed = torch.cat([torch.stack(parts), torch.stack(counts).long()[:, :, None]], dim=2)
@@ -922,16 +1030,26 @@ class Indexer:
         if want_keys:   # the 64-bit sort keys of the merged lists: monotone(dist) << 32 | id, ~0 for padding
             bits = dist.view(torch.int32).long() & 0xFFFFFFFF
             mono = torch.where(bits >= (1 << 31), (~bits) & 0xFFFFFFFF, bits | (1 << 31))
-            keys64 = torch.where(idx < 0, torch.full_like(mono, -1), (mono << 32) | (idx.long() & 0xFFFFFFFF))
+            # padding is (-1, +inf) -- not `idx < 0`: negative ids, -1 among them, are legal row ids (a filtered `query()` takes its list
+            # lengths from these keys); for ids >= 0 the two tests agree
+            pad = (idx == -1) & (dist == float("inf"))
+            keys64 = torch.where(pad, torch.full_like(mono, -1), (mono << 32) | (idx.long() & 0xFFFFFFFF))
         return dist, idx, ncand, keys64
 
     def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None, probes=None,
-                      candidate_budget=None):
+                      candidate_budget=None, filter=None):
         """Device-resident form of `query`: hashing + scan, nothing copied to the host.
         events = (begin, end) torch.cuda.Event pair (already recorded once) bracketing the scan kernel.
         probes ("sampled" | "ranked", None = the hasher's `probes` attribute): the multi-probe mode of this call.
         candidate_budget (ranked mode only; None = off): a query probes its ranked keys until their buckets hold that many candidates,
-        `hash_times` keys at the most."""
+        `hash_times` keys at the most.
+        filter (a `RowFilter` of this index; None = off): see `scan_tensors`.  A filtered call takes the two-step route (hash, then the
+        filtered tiled scan; `last_query_path == "two_step"`), never the fused or the ranked one-call route.  The candidate counts and
+        `candidate_budget` count bucket rows BEFORE the filter: the probe kernel does not know it."""
+        filter = self._checked_filter(filter)
+        if filter is not None:
+            keys, nkeys = self._filtered_keys(query_vectors, hash_times, seed, probes, candidate_budget)
+            return self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events, filter=filter)
         if candidate_budget is not None:
             budget = self._candidate_budget(candidate_budget, probes)
             q = self._as_queries(query_vectors)
@@ -945,6 +1063,27 @@ class Indexer:
             return self._batch_tensors(query_vectors, k, hash_times, seed, want_keys=want_keys, check=check, events=events)[:4]
         with self._probe_mode(probes):
             return self._batch_tensors(query_vectors, k, hash_times, seed, want_keys=want_keys, check=check, events=events)[:4]
+
+    def _filtered_keys(self, query_vectors, hash_times, seed, probes, candidate_budget):
+        """The key table of a filtered call: always the two-step route's first step, whatever the probe mode."""
+        if hash_times < 1:
+            raise ValueError(f"`n` should be positive integer, but got {hash_times}")
+        self.last_query_path = "two_step"
+        q = self._as_queries(query_vectors)
+        if candidate_budget is not None:
+            return self._hash_budget(q, HASH_BATCH, hash_times, self._candidate_budget(candidate_budget, probes))[:2]
+        return self.hash_device(q, hash_times=hash_times, seed=seed, probes=probes)
+
+    def _filtered_lists(self, idx, ncand, keys64):
+        """Device results of a filtered call -> (lists, candidate counts).  A list's length comes from its sort keys (~0 = padding), not
+        from `idx >= 0`: -1 is a legal row id."""
+        idx_h, nc_h = idx.cpu().numpy(), ncand.cpu().numpy()
+        lens = (keys64 != -1).sum(dim=1).cpu().numpy()
+        rows, counts = self._plain_lists(np.ascontiguousarray(idx_h), nc_h)
+        k = idx_h.shape[1] if idx_h.ndim == 2 else 0
+        for qi in np.nonzero(lens < k)[0].tolist():
+            rows[qi] = rows[qi][:int(lens[qi])]
+        return rows, counts
 
     def _fuses(self, q, hash_times, algo):
         """One `nlsh_query_batch` call (ABI v4: five launches, the bucket lookup in the encode's epilogue) serves a batch when the
@@ -1385,11 +1524,23 @@ class Indexer:
     # of two threads and the nested pause of `_plain_lists` leave the collector as the FIRST of them found it (r06).
     pause_collector_for_call = True
 
-    def query(self, query_vectors, k=10, hash_times=10, seed=None, probes=None, candidate_budget=None) -> Tuple[List[List[int]], List[int]]:
+    def query(self, query_vectors, k=10, hash_times=10, seed=None, probes=None, candidate_budget=None,
+              filter=None) -> Tuple[List[List[int]], List[int]]:
         """nlsh/indexer.py:56-96.  `seed` (not in the reference): the Philox seed of the multi-probe draws; None takes the next one
         from the hasher's call counter, like every other hashing call.  `probes` (not in the reference): "sampled" | "ranked", the
         multi-probe mode of this call; None = the hasher's `probes` attribute.  `candidate_budget` (not in the reference; ranked mode
-        only, None = off): a query probes its ranked keys until their buckets hold that many candidates, `hash_times` keys at the most."""
+        only, None = off): a query probes its ranked keys until their buckets hold that many candidates, `hash_times` keys at the most.
+        `filter` (not in the reference; a `RowFilter` of this index, `row_filter()`; None = off): every list holds allowed ids only, in
+        (distance, id) order, min(k, allowed candidates) of them -- what the index over the allowed rows alone returns with
+        compat=False.  The reference's "fewer than k candidates -> rows of the last key" rule (F7) describes an unfiltered query and is
+        NOT applied to a filtered one, whatever `compat` says.  The candidate counts (and `candidate_budget`) count the rows of the
+        probed buckets BEFORE the filter.  Tiled schedule, two-step route (`last_query_path == "two_step"`)."""
+        filter = self._checked_filter(filter)
+        if filter is not None:
+            with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
+                keys, nkeys = self._filtered_keys(query_vectors, hash_times, seed, probes, candidate_budget)
+                _, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter)
+                return self._keep(self._filtered_lists(idx, ncand, keys64))
         if candidate_budget is not None:
             budget = self._candidate_budget(candidate_budget, probes)
             with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
@@ -1468,9 +1619,11 @@ class Indexer:
             q = q.float().contiguous()
         return q
 
-    def query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], k=10):
+    def query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], k=10, filter=None):
         """Scan stage on caller-supplied key lists (each in the iteration order the caller saw):
-        parity on identical candidate sets, independent of hashing."""
+        parity on identical candidate sets, independent of hashing.  `filter`: as in `query` (allowed ids only, list lengths
+        from the sort keys, no F7 rule, candidate counts before the filter)."""
+        filter = self._checked_filter(filter)
         # a query's keys are a set (nlsh/utils.pyx:27-31): a repeated key probes its bucket once; first-occurrence order kept
         key_lists = [list(dict.fromkeys(int(key) for key in ks)) for ks in key_lists]
         Q = len(key_lists)
@@ -1484,6 +1637,9 @@ class Indexer:
         dev = query_vectors.device
         keys = torch.as_tensor(tab).to(dev)
         nkeys = torch.as_tensor(cnt).to(dev)
+        if filter is not None:
+            dist, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter)
+            return self._filtered_lists(idx, ncand, keys64) + (dist, idx)
         dist, idx, ncand, _ = self.scan_tensors(query_vectors, keys, nkeys, k=k)
         res, nc = self._to_lists(key_lists, idx.cpu().numpy(), ncand.cpu().numpy(), k)
         return res, nc, dist, idx
