@@ -577,6 +577,27 @@ int nlsh_step_busy(nlsh_step_t *step);
 int nlsh_merge_topk(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,
                     float *out_dist, int32_t *out_idx, int32_t *out_ncand, nlsh_stream_t stream);
 
+/* The merge of a MULTI-TABLE index: G lists per query, one per hash table over the same corpus, so the same row may
+ * sit in several lists.  nlsh_merge_topk's arguments and output conventions, with out_keys (nullable) in front of out_ncand.
+ *   Input: keys_in [dev] [G, Q, row_stride] u64 (8-byte aligned); the first k of each row are one table's list as the scan's out_keys
+ *         gives it: ascending, ~0-padded, its real keys distinct WITHIN the list.
+ *   De-duplication: equal 64-bit keys in different lists are ONE candidate and appear once in the output.  Padding (~0) is never a
+ *         candidate.  Repeats are dropped BEFORE the k best are selected: the output is short only when fewer than k distinct keys exist.
+ *   Precondition, NOT checked: an id carries the same distance word in every list (true of the tiled schedule's lists over one
+ *         corpus: the distance of a (query, row) pair is a function of the two vectors alone).  Two keys with one id and different
+ *         distance words are different keys: both stay, and the id appears twice.
+ *   Output: the k smallest distinct keys in ascending (distance bits, id) order -- out_dist [Q, k], out_idx [Q, k], out_keys [Q, k]
+ *         (nullable) -- the tail padded as the scan pads it: id -1, dist +inf, key ~0.
+ *   Candidate count: out_ncand [Q] (nullable) = the SUM over the lists -- scored (query, row) pairs, a row found by two tables counts
+ *         twice -- taken as nlsh_merge_topk takes it: from ncand_in [G, Q], or from element k of every row when ncand_in is NULL and
+ *         row_stride > k, or not at all (out_ncand untouched).
+ *   On disjoint input (no key repeated across lists) every output word equals nlsh_merge_topk's.
+ * Limits: 1 <= k <= NLSH_MAX_K_TILED and 1 <= G <= NLSH_MAX_TABLES (beyond either: NLSH_E_UNSUPPORTED), row_stride >= k, any Q; Q = 0 is
+ * NLSH_OK without a launch.  All arguments are checked on the host before anything touches the device.  No workspace, no atomics. */
+#define NLSH_MAX_TABLES 16
+int nlsh_merge_topk_unique(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,
+                           float *out_dist, int32_t *out_idx, uint64_t *out_keys /* nullable */, int32_t *out_ncand, nlsh_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Exact brute-force k-NN: every row of `corpus` against every query, fp32-MFMA distances with the top-k fused behind them.
  * Replaces the reference's mm + topk precompute (precompute.py:22-67): ground truth of a query set, self-kNN of a training set.

@@ -19,6 +19,7 @@ SCAN_QUERY_MAJOR, SCAN_BUCKET_MAJOR, SCAN_BUCKET_TILED = 0, 1, 2
 STORE_F32, STORE_F16, STORE_U8 = 0, 1, 2   # NLSH_STORE_*: element type of a bucket-sorted corpus copy (the *_typed entry points)
 MAX_LAYERS, MAX_HASH_BITS, MAX_PROBES, MAX_K, MAX_DIM, MAX_WIDTH = 8, 32, 64, 64, 1024, 632
 MAX_K_TILED = 256  # k of the tiled schedule and of nlsh_merge_topk (NLSH_MAX_K_TILED); MAX_K is what every schedule takes
+MAX_TABLES = 16    # lists per query of nlsh_merge_topk_unique = hash tables of a MultiTableIndexer (NLSH_MAX_TABLES)
 PHASE_PLAN, PHASE_SCAN, PHASE_MERGE = 1, 2, 4
 PHASE_ALL = 7
 MAX_ENCODE_PROBES = 128  # nlsh_encode_hash generates up to this many keys per row; the scan takes them in slices of MAX_PROBES
@@ -43,6 +44,7 @@ SYMBOLS = (
     "nlsh_csr_update_workspace", "nlsh_csr_update",
     "nlsh_scan_topk_cells_phase_typed", "nlsh_gather_rows_typed", "nlsh_csr_update_typed",
     "nlsh_row_filter_words", "nlsh_row_filter_build", "nlsh_scan_topk_cells_phase_filtered",
+    "nlsh_merge_topk_unique",
 )
 
 
@@ -156,6 +158,8 @@ def lib():
     L.nlsh_row_filter_build.argtypes = [vp, i64, vp, i64, vp, i64, ctypes.c_int32, i32, vp, vp, vp]
     L.nlsh_merge_topk.restype = i32
     L.nlsh_merge_topk.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, vp, vp]
+    L.nlsh_merge_topk_unique.restype = i32     # nlsh_merge_topk with out_keys in front of out_ncand
+    L.nlsh_merge_topk_unique.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp]
     L.nlsh_step_create.restype = i32
     L.nlsh_step_create.argtypes = [ctypes.POINTER(StepDesc), sz, ctypes.POINTER(vp)]
     L.nlsh_step_create_graph.restype = i32
