@@ -455,6 +455,61 @@ int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, int storage, 
                                         const uint32_t *row_filter);
 
 /* ---------------------------------------------------------------------------------------------
+ * Radius (range) queries: every candidate within radius[q] of query q, from the tiled scan.  No reference counterpart.
+ *
+ * Definition: the candidates of query q are the rows of the buckets of its keys (unknown keys: empty buckets), subject to row_filter
+ * when one is given (the rule of the filtered call: the index built from the allowed rows alone).  A candidate's distance is the one
+ * nlsh_scan_topk_cells_phase computes for that (query, row), bit for bit: one accumulation chain along d, whatever task scores the row.
+ * It is in range iff dist <= radius[q] as an IEEE float32 comparison -- a NaN distance never is, not even at radius +inf; a +inf
+ * distance only at radius +inf; a negative radius on L2 returns nothing.  The result of a query is every in-range candidate, once,
+ * ascending by the 64-bit sort key mono(dist) << 32 | id: the (distance, row id) order of every top-k call.  out_ncand[q] is the top-k
+ * call's: the rows of the probed buckets, counted before the radius and before the filter.
+ *
+ * The length of the output is not known before the scan has run, and the caller allocates everything: two calls, one host read between.
+ *
+ *   nlsh_range_count   index, query and key-table arguments of nlsh_scan_topk_cells_phase_filtered (no k, no out_* lists), then
+ *                      row_filter [dev] (NULL = off), radius [dev] float [Q], out_count [dev] int32 [Q] (zeroed by the call; on return
+ *                      the in-range candidates of every query), out_ncand [dev] int32 [Q], status, workspace, max_tasks, the two optional events
+ *                      of the top-k calls (recorded around the scan launch alone), stream.
+ *                      Runs the PLAN phase, sized as for k = 1 (nlsh_range_workspace), and one scan launch in count mode.  status is the
+ *                      top-k call's: status[0] tasks needed; status[1] 1 = task table too small, the counts are incomplete, repeat with
+ *                      max_tasks >= status[0]; 2 / 3 as in nlsh_scan_topk_cells_phase.
+ *   (caller)           total = sum of the counts, row_offsets [dev] int64 [Q + 1] = their exclusive prefix sum (row_offsets[Q] = total).
+ *   nlsh_range_fill    the same arguments, then row_offsets, total, cursor [dev] int32 [Q] (zeroed by the call; on return equal to the
+ *                      counts), out_keys [dev] uint64 [total] (NULL = not wanted), out_dist [dev] float [total] (NULL = not wanted),
+ *                      out_idx [dev] int32 [total], status, workspace, max_tasks, sort_workspace (nlsh_range_sort_workspace), events, stream.
+ *                      Runs one scan launch in fill mode ON THE PLAN THE COUNT CALL LEFT IN `workspace` -- same workspace, same
+ *                      max_tasks, same key table, radius and filter; nothing else may use that workspace in between --, sorts every
+ *                      query's segment [row_offsets[q], row_offsets[q + 1]) by key (rocPRIM segmented radix sort) and unpacks the
+ *                      sorted keys.  Keys within a query are distinct, so the result does not depend on the order of the atomics.
+ *                      A key whose slot lies outside its query's segment (offsets that are not the prefix sum of this plan's counts)
+ *                      is not stored; cursor[q] then differs from the segment's length.
+ *
+ * Tiled schedule only (algo NLSH_SCAN_BUCKET_TILED), every storage and metric, P <= NLSH_MAX_PROBES, d <= NLSH_MAX_DIM,
+ * total < 2^31.  Q = 0, total = 0 and an empty index are valid.  Checked on the host before anything is launched, NLSH_E_INVALID /
+ * NLSH_E_UNSUPPORTED with the argument's name in nlsh_last_error(): a null radius, out_count or row_offsets, a misaligned row_filter,
+ * another algo, P or d out of range, negative sizes.  The workspace-size functions return 0 and a message for sizes they refuse. */
+size_t nlsh_range_workspace(int64_t Q, int P, int64_t max_tasks, int64_t n_buckets, int d);
+size_t nlsh_range_sort_workspace(int64_t Q, int64_t total);
+int nlsh_range_count(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
+                     const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                     const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                     const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
+                     const int32_t *qkeys, const int32_t *nkeys, int P, int metric, int algo,
+                     const uint32_t *row_filter, const float *radius, int32_t *out_count, int32_t *out_ncand,
+                     int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
+                     void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream);
+int nlsh_range_fill(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
+                    const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                    const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                    const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
+                    const int32_t *qkeys, const int32_t *nkeys, int P, int metric, int algo,
+                    const uint32_t *row_filter, const float *radius, const int64_t *row_offsets, int64_t total, int32_t *cursor,
+                    uint64_t *out_keys, float *out_dist, int32_t *out_idx,
+                    int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
+                    void *sort_workspace, size_t sort_workspace_bytes, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * One pipelined query batch per call.  Replaces, for a caller that streams batches, the whole body of Indexer.query
  * (nlsh/indexer.py:56-96: hashing.hash on the batch :59 via Indexer.hash :40-54, then the per-query loop :62-95) by ONE
  * enqueue: nlsh_encode_hash + the PLAN, SCAN and MERGE phases of nlsh_scan_topk_cells_phase (five launches since r06: the bucket

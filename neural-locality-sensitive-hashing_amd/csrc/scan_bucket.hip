@@ -195,6 +195,13 @@ int bucket_scan_plan_args(const BucketScanCall &c, PlanArgs *pa) {
     return bucket_scan_args(c, a, *pa, metric, prep);
 }
 
+int bucket_scan_bargs(const BucketScanCall &c, BArgs *a) {
+    PlanArgs pa;
+    int metric;
+    bool prep;
+    return bucket_scan_args(c, *a, pa, metric, prep);
+}
+
 int bucket_scan_run(const BucketScanCall &c) {
     BArgs a;
     PlanArgs pa;

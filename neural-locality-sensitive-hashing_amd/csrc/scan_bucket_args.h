@@ -50,4 +50,22 @@ struct BArgs {
     int d4p;
 };
 
+// Second parameter of the radius-query kernels (bscanr_kernel, scan_bucket_range.hip; nlsh_range_count / nlsh_range_fill): what the range
+// epilogue of tiled_task_body reads beside BArgs, which keeps its layout.
+#define NLSH_RANGE_COUNT 0
+#define NLSH_RANGE_FILL 1
+struct RangeArgs {
+    const uint32_t *row_filter;    // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: every row allowed
+    const float *radius;           // [Q] a candidate is a hit iff dist <= radius[q] (IEEE: a NaN distance never is)
+    int32_t *counter;              // [Q] zeroed by the call; count mode: hits of the query; fill mode: its write cursor
+    const int64_t *row_offsets;    // fill mode: [Q + 1] exclusive prefix sum of the counts
+    uint64_t *keys;                // fill mode: [total] the hits' sort keys, a query's in no particular order
+    long long total;               // fill mode: row_offsets[Q] as the host read it; no key is stored at or behind it
+    int mode;                      // NLSH_RANGE_COUNT | NLSH_RANGE_FILL (wave-uniform)
+};
+
+// BArgs of a call, as bucket_scan_run builds them (scan_bucket.hip): the radius query launches its own kernel on the plan the PLAN phase
+// of a k = 1 call left in the workspace
+int bucket_scan_bargs(const BucketScanCall &c, BArgs *a);
+
 }  // namespace nlsh

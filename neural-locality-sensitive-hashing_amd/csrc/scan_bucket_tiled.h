@@ -2,7 +2,7 @@
 // instantiates the float32 kernels, scan_bucket_typed.hip the float16 / uint8 ones):
 // the hand-scheduled k-blocks, the task bodies built from them (l2_task*), one task start to finish (tiled_task_body) and the kernels
 // bscan3_kernel (k <= 64) and bscanw_kernel (k up to NLSH_MAX_K_TILED) over a float32 corpus, bscant_kernel over a float16 / uint8 one,
-// bscanf_kernel behind a row filter (scan_bucket_filtered.hip instantiates it).
+// bscanf_kernel behind a row filter (scan_bucket_filtered.hip instantiates it), bscanr_kernel for radius queries (scan_bucket_range.hip).
 #pragma once
 
 // Diagnostic build only (make EXTRA=-DNLSH_SCAN_TRACE, tools/scan_trace.py): wave 0 of every bscan3 workgroup
@@ -452,10 +452,19 @@ __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const typena
 // may be returned).  The lane's word of every tile is requested beside its row id at the top of the task and its bit enters `mine` in
 // the epilogue: a denied row is dropped in front of the selection and changes nothing in staging, in the k-blocks or in a distance.
 // Off (the default), neither the parameter nor the words exist in the code.
-template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = NLSH_STORE_F32, bool FILT = false>
+// RANGE (compile time; nlsh_range_count / nlsh_range_fill, bscanr_kernel): the RANGE EPILOGUE in place of the selection.  Everything up to
+// the epilogue is the same code, so every distance keeps its bits; per (task, slot) list a candidate is a hit iff it is `mine` and
+// dist <= range->radius[q] (IEEE float32: a NaN distance never is, +inf only at radius +inf), the hits are counted with ballots over the
+// TPS tiles and lane 0 adds the count to range->counter[q] -- the whole answer in count mode; in fill mode the add's result is the
+// list's first slot of the query's segment and every hit lane stores its key at row_offsets[q] + slot (mbcnt ranks, as in
+// select_k_smallest's compaction).  tauq and partial are not touched.  range->row_filter (nullable) is the filter, a run-time operand
+// here: a null pointer gives every lane an all-ones word.  Off (the default), neither the parameter nor the code exists.
+template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = NLSH_STORE_F32, bool FILT = false, bool RANGE = false>
 __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, long long t, const int4 desc, const int2 qr_all, int tid, int lane,
                                                 int wave, [[maybe_unused]] unsigned long long ts_entry,
-                                                [[maybe_unused]] const uint32_t *row_filter = nullptr) {
+                                                [[maybe_unused]] const uint32_t *row_filter = nullptr,
+                                                [[maybe_unused]] const RangeArgs *range = nullptr) {
+    static_assert(!(RANGE && (FILT || WIDEK)), "the range epilogue reads its filter from RangeArgs and selects nothing");
     static_assert(QW == 4 && TPS == 4 && NW == 4, "the hand-scheduled task bodies (l2_task_nt) are written for 4 waves x 4 queries x 4 row tiles");
 #ifdef NLSH_SCAN_TRACE_CLOCK
     const unsigned long long ts0 = SCAN_NOW();
@@ -511,6 +520,7 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
         mygid[tl] = valid[tl] ? a.gid[prow] : -1;
         myinv[tl] = (METRIC == NLSH_METRIC_COSINE && valid[tl]) ? a.inv_norm[prow] : 0.0f;
         if (FILT) myfw[tl] = row_filter[prow >> 5];
+        else if (RANGE) myfw[tl] = range->row_filter ? range->row_filter[prow >> 5] : 0xFFFFFFFFu;
     }
     [[maybe_unused]] unsigned long long trl[3] = {0, 0, 0};
     [[maybe_unused]] const unsigned long long ts_in = SCAN_NOW();
@@ -541,8 +551,12 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
     [[maybe_unused]] const unsigned long long ts3 = SCAN_NOW();
     // the running bounds of the wave's queries are requested together (one exposed round trip, not one per query)
     uint64_t tau_w[QW];
+    [[maybe_unused]] float rad_w[QW];   // RANGE: the queries' radii, requested together where the bounds are (the bounds are not read)
 #pragma unroll
-    for (int jq = 0; jq < QW; ++jq) tau_w[jq] = jq < nqw ? global_tau_load(a.tauq + qid[jq]) : KEY_NONE;
+    for (int jq = 0; jq < QW; ++jq) {
+        if (RANGE) { tau_w[jq] = KEY_NONE; rad_w[jq] = jq < nqw ? range->radius[qid[jq]] : 0.0f; }
+        else tau_w[jq] = jq < nqw ? global_tau_load(a.tauq + qid[jq]) : KEY_NONE;
+    }
     constexpr bool LEAN = METRIC != NLSH_METRIC_COSINE;   // r05: square roots without the range scaling, sign-free key build (L2 only)
 #pragma unroll
     for (int jq = 0; jq < QW; ++jq) {
@@ -554,6 +568,7 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
             const int rng = __builtin_amdgcn_readlane(qr_all.y, NLSH_SLOT(wave_u, jq));
             const unsigned r_lo = (unsigned)((rng & 0xFFFF) - h_lo), r_n = (unsigned)(rng >> 16) - (unsigned)(rng & 0xFFFF);   // relative to the first row staged
             uint64_t key[TPS];
+            [[maybe_unused]] bool hit[TPS];   // RANGE: in range (the key is then the candidate's, never KEY_NONE)
             // LEAN: every accumulator of the list at or above 2^-96 (wave-uniform test; NaN compares false and takes the general path)
             // -> square roots without the range scaling, and a non-negative distance's order-preserving word is its bits with the sign set
             bool lean = LEAN;
@@ -568,16 +583,48 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
 #pragma unroll
             for (int tl = 0; tl < TPS; ++tl) {
                 bool mine = valid[tl] && (unsigned)(tl * 64 + lane) - r_lo < r_n;
-                if (FILT) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
+                if (FILT || RANGE) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
                 uint64_t kk;
+                [[maybe_unused]] float dist_r;   // RANGE: the distance the key is built from, held against the radius
                 if (lean) {
                     const float dist = sqrt_rn_unscaled(acc[tl][jq]);
                     kk = ((uint64_t)(__builtin_bit_cast(uint32_t, dist) | 0x80000000u) << 32) | (uint32_t)mygid[tl];   // == make_key for dist >= +0
+                    dist_r = dist;
                 } else {
-                    kk = make_key(finish_distance<METRIC>(acc[tl][jq], myinv[tl]), mygid[tl]);
+                    const float dist = finish_distance<METRIC>(acc[tl][jq], myinv[tl]);
+                    kk = make_key(dist, mygid[tl]);
+                    dist_r = dist;
                 }
+                if (RANGE) hit[tl] = mine && dist_r <= rad_w[jq];   // a NaN distance compares false, whatever the radius
                 kk = mine ? kk : KEY_NONE;
                 key[tl] = kk < tau_g ? kk : KEY_NONE;  // beyond another list's k-th best: cannot reach the final top-k
+            }
+            if (RANGE) {
+                // hits of the list: one ballot per tile; a hit lane's rank is the hits of the tiles in front of its own plus the hit
+                // lanes below it (mbcnt).  One atomic per list and mode, by lane 0, and none for a list without a hit.
+                unsigned long long hm[TPS];
+                int n_hits = 0;
+#pragma unroll
+                for (int tl = 0; tl < TPS; ++tl) { hm[tl] = __ballot(hit[tl]); n_hits += __popcll(hm[tl]); }
+                if (n_hits == 0) continue;   // wave-uniform
+                int32_t *ctr = range->counter + qid[jq];
+                if (range->mode == NLSH_RANGE_COUNT) {
+                    if (lane == 0) atomicAdd(ctr, n_hits);
+                    continue;
+                }
+                int base = 0;
+                if (lane == 0) base = atomicAdd(ctr, n_hits);
+                base = __builtin_amdgcn_readfirstlane(base);
+                // the query's segment: a slot past its end (offsets that are not the prefix sum of THIS plan's counts) is not written,
+                // and the cursor the call leaves then exceeds the segment's length
+                const long long seg0 = range->row_offsets[qid[jq]], seg_n = range->row_offsets[qid[jq] + 1] - seg0;
+#pragma unroll
+                for (int tl = 0; tl < TPS; ++tl) {
+                    const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(hm[tl] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm[tl], 0u));
+                    if (hit[tl] && pos >= 0 && pos < seg_n && seg0 >= 0 && seg0 + pos < range->total) range->keys[seg0 + pos] = key[tl];
+                    base += __popcll(hm[tl]);
+                }
+                continue;
             }
             uint64_t *out = a.partial + ((long long)t * (QW * NW) + NLSH_SLOT(wave, jq)) * a.k;
 #ifdef NLSH_SCAN_TRACE_EPILOGUE
@@ -740,6 +787,32 @@ __global__ __launch_bounds__(64 * NW, 1) void bscanf_kernel(BArgs a, const uint3
     const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
     if (t >= ntasks) return;
     tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, row_filter);
+}
+
+// The radius query's scan (RANGE of tiled_task_body; nlsh_range_count / nlsh_range_fill), every storage: the tiled kernels with the range
+// epilogue.  One kernel per (metric, storage) serves both modes and both filter states -- r.mode and r.row_filter are wave-uniform
+// run-time operands of the epilogue.  RangeArgs is a SECOND kernel parameter, as the filter is bscanf_kernel's: BArgs and every kernel
+// above keep their layout and their code (profiles/range_query.txt).  Instantiated in scan_bucket_range.hip, a translation unit of its
+// own.  The task pick is bscan3_kernel's, line for line (see the comments there), written out again for the reason given at bscanw_kernel.
+template <int METRIC, int QW, int NW, int TPS, int STORE>
+__global__ __launch_bounds__(64 * NW, 1) void bscanr_kernel(BArgs a, RangeArgs r) {
+    constexpr int RS = NLSH_TILED_KB + 1;
+    __shared__ float4 tile[64 * TPS * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
+    long long ntasks = a.status[0];
+    if (ntasks > a.max_tasks) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
+        ntasks = a.max_tasks;
+    }
+    constexpr int XC = 16;
+    const long long j = blockIdx.x >> 3;
+    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
+    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
+    const int4 desc = a.task[tc];
+    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
+    if (t >= ntasks) return;
+    tiled_task_body<METRIC, QW, NW, TPS, false, STORE, false, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, nullptr, &r);
 }
 
 }  // namespace nlsh

@@ -45,6 +45,7 @@ SYMBOLS = (
     "nlsh_scan_topk_cells_phase_typed", "nlsh_gather_rows_typed", "nlsh_csr_update_typed",
     "nlsh_row_filter_words", "nlsh_row_filter_build", "nlsh_scan_topk_cells_phase_filtered",
     "nlsh_merge_topk_unique",
+    "nlsh_range_workspace", "nlsh_range_sort_workspace", "nlsh_range_count", "nlsh_range_fill",
 )
 
 
@@ -152,6 +153,16 @@ def lib():
     L.nlsh_scan_topk_cells_phase_typed.argtypes = L.nlsh_scan_topk_cells_phase.argtypes[:1] + [i32] + L.nlsh_scan_topk_cells_phase.argtypes[1:]
     L.nlsh_scan_topk_cells_phase_filtered.restype = i32     # the typed call, row_filter behind phases
     L.nlsh_scan_topk_cells_phase_filtered.argtypes = L.nlsh_scan_topk_cells_phase_typed.argtypes + [vp]
+    L.nlsh_range_workspace.restype = sz
+    L.nlsh_range_workspace.argtypes = [i64, i32, i64, i64, i32]
+    L.nlsh_range_sort_workspace.restype = sz
+    L.nlsh_range_sort_workspace.argtypes = [i64, i64]
+    # the filtered call's arguments up to nkeys, P | metric, algo | row_filter, radius | ...
+    range_head = L.nlsh_scan_topk_cells_phase_filtered.argtypes[:19] + [i32, i32, vp, vp]
+    L.nlsh_range_count.restype = i32     # ... out_count, out_ncand | status, workspace, bytes, max_tasks | scan events, stream
+    L.nlsh_range_count.argtypes = range_head + [vp, vp, vp, vp, sz, i64, vp, vp, vp]
+    L.nlsh_range_fill.restype = i32      # ... row_offsets, total, cursor | out_keys, out_dist, out_idx | status, workspace, bytes, max_tasks | sort workspace, bytes | scan events, stream
+    L.nlsh_range_fill.argtypes = range_head + [vp, i64, vp, vp, vp, vp, vp, vp, sz, i64, vp, sz, vp, vp, vp]
     L.nlsh_row_filter_words.restype = sz
     L.nlsh_row_filter_words.argtypes = [i64]
     L.nlsh_row_filter_build.restype = i32      # gid, n_rows | ids, n_ids | dense, n_dense, id_base | invert | row_filter, n_allowed, stream

@@ -965,7 +965,7 @@ class Indexer:
         from them.  Callers that launch many batches (the kept range plans, nlsh_amd/pipeline.py) build them once per buffer set; a
         call is then one ctypes transition."""
         a = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (the tensors that may be absent)
-        metric = (_capi.METRIC_L2_EPS_FOLDED if self.l2_form == "folded" else _capi.METRIC_L2_EPS) if self.metric == "l2" else _capi.METRIC_COSINE
+        metric = self._metric_code()
         if window is None:
             window = self.choose_window(Q, keys.shape[1], algo)
         if window and algo == _capi.SCAN_BUCKET_TILED:
@@ -1035,6 +1035,161 @@ class Indexer:
             pad = (idx == -1) & (dist == float("inf"))
             keys64 = torch.where(pad, torch.full_like(mono, -1), (mono << 32) | (idx.long() & 0xFFFFFFFF))
         return dist, idx, ncand, keys64
+
+    # ------------------------------------------------------------------ radius (range) queries
+    @staticmethod
+    def _checked_radius(radius, Q, dev):
+        """`radius=` of a range call, checked before anything is launched -> float32 [Q] on `dev`."""
+        if isinstance(radius, torch.Tensor):
+            if radius.dtype != torch.float32:
+                raise ValueError(f"radius must be a Python float or a float32 tensor, got dtype {radius.dtype}")
+            if radius.dim() != 1 or radius.shape[0] != Q:
+                raise ValueError(f"radius must hold one value per query: shape {tuple(radius.shape)} != ({Q},)")
+            if radius.device != dev:
+                raise ValueError(f"radius is on {radius.device}, the queries on {dev}")
+            if Q and bool(torch.isnan(radius).any()):
+                raise ValueError("radius holds a NaN: no distance compares <= NaN")
+            return radius.contiguous()
+        if isinstance(radius, bool) or not isinstance(radius, numbers.Real):
+            raise ValueError(f"radius must be a Python float or a float32 tensor, got {type(radius).__name__}")
+        if radius != radius:
+            raise ValueError("radius is NaN: no distance compares <= NaN")
+        with np.errstate(over="ignore"):
+            r32 = np.full((Q,), radius, dtype=np.float64).astype(np.float32)    # the float32 the kernel compares with (beyond its range: +-inf)
+        return torch.as_tensor(r32).to(dev)
+
+    def _metric_code(self):
+        return (_capi.METRIC_L2_EPS_FOLDED if self.l2_form == "folded" else _capi.METRIC_L2_EPS) if self.metric == "l2" else _capi.METRIC_COSINE
+
+    def _range_head(self, q, keys, nkeys, window, filter, rad):
+        """The arguments `nlsh_range_count` and `nlsh_range_fill` share, in their order: index, queries, key table, metric, schedule,
+        filter words (or None) and radii."""
+        a = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        if window:
+            cell_of, cell_offsets, order, n_cells = self.cells(window)
+        else:
+            cell_of, cell_offsets, order, n_cells = None, None, self.bucket_order, 0
+        return (self.corpus_sorted.data_ptr(), _STORAGES[self.storage][1], self.row_stride, q.shape[1], self.gid.data_ptr(),
+                self.uniq_keys.data_ptr(), self.offsets.data_ptr(), order.data_ptr(), self.n_buckets, a(cell_of), a(cell_offsets), n_cells,
+                a(self.inv_norm), q.data_ptr(), q.stride(0), q.shape[0], keys.data_ptr(), nkeys.data_ptr(), keys.shape[1],
+                self._metric_code(), _capi.SCAN_BUCKET_TILED, a(filter.words) if filter is not None else None, rad.data_ptr())
+
+    def range_scan_tensors(self, query_vectors, keys, nkeys, radius, filter=None, limit=None, want_keys=False):
+        """Radius query on a device key table -> (offsets int64 [Q + 1], idx int32 [T], dist float32 [T], ncand int32 [Q], keys64 | None),
+        all on the device: query q's result is idx / dist [offsets[q]:offsets[q + 1]], EVERY row of its keys' buckets with
+        dist <= radius[q] (IEEE float32: a NaN distance never is, +inf only at radius +inf), each once, in the (distance, row id) order
+        of the top-k calls, with the distance bits `scan_tensors` reports for that (query, row).  DESIGN.md 4.12.
+        radius: a Python float (every query's) or a float32 tensor [Q] on the queries' device.  filter: as in `scan_tensors`.
+        ncand: the rows of the probed buckets, before the radius and before the filter -- `scan_tensors`' value.
+        limit (None = off): ValueError once the counts are known and before any output is allocated, if T > limit.
+        Two scan launches with one host read between them (`nlsh_range_count`, `nlsh_range_fill`): the call synchronises.  Always the
+        tiled schedule, as filtered and compressed calls; key tables wider than 64 probes are refused."""
+        filter = self._checked_filter(filter)
+        if self.metric not in ("l2", "cosine"):
+            raise NotImplementedError("range queries need metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
+        q = self._as_queries(query_vectors)
+        Q, d = q.shape
+        if d != self.dim:
+            raise ValueError(f"query dim {d} != corpus dim {self.dim}")
+        P = keys.shape[1]
+        if P > _capi.MAX_PROBES:
+            raise ValueError(f"range queries take at most {_capi.MAX_PROBES} keys per query (hash_times <= {_capi.MAX_PROBES}), got {P}")
+        if limit is not None and limit < 0:
+            raise ValueError(f"limit must be None or >= 0, got {limit}")
+        dev = q.device
+        rad = self._checked_radius(radius, Q, dev)
+        keys, nkeys = keys.contiguous(), nkeys.contiguous()
+        algo, stream, L = _capi.SCAN_BUCKET_TILED, _stream(dev), _capi.lib()
+        pack = torch.empty((2 * Q + 2,), dtype=torch.int32, device=dev)     # one copy brings counts, candidate counts and status to the host
+        count, ncand, status = pack.split((Q, Q, 2))
+        a = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        if Q == 0:
+            return (torch.zeros((1,), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.int32, device=dev),
+                    torch.empty((0,), dtype=torch.float32, device=dev), ncand, torch.empty((0,), dtype=torch.int64, device=dev) if want_keys else None)
+        while True:
+            tkey, window, max_tasks = self._task_table(algo, Q, P)
+            wkey, ws = self._workspace(dev, stream, True, L.nlsh_range_workspace(Q, P, max_tasks, self.n_buckets, d))
+            head = self._range_head(q, keys, nkeys, window, filter, rad)
+            tail = (status.data_ptr(), ws.data_ptr(), ws.numel(), max_tasks)
+            try:
+                _capi.check(L.nlsh_range_count(*head, count.data_ptr(), ncand.data_ptr(), *tail, None, None, stream))
+            except _capi.NlshHipError:
+                self._ws.pop(wkey, None)    # a call that failed part-way may have left the counters at the head non-zero
+                raise
+            host = pack.cpu()
+            needed, overflow = host[2 * Q:].tolist()
+            if self._settle(tkey, needed, overflow, max_tasks):     # else: task table too small, grown: count again
+                break
+        offsets_h = torch.zeros((Q + 1,), dtype=torch.int64)
+        offsets_h[1:] = torch.cumsum(host[:Q].long(), 0)
+        T = int(offsets_h[-1])
+        if limit is not None and T > limit:
+            raise ValueError(f"range query: {T} rows are in range, limit={limit}")
+        if T >= 1 << 31:
+            raise ValueError(f"range query: {T} rows are in range; one call returns fewer than 2^31 (split the batch)")
+        offsets = offsets_h.to(dev)
+        idx = torch.empty((T,), dtype=torch.int32, device=dev)
+        dist = torch.empty((T,), dtype=torch.float32, device=dev)
+        keys64 = torch.empty((T,), dtype=torch.int64, device=dev) if want_keys else None
+        if T:
+            sort_bytes = L.nlsh_range_sort_workspace(Q, T)
+            if sort_bytes == 0:
+                _capi.check(_capi.E_HIP)
+            sort_ws = torch.empty((sort_bytes,), dtype=torch.uint8, device=dev)
+            cursor = torch.empty((Q,), dtype=torch.int32, device=dev)
+            # the fill launch runs on the plan the count call left in `ws`: same table, same workspace, nothing in between
+            _capi.check(L.nlsh_range_fill(*head, offsets.data_ptr(), T, cursor.data_ptr(), a(keys64), dist.data_ptr(), idx.data_ptr(), *tail,
+                                          sort_ws.data_ptr(), sort_bytes, None, None, stream))
+        self._set_last(status, algo, window, pack, tkey, max_tasks)
+        return offsets, idx, dist, ncand, keys64
+
+    def range_tensors(self, query_vectors, radius, hash_times=10, seed=None, probes=None, candidate_budget=None, filter=None, limit=None,
+                      want_keys=False):
+        """Device-resident radius query: the hash by the two-step route (`last_query_path == "two_step"`; probes / candidate_budget as in
+        `query_tensors`), then `range_scan_tensors`.  hash_times <= 64."""
+        filter = self._checked_filter(filter)
+        if self.metric not in ("l2", "cosine"):
+            raise NotImplementedError("range queries need metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
+        if hash_times > _capi.MAX_PROBES:
+            raise ValueError(f"range queries take hash_times <= {_capi.MAX_PROBES}, got {hash_times}")
+        q = self._as_queries(query_vectors)
+        self._checked_radius(radius, q.shape[0], q.device)      # refused before the hash is launched
+        keys, nkeys = self._filtered_keys(q, hash_times, seed, probes, candidate_budget)
+        return self.range_scan_tensors(q, keys, nkeys, radius, filter=filter, limit=limit, want_keys=want_keys)
+
+    @staticmethod
+    def _range_lists(offsets, idx, dist, ncand, return_distances):
+        off = offsets.cpu().tolist()
+        ids, nc = idx.cpu().tolist(), ncand.cpu().tolist()
+        rows = [ids[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
+        if not return_distances:
+            return rows, nc
+        dh = dist.cpu().tolist()
+        return rows, nc, [dh[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
+
+    def range_query(self, query_vectors, radius, hash_times=10, seed=None, probes=None, candidate_budget=None, filter=None, limit=None,
+                    return_distances=False):
+        """Radius query in the shape `query()` returns: (List[List[int]], List[int]) -- per query the ids of every candidate within
+        `radius`, in (distance, row id) order, and the candidate counts (before the radius and the filter); with return_distances=True
+        also the lists of distances.  See `range_scan_tensors`."""
+        out = self.range_tensors(query_vectors, radius, hash_times, seed, probes, candidate_budget, filter, limit)
+        return self._range_lists(*out[:4], return_distances)
+
+    def range_query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], radius, filter=None, return_distances=False):
+        """`range_query` on caller-supplied key lists, like `query_with_keys`."""
+        filter = self._checked_filter(filter)
+        key_lists = [list(dict.fromkeys(int(key) for key in ks)) for ks in key_lists]
+        Q = len(key_lists)
+        P = max([len(ks) for ks in key_lists] + [1])
+        tab = np.zeros((Q, P), dtype=np.int64)
+        cnt = np.zeros((Q,), dtype=np.int32)
+        for i, ks in enumerate(key_lists):
+            cnt[i] = len(ks)
+            tab[i, :len(ks)] = list(ks)
+        tab = np.where(tab >= (1 << 31), tab - (1 << 32), tab).astype(np.int32)
+        dev = query_vectors.device
+        out = self.range_scan_tensors(query_vectors, torch.as_tensor(tab).to(dev), torch.as_tensor(cnt).to(dev), radius, filter=filter)
+        return self._range_lists(*out[:4], return_distances)
 
     def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None, probes=None,
                       candidate_budget=None, filter=None):
