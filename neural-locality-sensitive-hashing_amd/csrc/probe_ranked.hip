@@ -301,7 +301,7 @@ __global__ __launch_bounds__(PRP_ROWS * 64) void probe_ranked_plan_kernel(const 
 
 }  // namespace
 
-// the launch of nlsh_query_batch_ranked (step.hip): `pa` = the PlanArgs of the scan call the keys go to (bucket_scan_plan_args); the coarse
+// the launch of nlsh_query_batch_ranked (step.hip): `pa` = the PlanArgs of the scan call the keys go to (bucket_scan_args: BucketScanPrep::pa); the coarse
 // table is sized here.  *blocks_out = workgroups launched = entries of `hits` the scan call's NLSH_PHASE_PLAN_REST sums.
 int probe_ranked_plan_launch(const float *z, long long z_stride, const uint32_t *code, int H, int key_mode, long long n_multi_rows, int32_t budget,
                              PlanArgs &pa, int32_t *keys_out, int32_t *nkeys_out, hipStream_t stream, int *blocks_out) {

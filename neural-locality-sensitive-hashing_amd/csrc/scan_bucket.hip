@@ -36,12 +36,6 @@
 
 namespace nlsh {
 
-constexpr int TILED_QB = 16;  // queries per task of the tiled schedule (4 per wave)
-constexpr int TILED_TPS = 4;  // 64-row tiles per task of the tiled schedule (segment = 64*TPS rows)
-// a shared window (nlsh_build_cells: window_rows <= 256) must fit ONE segment: bscatter derives a window bucket's partial-list count from
-// its own size and clamps its row range to the segment, so a window wider than a segment would silently lose rows
-static_assert(64 * TILED_TPS >= 256, "the tiled schedule's segment must hold the widest row window nlsh_build_cells accepts (256 rows)");
-
 struct BWs {
     size_t ppair, prec, inv_q, bcount, cellrec, lookback, hits, task, task_qr, partial, qpad, tauq, total;
 };
@@ -102,58 +96,63 @@ static const void *bscan2_of(int d4) {
     return (const void *)bscan2_kernel<64, 4, METRIC, 2>;
 }
 
-// the scan kernel of a call and its launch shape
-static void scan_kernel_of(const BucketScanCall &c, int metric, int d4, const void **fn, dim3 *grid, dim3 *block) {
-    if (c.tiled) {
-        // QW = 4 queries per wave (SGPR budget: two chunks x QW x 4 scalar values in flight), NW = 4 waves
-        // one workgroup per task; the chunked XCD map works on 8 x 16 ids.  (Persistent workgroups pulling tasks from a
-        // per-XCD queue were measured three ways in r02 -- 0.447 / 0.423 / 0.350 ms against 0.283 ms; r04: 2 / 4 / 8 consecutive
-        // task ids per workgroup, 79 VGPRs, +3 / +10 / +25 % on the headline and no better on the small-bucket workloads:
-        // profiles/r04_tasks_per_workgroup_ab.txt, DESIGN.md appendix A.)
-        *grid = dim3((unsigned)((c.max_tasks + 127) / 128 * 128));
-        *block = dim3(64 * (TILED_QB / 4));
-        if (c.storage != NLSH_STORE_F32) {   // a float16 / uint8 corpus: kernels of their own, in a translation unit of their own (scan_bucket_typed.hip)
-            *fn = typed_scan_kernel_of(c.storage, metric, c.k > NLSH_MAX_K);
-        } else if (c.k > NLSH_MAX_K) {   // wide k: the same task body, its epilogue selecting up to 64 * TPS keys per list
-            static_assert(NLSH_MAX_K_TILED <= 64 * TILED_TPS, "a (task, query) list is selected from the 64 * TPS candidates the wave holds");
-            if (metric == NLSH_METRIC_L2_EPS) *fn = (const void *)bscanw_kernel<NLSH_METRIC_L2_EPS, 4, TILED_QB / 4, TILED_TPS>;
-            else if (metric == NLSH_METRIC_L2_EPS_FOLDED) *fn = (const void *)bscanw_kernel<NLSH_METRIC_L2_EPS_FOLDED, 4, TILED_QB / 4, TILED_TPS>;
-            else *fn = (const void *)bscanw_kernel<NLSH_METRIC_COSINE, 4, TILED_QB / 4, TILED_TPS>;
-        } else if (metric == NLSH_METRIC_L2_EPS) *fn = (const void *)bscan3_kernel<NLSH_METRIC_L2_EPS, 4, TILED_QB / 4, TILED_TPS>;
-        else if (metric == NLSH_METRIC_L2_EPS_FOLDED) *fn = (const void *)bscan3_kernel<NLSH_METRIC_L2_EPS_FOLDED, 4, TILED_QB / 4, TILED_TPS>;
-        else *fn = (const void *)bscan3_kernel<NLSH_METRIC_COSINE, 4, TILED_QB / 4, TILED_TPS>;
+// The SCAN phase's launch of a call -- kernel, grid, block and argument vector -- for bucket_scan_run and bucket_scan_node alike.
+struct ScanLaunch {
+    const void *fn;
+    dim3 grid, block;
+    void *argv[2];   // the kernel's BArgs and, read by the filtered kernels alone, the filter pointer as their second parameter
+};
+static int scan_launch_of(const BucketScanCall &c, int metric, const BArgs *a, ScanLaunch *l) {
+    l->argv[0] = (void *)a;
+    l->argv[1] = (void *)&c.row_filter;
+    const bool wide = c.k > NLSH_MAX_K;   // wide k: the same task body, its epilogue selecting up to 64 * TPS keys per list
+    if (!c.tiled()) {
+        NLSH_REQUIRE(!c.row_filter && c.storage == NLSH_STORE_F32, NLSH_E_UNSUPPORTED,
+                     "scan_topk(bucket-major): row_filter and a float16 / uint8 corpus are read by the tiled schedule only");
+        l->grid = dim3((unsigned)((c.max_tasks + 3) / 4));  // one wavefront per task
+        l->block = dim3(256);
     } else {
-        *grid = dim3((unsigned)((c.max_tasks + 3) / 4));  // one wavefront per task
-        *block = dim3(256);
-        *fn = metric == NLSH_METRIC_L2_EPS ? bscan2_of<NLSH_METRIC_L2_EPS>(d4) : bscan2_of<NLSH_METRIC_COSINE>(d4);
+        l->grid = tiled_grid(c.max_tasks);
+        l->block = tiled_block();
     }
+    // (the float32 tiled kernels are named before the wave-level ones: a code object keeps its kernels in the order the host code first
+    // names them, and scan_bucket.hip's is compared byte for byte across changes of this file)
+    if (c.tiled() && c.row_filter) l->fn = filtered_scan_kernel_of(c.storage, metric, wide);                    // scan_bucket_filtered.hip
+    else if (c.tiled() && c.storage != NLSH_STORE_F32) l->fn = typed_scan_kernel_of(c.storage, metric, wide);   // scan_bucket_typed.hip
+    else if (c.tiled() && wide) l->fn = NLSH_TILED_KERNEL(bscanw_kernel, metric);
+    else if (c.tiled()) l->fn = NLSH_TILED_KERNEL(bscan3_kernel, metric);
+    else l->fn = metric == NLSH_METRIC_L2_EPS ? bscan2_of<NLSH_METRIC_L2_EPS>((c.d + 3) / 4) : bscan2_of<NLSH_METRIC_COSINE>((c.d + 3) / 4);
+    return NLSH_OK;
 }
 
-// BArgs (what the scan kernels take) and PlanArgs (what the lookup takes) of one call: pointers into the caller's workspace.
-static int bucket_scan_args(const BucketScanCall &c, BArgs &a, PlanArgs &pa, int &metric_out, bool &prep_out) {
+// A call's prepared launch (scan_bucket_args.h): BArgs and PlanArgs pointing into the caller's workspace, the effective metric, `prep`.
+int bucket_scan_args(const BucketScanCall &c, BucketScanPrep *p) {
+    BArgs &a = p->a;
+    PlanArgs &pa = p->pa;
+    const bool tiled = c.tiled();
     BWs w;
-    blayout(c.Q, c.P, c.k, c.max_tasks, c.nb, c.d, c.tiled != 0, &w);
+    blayout(c.Q, c.P, c.k, c.max_tasks, c.nb, c.d, tiled, &w);
     NLSH_REQUIRE(c.workspace_bytes >= w.total, NLSH_E_WORKSPACE, "scan_topk(bucket-major): workspace %zu < %zu", c.workspace_bytes, w.total);
     const int d4 = (c.d + 3) / 4;
     a.corpus = c.corpus; a.row_stride = c.row_stride; a.d = c.d; a.gid = c.gid; a.uniq = c.uniq; a.offsets = c.offsets; a.nb = c.nb;
     // cells exist for the tiled schedule only (a window is one 256-row segment of its task shape); the wave-level schedule ignores them
-    const bool cells = c.tiled && c.cell_of && c.cell_offsets && c.n_cells > 0;
+    const bool cells = tiled && c.cell_of && c.cell_offsets && c.n_cells > 0;
     a.cell_of = cells ? c.cell_of : nullptr; a.coffsets = cells ? c.cell_offsets : c.offsets; a.nc = cells ? c.n_cells : c.nb;
     a.inv_norm = c.inv_norm; a.queries = c.queries; a.q_stride = c.q_stride; a.Q = c.Q; a.qkeys = c.qkeys; a.nkeys = c.nkeys;
-    a.P = c.P; a.k = c.k; a.seg = c.tiled ? 64 * TILED_TPS : c.seg; a.QB = c.tiled ? TILED_QB : (d4 <= 64 ? 8 : (d4 <= 128 ? 4 : 2));
+    a.P = c.P; a.k = c.k; a.seg = tiled ? 64 * TILED_TPS : scan_seg_rows(c.seg); a.QB = tiled ? TILED_QB : (d4 <= 64 ? 8 : (d4 <= 128 ? 4 : 2));
     a.qpad_w = (float *)((char *)c.workspace + w.qpad); a.qpad = a.qpad_w; a.qpad_stride = (long long)d4 * 4; a.d4p = d4;
     // L2 with d % 4 == 0 needs neither padding nor normalisation: read the caller's queries directly
     // the folded L2 form exists in the tiled schedule only (it always needs the prepared query copy: q + eps); the other two
     // schedules answer NLSH_METRIC_L2_EPS_FOLDED with the exact form, which is inside the same tolerance
-    const int metric = (!c.tiled && c.metric == NLSH_METRIC_L2_EPS_FOLDED) ? NLSH_METRIC_L2_EPS : c.metric;
-    const bool prep = c.tiled && !(metric == NLSH_METRIC_L2_EPS && (c.d & 3) == 0 && (c.q_stride & 3) == 0 && ((uintptr_t)c.queries & 15) == 0);
-    if (c.tiled && !prep) { a.qpad = c.queries; a.qpad_stride = c.q_stride; }
+    const int metric = (!tiled && c.metric == NLSH_METRIC_L2_EPS_FOLDED) ? NLSH_METRIC_L2_EPS : c.metric;
+    const bool prep = tiled && !(metric == NLSH_METRIC_L2_EPS && (c.d & 3) == 0 && (c.q_stride & 3) == 0 && ((uintptr_t)c.queries & 15) == 0);
+    if (tiled && !prep) { a.qpad = c.queries; a.qpad_stride = c.q_stride; }
     a.out_dist = c.out_dist; a.out_idx = c.out_idx; a.out_keys = c.out_keys; a.out_ncand = c.out_ncand; a.status = c.status;
     char *base = (char *)c.workspace;
     a.ppair = (int4 *)(base + w.ppair); a.prec = (int4 *)(base + w.prec); a.inv_q = (int32_t *)(base + w.inv_q);
     a.bcount = (int32_t *)(base + w.bcount); a.cellrec = (int4 *)(base + w.cellrec); a.lookback = (unsigned long long *)(base + w.lookback);
     a.hits = (int32_t *)(base + w.hits); a.border = c.bucket_order; a.task = (int4 *)(base + w.task);
-    a.task_qr = c.tiled ? (int2 *)(base + w.task_qr) : nullptr; a.partial = (uint64_t *)(base + w.partial);
+    a.task_qr = tiled ? (int2 *)(base + w.task_qr) : nullptr; a.partial = (uint64_t *)(base + w.partial);
     a.max_tasks = c.max_tasks;
     a.tauq = (unsigned long long *)(base + w.tauq);
 
@@ -165,51 +164,39 @@ static int bucket_scan_args(const BucketScanCall &c, BArgs &a, PlanArgs &pa, int
     pa.queries = c.queries; pa.q_stride = c.q_stride; pa.qpad = a.qpad_w; pa.qpad_stride = (long long)d4 * 4; pa.d = c.d; pa.d4p = d4;
     pa.prep_metric = prep ? metric : -1;
     pa.enabled = 1;
-    metric_out = metric;
-    prep_out = prep;
+    p->metric = metric;
+    p->prep = prep;
     return NLSH_OK;
 }
 
 int bucket_scan_node(const BucketScanCall &c, ScanNode *out) {
     static_assert(sizeof(BArgs) <= sizeof(out->args) && alignof(BArgs) <= 16, "ScanNode::args must hold the scan kernels' argument struct");
     NLSH_REQUIRE(c.max_tasks > 0, NLSH_E_INVALID, "scan node: empty task table");
-    BArgs *a = new (out->args) BArgs;
-    PlanArgs pa;
-    int metric;
-    bool prep;
-    const int rc = bucket_scan_args(c, *a, pa, metric, prep);
+    // a node carries ONE kernel parameter (ScanNode::argv): the filtered kernels take two
+    NLSH_REQUIRE(c.row_filter == nullptr, NLSH_E_UNSUPPORTED, "scan node: a call with a row_filter cannot be replayed from a graph node");
+    BucketScanPrep p;
+    int rc = bucket_scan_args(c, &p);
     if (rc != NLSH_OK) return rc;
-    const void *fn;
+    BArgs *a = new (out->args) BArgs(p.a);
+    ScanLaunch l;
+    rc = scan_launch_of(c, p.metric, a, &l);
+    if (rc != NLSH_OK) return rc;
     out->p = hipKernelNodeParams{};
-    scan_kernel_of(c, metric, (c.d + 3) / 4, &fn, &out->p.gridDim, &out->p.blockDim);
-    out->p.func = const_cast<void *>(fn);
-    out->argv[0] = out->args;
+    out->p.func = const_cast<void *>(l.fn);
+    out->p.gridDim = l.grid; out->p.blockDim = l.block;
+    out->argv[0] = l.argv[0];
     out->p.kernelParams = out->argv; out->p.sharedMemBytes = 0; out->p.extra = nullptr;
     return NLSH_OK;
 }
 
-int bucket_scan_plan_args(const BucketScanCall &c, PlanArgs *pa) {
-    BArgs a;
-    int metric;
-    bool prep;
-    return bucket_scan_args(c, a, *pa, metric, prep);
-}
-
-int bucket_scan_bargs(const BucketScanCall &c, BArgs *a) {
-    PlanArgs pa;
-    int metric;
-    bool prep;
-    return bucket_scan_args(c, *a, pa, metric, prep);
-}
-
 int bucket_scan_run(const BucketScanCall &c) {
-    BArgs a;
-    PlanArgs pa;
-    int metric;
-    bool prep;
-    const int rc = bucket_scan_args(c, a, pa, metric, prep);
+    BucketScanPrep p;
+    int rc = bucket_scan_args(c, &p);
     if (rc != NLSH_OK) return rc;
-    const int d4 = (c.d + 3) / 4;
+    const BArgs &a = p.a;
+    const bool scan = (c.phases & NLSH_PHASE_SCAN) && c.max_tasks > 0;
+    ScanLaunch l;
+    if (scan && (rc = scan_launch_of(c, p.metric, &a, &l)) != NLSH_OK) return rc;   // before anything is enqueued
 
     hipStream_t s = c.stream;
     const unsigned gp = (unsigned)((c.Q * c.P + 255) / 256);
@@ -220,8 +207,9 @@ int bucket_scan_run(const BucketScanCall &c) {
         // with device-coherent sc1 accesses instead, against 35 us for the separate launches: crossing XCDs inside a kernel costs as
         // much as a kernel boundary on this part.)  The per-cell pair counters need no clearing launch: bscan_kernel hands every
         // count back, so they are zero again after every call (workspace contract, nlsh_hip.h).
+        PlanArgs pa = p.pa;
         plan_coarse(pa, 1024);
-        const unsigned gprep = prep ? (unsigned)((c.Q + 3) / 4) : 0u;   // the query copy rides in the same launch
+        const unsigned gprep = p.prep ? (unsigned)((c.Q + 3) / 4) : 0u;   // the query copy rides in the same launch
         hipLaunchKernelGGL(bplan_kernel, dim3(gp + gprep), dim3(256), 0, s, pa, gp);
     }
     if (c.phases & (NLSH_PHASE_PLAN | NLSH_PHASE_PLAN_REST)) {
@@ -232,18 +220,9 @@ int bucket_scan_run(const BucketScanCall &c) {
         if (a.nc > 0) hipLaunchKernelGGL(bscan_kernel, dim3((unsigned)((a.nc + 255) / 256)), dim3(256), 0, s, a, plan_blocks);
         hipLaunchKernelGGL(bscatter_kernel, dim3(gp), dim3(256), 0, s, a);
     }
-    if ((c.phases & NLSH_PHASE_SCAN) && c.max_tasks > 0) {
+    if (scan) {
         if (c.ev_begin) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)c.ev_begin, s));
-        const void *fn;
-        dim3 grid, block;
-        scan_kernel_of(c, metric, d4, &fn, &grid, &block);
-        const uint32_t *row_filter = c.row_filter;
-        void *argv[2] = {&a, &row_filter};   // the second parameter is the filtered kernels' alone
-        if (row_filter) {   // same grid and block: the filtered kernels are the tiled kernels with one more term in the epilogue
-            NLSH_REQUIRE(c.tiled, NLSH_E_UNSUPPORTED, "scan_topk(bucket-major): row_filter is read by the tiled schedule only");
-            fn = filtered_scan_kernel_of(c.storage, metric, c.k > NLSH_MAX_K);
-        }
-        NLSH_CHECK_HIP(hipLaunchKernel(fn, grid, block, argv, 0, s));
+        NLSH_CHECK_HIP(hipLaunchKernel(l.fn, l.grid, l.block, l.argv, 0, s));
         if (c.ev_end) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)c.ev_end, s));
     }
     if (c.phases & NLSH_PHASE_MERGE) {

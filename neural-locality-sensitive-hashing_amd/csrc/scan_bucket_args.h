@@ -1,8 +1,29 @@
-// The argument struct of the bucket-major scan kernels (scan_bucket.hip, scan_bucket_typed.hip): pointers into the caller's arrays and workspace.
+// The argument struct of the bucket-major scan kernels (scan_bucket.hip and the typed, filtered and range units), the tile shape they are
+// all instantiated with, and a call's prepared launch: pointers into the caller's arrays and workspace.
 #pragma once
 #include "scan_common.h"
+#include "scan_plan.h"
 
 namespace nlsh {
+
+// The shape tiled_task_body is written for, and every tiled kernel is instantiated with <METRIC, TILED_QW, TILED_NW, TILED_TPS, ...>:
+constexpr int TILED_QW = 4;   // queries per wave (SGPR budget: two chunks x QW x 4 scalar values in flight)
+constexpr int TILED_QB = 16;  // queries per task of the tiled schedule
+constexpr int TILED_NW = TILED_QB / TILED_QW;   // waves per workgroup
+constexpr int TILED_TPS = 4;  // 64-row tiles per task of the tiled schedule (segment = 64*TPS rows)
+// a shared window (nlsh_build_cells: window_rows <= 256) must fit ONE segment: bscatter derives a window bucket's partial-list count from
+// its own size and clamps its row range to the segment, so a window wider than a segment would silently lose rows
+static_assert(64 * TILED_TPS >= 256, "the tiled schedule's segment must hold the widest row window nlsh_build_cells accepts (256 rows)");
+static_assert(NLSH_MAX_K_TILED <= 64 * TILED_TPS, "a (task, query) list is selected from the 64 * TPS candidates the wave holds");
+// The launch shape of every tiled kernel: one workgroup per task; the chunked XCD map works on 8 x 16 ids.  (Persistent workgroups and
+// several tasks per workgroup were measured slower in r02 and r04: profiles/r04_tasks_per_workgroup_ab.txt, DESIGN.md appendix A.)
+inline dim3 tiled_grid(long long max_tasks) { return dim3((unsigned)((max_tasks + 127) / 128 * 128)); }
+inline dim3 tiled_block() { return dim3(64 * TILED_NW); }
+// the instantiation K<METRIC, TILED_QW, TILED_NW, TILED_TPS, ...> of a tiled kernel template for a run-time metric
+#define NLSH_TILED_KERNEL(K, metric, ...)                                                                                                  \
+    ((metric) == NLSH_METRIC_L2_EPS          ? (const void *)K<NLSH_METRIC_L2_EPS, TILED_QW, TILED_NW, TILED_TPS, ##__VA_ARGS__>           \
+     : (metric) == NLSH_METRIC_L2_EPS_FOLDED ? (const void *)K<NLSH_METRIC_L2_EPS_FOLDED, TILED_QW, TILED_NW, TILED_TPS, ##__VA_ARGS__>    \
+                                             : (const void *)K<NLSH_METRIC_COSINE, TILED_QW, TILED_NW, TILED_TPS, ##__VA_ARGS__>)
 
 struct BArgs {
     const float *corpus;
@@ -64,8 +85,10 @@ struct RangeArgs {
     int mode;                      // NLSH_RANGE_COUNT | NLSH_RANGE_FILL (wave-uniform)
 };
 
-// BArgs of a call, as bucket_scan_run builds them (scan_bucket.hip): the radius query launches its own kernel on the plan the PLAN phase
-// of a k = 1 call left in the workspace
-int bucket_scan_bargs(const BucketScanCall &c, BArgs *a);
+// A call's prepared launch (scan_bucket.hip): the workspace held against the schedule's layout (NLSH_E_WORKSPACE), then what the scan kernels
+// take (bucket_scan_run; the radius calls for their own kernel), what the lookup takes (step.hip, probe_ranked.hip: the launch that does it),
+// the metric the schedule really computes and whether the tiled schedule needs its padded / pre-normalised query copy
+struct BucketScanPrep { BArgs a; PlanArgs pa; int metric; bool prep; };
+int bucket_scan_args(const BucketScanCall &c, BucketScanPrep *p);
 
 }  // namespace nlsh

@@ -12,13 +12,8 @@
 
 namespace nlsh {
 
-// 4 queries per wave, 4 waves, 4 row tiles: the shape tiled_task_body is written for (scan_bucket.hip: TILED_QB / 4, TILED_TPS)
 template <int STORE, bool WIDEK>
-static const void *bscanf_of(int metric) {
-    if (metric == NLSH_METRIC_L2_EPS) return (const void *)bscanf_kernel<NLSH_METRIC_L2_EPS, 4, 4, 4, STORE, WIDEK>;
-    if (metric == NLSH_METRIC_L2_EPS_FOLDED) return (const void *)bscanf_kernel<NLSH_METRIC_L2_EPS_FOLDED, 4, 4, 4, STORE, WIDEK>;
-    return (const void *)bscanf_kernel<NLSH_METRIC_COSINE, 4, 4, 4, STORE, WIDEK>;
-}
+static const void *bscanf_of(int metric) { return NLSH_TILED_KERNEL(bscanf_kernel, metric, STORE, WIDEK); }
 const void *filtered_scan_kernel_of(int storage, int metric, bool wide) {
     if (storage == NLSH_STORE_F16) return wide ? bscanf_of<NLSH_STORE_F16, true>(metric) : bscanf_of<NLSH_STORE_F16, false>(metric);
     if (storage == NLSH_STORE_U8) return wide ? bscanf_of<NLSH_STORE_U8, true>(metric) : bscanf_of<NLSH_STORE_U8, false>(metric);

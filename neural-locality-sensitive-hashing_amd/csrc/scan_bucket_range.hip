@@ -26,13 +26,8 @@
 
 namespace nlsh {
 
-// 4 queries per wave, 4 waves, 4 row tiles: the shape tiled_task_body is written for (scan_bucket.hip: TILED_QB / 4, TILED_TPS)
 template <int STORE>
-static const void *bscanr_of(int metric) {
-    if (metric == NLSH_METRIC_L2_EPS) return (const void *)bscanr_kernel<NLSH_METRIC_L2_EPS, 4, 4, 4, STORE>;
-    if (metric == NLSH_METRIC_L2_EPS_FOLDED) return (const void *)bscanr_kernel<NLSH_METRIC_L2_EPS_FOLDED, 4, 4, 4, STORE>;
-    return (const void *)bscanr_kernel<NLSH_METRIC_COSINE, 4, 4, 4, STORE>;
-}
+static const void *bscanr_of(int metric) { return NLSH_TILED_KERNEL(bscanr_kernel, metric, STORE); }
 static const void *range_scan_kernel_of(int storage, int metric) {
     if (storage == NLSH_STORE_F16) return bscanr_of<NLSH_STORE_F16>(metric);
     if (storage == NLSH_STORE_U8) return bscanr_of<NLSH_STORE_U8>(metric);
@@ -73,42 +68,13 @@ static void range_sort_layout(long long Q, long long total, RangeSortWs *w) {
     w->total = o;
 }
 
-// what both calls check before anything is launched, and the call descriptor of the k = 1 plan
-static int range_call(const char *who, const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid, const int32_t *uniq_keys,
-                      const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets, const int32_t *cell_of, const int32_t *cell_offsets,
-                      int32_t n_cells, const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys,
-                      const int32_t *nkeys, int P, int metric, int algo, const uint32_t *row_filter, const float *radius, int32_t *status,
-                      void *workspace, size_t workspace_bytes, int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream,
-                      BucketScanCall *c) {
-    NLSH_REQUIRE(storage == NLSH_STORE_F32 || storage == NLSH_STORE_F16 || storage == NLSH_STORE_U8, NLSH_E_INVALID,
-                 "%s: storage=%d is none of NLSH_STORE_F32 / F16 / U8", who, storage);
-    NLSH_REQUIRE(algo == NLSH_SCAN_QUERY_MAJOR || algo == NLSH_SCAN_BUCKET_MAJOR || algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_INVALID, "%s: algo=%d", who, algo);
-    NLSH_REQUIRE(algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_UNSUPPORTED,
-                 "%s: a radius query is scanned by the tiled schedule only (NLSH_SCAN_BUCKET_TILED), not by algo=%d", who, algo);
-    NLSH_REQUIRE(Q >= 0 && Q < (1ll << 31), NLSH_E_INVALID, "%s: Q=%lld", who, (long long)Q);
-    NLSH_REQUIRE(d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_UNSUPPORTED, "%s: d=%d not in [1,%d]", who, d, NLSH_MAX_DIM);
-    NLSH_REQUIRE(P >= 1 && P <= NLSH_MAX_PROBES, NLSH_E_UNSUPPORTED, "%s: P=%d not in [1,%d]", who, P, NLSH_MAX_PROBES);
-    NLSH_REQUIRE(metric == NLSH_METRIC_L2_EPS || metric == NLSH_METRIC_COSINE || metric == NLSH_METRIC_L2_EPS_FOLDED, NLSH_E_INVALID, "%s: metric=%d", who, metric);
-    NLSH_REQUIRE(n_buckets >= 0 && max_tasks >= 0, NLSH_E_INVALID, "%s: negative size (n_buckets=%d, max_tasks=%lld)", who, (int)n_buckets, (long long)max_tasks);
-    NLSH_REQUIRE(n_cells >= 0 && n_cells <= n_buckets && (n_cells == 0 || (cell_of && cell_offsets)), NLSH_E_INVALID,
-                 "%s: n_cells=%d needs cell_of and cell_offsets and cannot exceed n_buckets=%d", who, (int)n_cells, (int)n_buckets);
+// what both calls check before anything is launched: the one check of a scan call, on the descriptor of the k = 1 plan their kernel runs
+// on, and the argument only a radius call has
+static int range_check(const char *who, const BucketScanCall &c, const float *radius) {
+    const int rc = scan_call_check(who, c, 0);   // no top-k outputs: each call checks its own
+    if (rc != NLSH_OK) return rc;
     NLSH_REQUIRE(radius, NLSH_E_INVALID, "%s: radius is null", who);
     NLSH_REQUIRE(((uintptr_t)radius & 3) == 0, NLSH_E_INVALID, "%s: radius must be 4-byte aligned", who);
-    NLSH_REQUIRE(((uintptr_t)row_filter & 3) == 0, NLSH_E_INVALID, "%s: row_filter must be 4-byte aligned", who);
-    if (Q == 0) return NLSH_OK;
-    NLSH_REQUIRE(queries && qkeys && nkeys && status && workspace, NLSH_E_INVALID, "%s: null pointer (queries, qkeys, nkeys, status or workspace)", who);
-    NLSH_REQUIRE(n_buckets == 0 || (corpus_sorted && gid && uniq_keys && offsets), NLSH_E_INVALID, "%s: null index pointer", who);
-    NLSH_REQUIRE(metric != NLSH_METRIC_COSINE || n_buckets == 0 || inv_norm, NLSH_E_INVALID, "%s: cosine needs inv_norm", who);
-    const int per16 = storage == NLSH_STORE_F32 ? 4 : (storage == NLSH_STORE_F16 ? 8 : 16);
-    NLSH_REQUIRE(row_stride >= d && row_stride % per16 == 0 && ((uintptr_t)corpus_sorted & 15) == 0, NLSH_E_INVALID,
-                 "%s: row_stride=%lld must be >= d=%d and a multiple of %d elements for storage=%d, corpus_sorted 16-byte aligned", who,
-                 (long long)row_stride, d, per16, storage);
-    NLSH_REQUIRE(q_stride >= d, NLSH_E_INVALID, "%s: q_stride < d", who);
-    NLSH_REQUIRE(((uintptr_t)workspace & 15) == 0, NLSH_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
-    *c = BucketScanCall{(const float *)corpus_sorted, row_stride, d, gid, uniq_keys, offsets, n_buckets, inv_norm, queries, q_stride, Q,
-                        qkeys, nkeys, P, 1, metric, 512, nullptr, nullptr, nullptr, nullptr, status, workspace,
-                        workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end, (hipStream_t)stream, 1, bucket_order, NLSH_PHASE_PLAN,
-                        cell_of, cell_offsets, (int)n_cells, 0, nullptr, storage, nullptr};
     return NLSH_OK;
 }
 
@@ -120,8 +86,7 @@ static int range_scan_launch(const BucketScanCall &c, const BArgs &a, const Rang
     BArgs a_ = a;
     RangeArgs r_ = r;
     void *argv[2] = {&a_, &r_};
-    // the tiled kernels' launch shape (scan_bucket.hip: scan_kernel_of)
-    NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)((c.max_tasks + 127) / 128 * 128)), dim3(256), argv, 0, c.stream));
+    NLSH_CHECK_HIP(hipLaunchKernel(fn, tiled_grid(c.max_tasks), tiled_block(), argv, 0, c.stream));
     if (c.ev_end) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)c.ev_end, c.stream));
     return NLSH_OK;
 }
@@ -154,24 +119,25 @@ extern "C" int nlsh_range_count(const void *corpus_sorted, int storage, int64_t 
                                 const float *radius, int32_t *out_count, int32_t *out_ncand, int32_t *status, void *workspace,
                                 size_t workspace_bytes, int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream) {
     using namespace nlsh;
-    BucketScanCall c;
-    const int rc = range_call("range_count", corpus_sorted, storage, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of,
-                              cell_offsets, n_cells, inv_norm, queries, q_stride, Q, qkeys, nkeys, P, metric, algo, row_filter, radius, status,
-                              workspace, workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end, stream, &c);
+    BucketScanCall c = {};
+    NLSH_SCAN_CALL_COMMON(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells; c.storage = storage; c.row_filter = row_filter;
+    c.k = 1; c.seg = 512; c.phases = NLSH_PHASE_PLAN;   // the plan of a k = 1 call: a k = 1 partial area costs nothing and is never written
+    const int rc = range_check("range_count", c, radius);
     if (rc != NLSH_OK) return rc;
     NLSH_REQUIRE(out_count, NLSH_E_INVALID, "range_count: out_count is null");
     NLSH_REQUIRE(((uintptr_t)out_count & 3) == 0 && ((uintptr_t)out_ncand & 3) == 0, NLSH_E_INVALID, "range_count: out_count / out_ncand must be 4-byte aligned");
     if (Q == 0) return NLSH_OK;
     NLSH_REQUIRE(out_ncand, NLSH_E_INVALID, "range_count: out_ncand is null");
-    BArgs a;
-    const int ra = bucket_scan_bargs(c, &a);   // holds the workspace against the k = 1 layout
+    BucketScanPrep p;
+    const int ra = bucket_scan_args(c, &p);   // holds the workspace against the k = 1 layout
     if (ra != NLSH_OK) return ra;
     NLSH_CHECK_HIP(hipMemsetAsync(out_count, 0, (size_t)Q * sizeof(int32_t), c.stream));
     const int rp = bucket_scan_run(c);         // PLAN: status words, task table, slot records, per-probe records
     if (rp != NLSH_OK) return rp;
-    hipLaunchKernelGGL(range_ncand_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, c.stream, (const int4 *)a.prec, (long long)Q, P, out_ncand);
+    hipLaunchKernelGGL(range_ncand_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, c.stream, (const int4 *)p.a.prec, (long long)Q, P, out_ncand);
     RangeArgs r = {row_filter, radius, out_count, nullptr, nullptr, 0, NLSH_RANGE_COUNT};
-    const int rs = range_scan_launch(c, a, r);
+    const int rs = range_scan_launch(c, p.a, r);
     if (rs != NLSH_OK) return rs;
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
@@ -185,10 +151,11 @@ extern "C" int nlsh_range_fill(const void *corpus_sorted, int storage, int64_t r
                                float *out_dist, int32_t *out_idx, int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
                                void *sort_workspace, size_t sort_workspace_bytes, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream) {
     using namespace nlsh;
-    BucketScanCall c;
-    const int rc = range_call("range_fill", corpus_sorted, storage, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of,
-                              cell_offsets, n_cells, inv_norm, queries, q_stride, Q, qkeys, nkeys, P, metric, algo, row_filter, radius, status,
-                              workspace, workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end, stream, &c);
+    BucketScanCall c = {};
+    NLSH_SCAN_CALL_COMMON(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells; c.storage = storage; c.row_filter = row_filter;
+    c.k = 1; c.seg = 512; c.phases = NLSH_PHASE_PLAN;   // the plan of a k = 1 call: a k = 1 partial area costs nothing and is never written
+    const int rc = range_check("range_fill", c, radius);
     if (rc != NLSH_OK) return rc;
     NLSH_REQUIRE(row_offsets, NLSH_E_INVALID, "range_fill: row_offsets is null");
     NLSH_REQUIRE(((uintptr_t)row_offsets & 7) == 0 && ((uintptr_t)out_keys & 7) == 0, NLSH_E_INVALID, "range_fill: row_offsets / out_keys must be 8-byte aligned");
@@ -200,8 +167,8 @@ extern "C" int nlsh_range_fill(const void *corpus_sorted, int storage, int64_t r
     range_sort_layout(Q, total, &w);
     NLSH_REQUIRE(total == 0 || (sort_workspace && ((uintptr_t)sort_workspace & 15) == 0 && sort_workspace_bytes >= w.total), NLSH_E_WORKSPACE,
                  "range_fill: sort_workspace %zu < %zu (or null / not 16-byte aligned)", sort_workspace_bytes, w.total);
-    BArgs a;
-    const int ra = bucket_scan_bargs(c, &a);
+    BucketScanPrep p;
+    const int ra = bucket_scan_args(c, &p);
     if (ra != NLSH_OK) return ra;
     if (total > 0) {   // the sort's own need against the bound nlsh_range_sort_workspace sized the workspace by
         size_t need = 0;
@@ -215,7 +182,7 @@ extern "C" int nlsh_range_fill(const void *corpus_sorted, int storage, int64_t r
     char *sb = (char *)sort_workspace;
     uint64_t *unsorted = (uint64_t *)(sb + w.unsorted), *sorted = out_keys ? out_keys : (uint64_t *)(sb + w.sorted);
     RangeArgs r = {row_filter, radius, cursor, row_offsets, unsorted, (long long)total, NLSH_RANGE_FILL};
-    const int rs = range_scan_launch(c, a, r);
+    const int rs = range_scan_launch(c, p.a, r);
     if (rs != NLSH_OK) return rs;
     size_t tb = w.tmp_bytes;
     NLSH_CHECK_HIP(rocprim::segmented_radix_sort_keys(sb + w.tmp, tb, unsorted, sorted, (unsigned)total, (unsigned)Q, row_offsets, row_offsets + 1, 0, 64, c.stream));

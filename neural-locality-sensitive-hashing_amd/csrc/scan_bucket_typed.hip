@@ -11,13 +11,8 @@
 
 namespace nlsh {
 
-// 4 queries per wave, 4 waves, 4 row tiles: the shape tiled_task_body is written for (scan_bucket.hip: TILED_QB / 4, TILED_TPS)
 template <int STORE, bool WIDEK>
-static const void *bscant_of(int metric) {
-    if (metric == NLSH_METRIC_L2_EPS) return (const void *)bscant_kernel<NLSH_METRIC_L2_EPS, 4, 4, 4, STORE, WIDEK>;
-    if (metric == NLSH_METRIC_L2_EPS_FOLDED) return (const void *)bscant_kernel<NLSH_METRIC_L2_EPS_FOLDED, 4, 4, 4, STORE, WIDEK>;
-    return (const void *)bscant_kernel<NLSH_METRIC_COSINE, 4, 4, 4, STORE, WIDEK>;
-}
+static const void *bscant_of(int metric) { return NLSH_TILED_KERNEL(bscant_kernel, metric, STORE, WIDEK); }
 const void *typed_scan_kernel_of(int storage, int metric, bool wide) {
     if (storage == NLSH_STORE_F16) return wide ? bscant_of<NLSH_STORE_F16, true>(metric) : bscant_of<NLSH_STORE_F16, false>(metric);
     return wide ? bscant_of<NLSH_STORE_U8, true>(metric) : bscant_of<NLSH_STORE_U8, false>(metric);

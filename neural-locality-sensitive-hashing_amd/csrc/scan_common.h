@@ -415,14 +415,18 @@ __device__ __forceinline__ float finish_distance(float acc, float inv_norm) {
 
 static inline size_t ws_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// entry point of the bucket-major algorithm (scan_bucket.hip)
+// One scan call, for all three schedules: what every C entry point (scan_topk.hip, scan_bucket_range.hip) and every batch of a step
+// descriptor (step.hip) fills by member name, scan_call_check checks and scan_call_run enqueues.  Start from `BucketScanCall c = {}`.
 struct BucketScanCall {
     const float *corpus; long long row_stride; int d; const int32_t *gid; const int32_t *uniq; const int32_t *offsets; int nb;
     const float *inv_norm; const float *queries; long long q_stride; long long Q; const int32_t *qkeys; const int32_t *nkeys;
-    int P, k, metric, seg; float *out_dist; int32_t *out_idx; uint64_t *out_keys; int32_t *out_ncand; int32_t *status;
-    void *workspace; size_t workspace_bytes; long long max_tasks; void *ev_begin; void *ev_end; hipStream_t stream; int tiled;
+    int P, k, metric;
+    int algo;                     // NLSH_SCAN_*: the schedule; set here and nowhere else (tiled() below is what the bucket-major code asks)
+    int seg;                      // seg_rows as the caller gave them (0 = default): scan_seg_rows() is what the two non-tiled schedules cut by
+    float *out_dist; int32_t *out_idx; uint64_t *out_keys; int32_t *out_ncand; int32_t *status;
+    void *workspace; size_t workspace_bytes; long long max_tasks; void *ev_begin; void *ev_end; hipStream_t stream;
     const int32_t *bucket_order;  // nlsh_bucket_order output (nlsh_build_cells' cell_order when cells are given) or nullptr
-    int phases;                   // NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE
+    int phases;                   // NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE (| NLSH_PHASE_PLAN_REST, step.hip only)
     const int32_t *cell_of;       // nlsh_build_cells outputs, or nullptr / 0: every bucket is its own cell
     const int32_t *cell_offsets;
     int n_cells;
@@ -430,31 +434,40 @@ struct BucketScanCall {
     int32_t *host_out;            // nlsh_query_batch_host: the MERGE phase (k <= NLSH_MAX_K) stores its results into this host-visible block
                                   // (layout: bmerge_host_kernel) instead of out_dist / out_idx / out_ncand; nullptr everywhere else
     int storage;                  // NLSH_STORE_*: what `corpus` really points to (row_stride in elements); anything but F32 is the tiled
-                                  // schedule's alone and set by nlsh_scan_topk_cells_phase_typed only (0 = F32 everywhere else)
-    const uint32_t *row_filter;   // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: the tiled schedule's alone, set by
-                                  // nlsh_scan_topk_cells_phase_filtered only; the SCAN phase then launches a filtered kernel, which takes
-                                  // the pointer as a second parameter (BArgs does not hold it)
+                                  // schedule's alone (0 = F32 for every entry without a storage argument)
+    const uint32_t *row_filter;   // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: the tiled schedule's alone; the SCAN phase
+                                  // then launches a filtered kernel, which takes the pointer as a second parameter (BArgs does not hold it)
+    bool tiled() const { return algo == NLSH_SCAN_BUCKET_TILED; }
 };
 // internal phase bit (not part of the C ABI's phase mask): the PLAN phase WITHOUT the bucket lookup, which the batch's encode_hash
 // launch already did in its epilogue (scan_plan.h, encode_plan_fuse_lookup): bscan + bscatter only
 #define NLSH_PHASE_PLAN_REST 8
-struct PlanArgs;
+inline int scan_seg_rows(int seg_rows) { return ((seg_rows ? seg_rows : 512) + 63) / 64 * 64; }
+
+// The members every scan entry point of the C ABI has, under the parameter names the header gives them: the one place they are copied.
+#define NLSH_SCAN_CALL_COMMON(c)                                                                                                         \
+    (c).corpus = (const float *)corpus_sorted; (c).row_stride = row_stride; (c).d = d; (c).gid = gid; (c).uniq = uniq_keys;              \
+    (c).offsets = offsets; (c).nb = n_buckets; (c).bucket_order = bucket_order; (c).inv_norm = inv_norm; (c).queries = queries;           \
+    (c).q_stride = q_stride; (c).Q = Q; (c).qkeys = qkeys; (c).nkeys = nkeys; (c).P = P; (c).metric = metric; (c).algo = algo;            \
+    (c).status = status; (c).workspace = workspace; (c).workspace_bytes = workspace_bytes; (c).max_tasks = max_tasks;                     \
+    (c).ev_begin = ev_scan_begin; (c).ev_end = ev_scan_end; (c).stream = (hipStream_t)stream
+
+// THE argument check of a scan call (scan_topk.hip): limits, schedule, storage, filter, null pointers, strides and alignments, for every
+// entry.  Host arithmetic only, before anything is enqueued; `who` prefixes the message.  An empty batch (Q == 0) passes without its
+// pointers being looked at: the caller returns NLSH_OK for it after its own checks.
+enum : unsigned {
+    SCAN_NEEDS_TOPK_OUT = 1,      // out_dist, out_idx and out_ncand are written (every top-k call; a radius call has outputs of its own)
+    SCAN_ALLOWS_PLAN_REST = 2,    // the internal phase bit may be set (step.hip); the C ABI's phase mask ends at NLSH_PHASE_MERGE
+};
+int scan_call_check(const char *who, const BucketScanCall &c, unsigned needs);
 size_t bucket_scan_workspace(long long Q, int P, int k, long long max_tasks, long long n_buckets, int d);
-int bucket_scan_run(const BucketScanCall &c);
-int bucket_scan_plan_args(const BucketScanCall &c, PlanArgs *pa);   // the lookup's arguments for this call's workspace
+int query_major_workspace(const BucketScanCall &c);   // holds workspace_bytes against the query-major layout
+int query_major_run(const BucketScanCall &c);         // scan_topk.hip
+int bucket_scan_run(const BucketScanCall &c);         // scan_bucket.hip
+inline int scan_call_run(const BucketScanCall &c) { return c.algo == NLSH_SCAN_QUERY_MAJOR ? query_major_run(c) : bucket_scan_run(c); }
 // the tiled scan kernel over a float16 / uint8 corpus (scan_bucket_typed.hip): storage NLSH_STORE_F16 | NLSH_STORE_U8, wide = k > NLSH_MAX_K
 const void *typed_scan_kernel_of(int storage, int metric, bool wide);
 // the tiled scan kernel behind a row filter (scan_bucket_filtered.hip): any storage; its parameters are (BArgs, const uint32_t *row_filter)
 const void *filtered_scan_kernel_of(int storage, int metric, bool wide);
-
-// nlsh_scan_topk_cells_phase after argument validation, with the internal phase bit allowed; `call_out` (nullable) receives the
-// bucket-major call descriptor instead of running it (step.hip builds the fused lookup's arguments from it)
-int scan_topk_cells_phase_checked(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid, const int32_t *uniq_keys,
-                                  const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets, const int32_t *cell_of,
-                                  const int32_t *cell_offsets, int32_t n_cells, const float *inv_norm, const float *queries, int64_t q_stride,
-                                  int64_t Q, const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows,
-                                  float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace,
-                                  size_t workspace_bytes, int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream,
-                                  int phases, int plan_blocks, BucketScanCall *call_out);
 
 }  // namespace nlsh

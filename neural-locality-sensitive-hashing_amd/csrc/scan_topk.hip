@@ -311,6 +311,108 @@ static void launch_scan(const ScanArgs &a, int d4, unsigned grid, hipStream_t s)
     else hipLaunchKernelGGL((scan_kernel<64, 4, METRIC>), dim3(grid), dim3(256), 0, s, a);
 }
 
+// ScanArgs of a call: the query-major layout of its workspace, held against workspace_bytes
+static int query_major_args(const BucketScanCall &c, ScanArgs *args) {
+    ScanWs w;
+    scan_layout(c.Q, c.P, c.k, c.max_tasks, &w);
+    NLSH_REQUIRE(c.workspace_bytes >= w.total, NLSH_E_WORKSPACE, "scan_topk: workspace %zu < %zu", c.workspace_bytes, w.total);
+    ScanArgs &a = *args;
+    a.corpus = c.corpus; a.row_stride = c.row_stride; a.d = c.d; a.gid = c.gid; a.uniq = c.uniq; a.offsets = c.offsets;
+    a.nb = c.nb; a.inv_norm = c.inv_norm; a.queries = c.queries; a.q_stride = c.q_stride; a.Q = c.Q; a.qkeys = c.qkeys;
+    a.nkeys = c.nkeys; a.P = c.P; a.k = c.k; a.seg = scan_seg_rows(c.seg); a.out_dist = c.out_dist; a.out_idx = c.out_idx;
+    a.out_keys = c.out_keys; a.out_ncand = c.out_ncand; a.status = c.status; a.max_tasks = c.max_tasks;
+    // the folded form exists in the tiled schedule only; the exact form is inside its tolerance
+    a.metric = c.metric == NLSH_METRIC_L2_EPS_FOLDED ? NLSH_METRIC_L2_EPS : c.metric;
+    char *base = (char *)c.workspace;
+    a.pstart = (int32_t *)(base + w.pstart); a.pcum = (int32_t *)(base + w.pcum); a.nseg = (int32_t *)(base + w.nseg);
+    a.tbase = (int32_t *)(base + w.tbase); a.task_q = (int32_t *)(base + w.task_q); a.task_s = (int32_t *)(base + w.task_s);
+    a.partial = (uint64_t *)(base + w.partial);
+    return NLSH_OK;
+}
+
+int query_major_workspace(const BucketScanCall &c) {
+    ScanArgs a;
+    return query_major_args(c, &a);
+}
+
+// The query-major schedule of a checked call: plan, scan, merge (bucket_scan_run is the same for the two bucket-major schedules)
+int query_major_run(const BucketScanCall &c) {
+    ScanArgs a;
+    const int rc = query_major_args(c, &a);
+    if (rc != NLSH_OK) return rc;
+    hipStream_t s = c.stream;
+    if (c.phases & NLSH_PHASE_PLAN) {
+        NLSH_CHECK_HIP(hipMemsetAsync(c.status, 0, 2 * sizeof(int32_t), s));
+        hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((c.Q + 255) / 256)), dim3(256), 0, s, a);
+    }
+    if ((c.phases & NLSH_PHASE_SCAN) && c.max_tasks > 0) {
+        const unsigned grid = (unsigned)((c.max_tasks + 3) / 4);
+        const int d4 = (c.d + 3) / 4;
+        if (c.ev_begin) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)c.ev_begin, s));
+        if (a.metric == NLSH_METRIC_L2_EPS) launch_scan<NLSH_METRIC_L2_EPS>(a, d4, grid, s);
+        else launch_scan<NLSH_METRIC_COSINE>(a, d4, grid, s);
+        if (c.ev_end) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)c.ev_end, s));
+    }
+    if ((c.phases & NLSH_PHASE_MERGE) && c.max_tasks > 0)
+        hipLaunchKernelGGL(merge_segments_kernel, dim3((unsigned)((c.Q + 3) / 4)), dim3(256), 0, s, a);
+    NLSH_CHECK_HIP(hipGetLastError());
+    return NLSH_OK;
+}
+
+// the pitch of the corpus rows: a multiple of 16 bytes -- 4 float32 / 8 float16 / 16 uint8 elements -- from a 16-byte aligned base
+static int corpus_pitch_check(const char *who, const BucketScanCall &c) {
+    const int per16 = c.storage == NLSH_STORE_F32 ? 4 : (c.storage == NLSH_STORE_F16 ? 8 : 16);
+    NLSH_REQUIRE(c.row_stride >= c.d && c.row_stride % per16 == 0, NLSH_E_INVALID, "%s: row_stride=%lld must be >= d=%d and a multiple of %d elements "
+                 "(a pitch of 16-byte units) for storage=%d", who, c.row_stride, c.d, per16, c.storage);
+    NLSH_REQUIRE(((uintptr_t)c.corpus & 15) == 0, NLSH_E_INVALID, "%s: corpus_sorted must be 16-byte aligned", who);
+    return NLSH_OK;
+}
+
+int scan_call_check(const char *who, const BucketScanCall &c, unsigned needs) {
+    const bool topk = (needs & SCAN_NEEDS_TOPK_OUT) != 0;
+    int rc;
+    const int phase_max = NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE | ((needs & SCAN_ALLOWS_PLAN_REST) ? NLSH_PHASE_PLAN_REST : 0);
+    const int both_plans = NLSH_PHASE_PLAN | NLSH_PHASE_PLAN_REST;
+    NLSH_REQUIRE(c.storage >= NLSH_STORE_F32 && c.storage <= NLSH_STORE_U8, NLSH_E_INVALID, "%s: storage=%d is none of NLSH_STORE_F32 / F16 / U8", who, c.storage);
+    NLSH_REQUIRE(c.phases >= 1 && c.phases <= phase_max && (c.phases & both_plans) != both_plans, NLSH_E_INVALID, "%s: phases=%d", who, c.phases);
+    NLSH_REQUIRE(c.algo == NLSH_SCAN_QUERY_MAJOR || c.algo == NLSH_SCAN_BUCKET_MAJOR || c.tiled(), NLSH_E_INVALID, "%s: algo=%d", who, c.algo);
+    NLSH_REQUIRE(!(c.phases & NLSH_PHASE_PLAN_REST) || c.algo != NLSH_SCAN_QUERY_MAJOR, NLSH_E_INVALID, "%s: the query-major schedule has no fused lookup", who);
+    // what the tiled schedule alone can do
+    const char *tiled_only = "the tiled schedule only (NLSH_SCAN_BUCKET_TILED)";
+    NLSH_REQUIRE(topk || c.tiled(), NLSH_E_UNSUPPORTED, "%s: a radius query is scanned by %s, not by algo=%d", who, tiled_only, c.algo);
+    NLSH_REQUIRE(!c.row_filter || c.tiled(), NLSH_E_UNSUPPORTED, "%s: row_filter is read by %s, not by algo=%d", who, tiled_only, c.algo);
+    NLSH_REQUIRE(c.storage == NLSH_STORE_F32 || c.tiled(), NLSH_E_UNSUPPORTED, "%s: a %s corpus (storage=%d) is read by %s, not by algo=%d", who,
+                 c.storage == NLSH_STORE_F16 ? "float16" : "uint8", c.storage, tiled_only, c.algo);
+    NLSH_REQUIRE(((uintptr_t)c.row_filter & 3) == 0, NLSH_E_INVALID, "%s: row_filter must be 4-byte aligned", who);
+    // A compressed copy's pitch is held HERE for the top-k calls, ahead of the limits and of the empty batch, as the typed entry always
+    // did; float32 rows and the radius calls have theirs held behind both, below: each entry keeps the code it had.
+    const bool pitch_first = topk && c.storage != NLSH_STORE_F32;
+    if (pitch_first && (rc = corpus_pitch_check(who, c)) != NLSH_OK) return rc;
+    NLSH_REQUIRE(c.Q >= 0 && c.Q < (1ll << 31), NLSH_E_INVALID, "%s: Q=%lld", who, c.Q);
+    NLSH_REQUIRE(c.d >= 1 && c.d <= NLSH_MAX_DIM, NLSH_E_UNSUPPORTED, "%s: d=%d not in [1,%d]", who, c.d, NLSH_MAX_DIM);
+    // one key per lane is built into the running top-k of the query-major and the wave-level bucket-major schedules; the tiled schedule
+    // selects a list from the 64 * TPS = 256 candidates a wave holds
+    NLSH_REQUIRE(c.k >= 1 && c.k <= (c.tiled() ? NLSH_MAX_K_TILED : NLSH_MAX_K), NLSH_E_UNSUPPORTED,
+                 "%s: k=%d not supported by algo=%d: every schedule takes k in [1,%d], only the tiled schedule (NLSH_SCAN_BUCKET_TILED, "
+                 "algo=\"tiled\" in the Python facade) takes k in [1,%d]", who, c.k, c.algo, NLSH_MAX_K, NLSH_MAX_K_TILED);
+    NLSH_REQUIRE(c.P >= 1 && c.P <= NLSH_MAX_PROBES, NLSH_E_UNSUPPORTED, "%s: P=%d not in [1,%d]", who, c.P, NLSH_MAX_PROBES);
+    NLSH_REQUIRE(c.metric >= NLSH_METRIC_L2_EPS && c.metric <= NLSH_METRIC_L2_EPS_FOLDED, NLSH_E_INVALID, "%s: metric=%d", who, c.metric);
+    NLSH_REQUIRE(c.nb >= 0 && c.max_tasks >= 0 && c.seg >= 0, NLSH_E_INVALID, "%s: negative size (n_buckets=%d, max_tasks=%lld, seg_rows=%d)", who, c.nb, c.max_tasks, c.seg);
+    NLSH_REQUIRE(c.n_cells >= 0 && c.n_cells <= c.nb && (c.n_cells == 0 || (c.cell_of && c.cell_offsets)), NLSH_E_INVALID,
+                 "%s: n_cells=%d needs cell_of and cell_offsets and cannot exceed n_buckets=%d", who, c.n_cells, c.nb);
+    if (c.Q == 0) return NLSH_OK;
+    NLSH_REQUIRE(c.queries && c.qkeys && c.nkeys && c.status && c.workspace, NLSH_E_INVALID, "%s: null pointer (queries, qkeys, nkeys, status or workspace)", who);
+    NLSH_REQUIRE(!topk || (c.out_dist && c.out_idx && c.out_ncand), NLSH_E_INVALID, "%s: null pointer (out_dist, out_idx or out_ncand)", who);
+    NLSH_REQUIRE(c.nb == 0 || (c.corpus && c.gid && c.uniq && c.offsets), NLSH_E_INVALID, "%s: null index pointer", who);
+    NLSH_REQUIRE(c.metric != NLSH_METRIC_COSINE || c.nb == 0 || c.inv_norm, NLSH_E_INVALID, "%s: cosine needs inv_norm", who);
+    if (!pitch_first && (rc = corpus_pitch_check(who, c)) != NLSH_OK) return rc;
+    NLSH_REQUIRE(c.q_stride >= c.d, NLSH_E_INVALID, "%s: q_stride=%lld < d=%d", who, c.q_stride, c.d);
+    // the task table and the partial lists are read with 16- and 8-byte accesses at 256-byte offsets of the workspace
+    NLSH_REQUIRE(((uintptr_t)c.workspace & 15) == 0 && ((uintptr_t)c.out_keys & 7) == 0, NLSH_E_INVALID,
+                 "%s: the workspace must be 16-byte aligned and out_keys 8-byte aligned", who);
+    return NLSH_OK;
+}
+
 }  // namespace nlsh
 
 using namespace nlsh;
@@ -323,6 +425,40 @@ extern "C" size_t nlsh_scan_workspace(int64_t Q, int P, int k, int64_t max_tasks
     return w.total > b ? w.total : b;
 }
 
+// The five top-k entry points: fill, check, run.  The descriptor with what they all have, under the header's parameter names:
+#define NLSH_TOPK_CALL(c)                                                                                                          \
+    BucketScanCall c = {};                                                                                                         \
+    NLSH_SCAN_CALL_COMMON(c);                                                                                                      \
+    c.k = k; c.seg = seg_rows; c.out_dist = out_dist; c.out_idx = out_idx; c.out_keys = out_keys; c.out_ncand = out_ncand
+static int topk_call(const char *who, const BucketScanCall &c) {
+    const int rc = scan_call_check(who, c, SCAN_NEEDS_TOPK_OUT);
+    if (rc != NLSH_OK || c.Q == 0) return rc;
+    return scan_call_run(c);
+}
+
+extern "C" int nlsh_scan_topk(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid,
+                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys,
+                              const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows, float *out_dist,
+                              int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace,
+                              size_t workspace_bytes, int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end,
+                              nlsh_stream_t stream) {
+    NLSH_TOPK_CALL(c);
+    c.phases = NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE;
+    return topk_call("scan_topk", c);
+}
+
+extern "C" int nlsh_scan_topk_phase(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid,
+                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
+                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
+                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
+                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases) {
+    NLSH_TOPK_CALL(c);
+    c.phases = phases;
+    return topk_call("scan_topk_phase", c);
+}
+
 extern "C" int nlsh_scan_topk_cells_phase(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid,
                               const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
                               const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
@@ -330,90 +466,10 @@ extern "C" int nlsh_scan_topk_cells_phase(const float *corpus_sorted, int64_t ro
                               int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
                               uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
                               int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases) {
-    NLSH_REQUIRE(phases >= 1 && phases <= (NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE), NLSH_E_INVALID, "scan_topk: phases=%d", phases);
-    return nlsh::scan_topk_cells_phase_checked(corpus_sorted, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of, cell_offsets, n_cells,
-                                               inv_norm, queries, q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows, out_dist, out_idx, out_keys,
-                                               out_ncand, status, workspace, workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end, stream, phases, 0,
-                                               nullptr);
-}
-
-int nlsh::scan_topk_cells_phase_checked(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid, const int32_t *uniq_keys,
-                                        const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets, const int32_t *cell_of,
-                                        const int32_t *cell_offsets, int32_t n_cells, const float *inv_norm, const float *queries,
-                                        int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric,
-                                        int algo, int seg_rows, float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand,
-                                        int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks, void *ev_scan_begin,
-                                        void *ev_scan_end, nlsh_stream_t stream, int phases, int plan_blocks, BucketScanCall *call_out) {
-    NLSH_REQUIRE(phases >= 1 && phases <= 15 && !((phases & NLSH_PHASE_PLAN) && (phases & NLSH_PHASE_PLAN_REST)), NLSH_E_INVALID, "scan_topk: phases=%d", phases);
-    NLSH_REQUIRE(!(phases & NLSH_PHASE_PLAN_REST) || algo != NLSH_SCAN_QUERY_MAJOR, NLSH_E_INVALID, "scan_topk: the query-major schedule has no fused lookup");
-    NLSH_REQUIRE(Q >= 0 && Q < (1ll << 31), NLSH_E_INVALID, "scan_topk: Q=%lld", (long long)Q);
-    NLSH_REQUIRE(d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_UNSUPPORTED, "scan_topk: d=%d not in [1,%d]", d, NLSH_MAX_DIM);
-    // one key per lane is built into the running top-k of the query-major and the wave-level bucket-major schedules; the tiled schedule
-    // selects a list from the 64 * TPS = 256 candidates a wave holds
-    NLSH_REQUIRE(k >= 1 && k <= (algo == NLSH_SCAN_BUCKET_TILED ? NLSH_MAX_K_TILED : NLSH_MAX_K), NLSH_E_UNSUPPORTED,
-                 "scan_topk: k=%d not supported by algo=%d: every schedule takes k in [1,%d], only the tiled schedule (NLSH_SCAN_BUCKET_TILED, "
-                 "algo=\"tiled\" in the Python facade) takes k in [1,%d]", k, algo, NLSH_MAX_K, NLSH_MAX_K_TILED);
-    NLSH_REQUIRE(P >= 1 && P <= NLSH_MAX_PROBES, NLSH_E_UNSUPPORTED, "scan_topk: P=%d not in [1,%d]", P, NLSH_MAX_PROBES);
-    NLSH_REQUIRE(metric == NLSH_METRIC_L2_EPS || metric == NLSH_METRIC_COSINE || metric == NLSH_METRIC_L2_EPS_FOLDED, NLSH_E_INVALID, "scan_topk: metric=%d", metric);
-    NLSH_REQUIRE(algo == NLSH_SCAN_QUERY_MAJOR || algo == NLSH_SCAN_BUCKET_MAJOR || algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_INVALID,
-                 "scan_topk: algo=%d", algo);
-    NLSH_REQUIRE(n_buckets >= 0 && max_tasks >= 0 && seg_rows >= 0, NLSH_E_INVALID, "scan_topk: negative size");
-    NLSH_REQUIRE(n_cells >= 0 && n_cells <= n_buckets && (n_cells == 0 || (cell_of && cell_offsets)), NLSH_E_INVALID,
-                 "scan_topk: n_cells=%d needs cell_of and cell_offsets and cannot exceed n_buckets=%d", (int)n_cells, (int)n_buckets);
-    if (Q == 0) return NLSH_OK;
-    NLSH_REQUIRE(queries && qkeys && nkeys && out_dist && out_idx && out_ncand && status && workspace, NLSH_E_INVALID, "scan_topk: null pointer");
-    NLSH_REQUIRE(n_buckets == 0 || (corpus_sorted && gid && uniq_keys && offsets), NLSH_E_INVALID, "scan_topk: null index pointer");
-    NLSH_REQUIRE(metric != NLSH_METRIC_COSINE || n_buckets == 0 || inv_norm, NLSH_E_INVALID, "scan_topk: cosine needs inv_norm");
-    NLSH_REQUIRE((row_stride & 3) == 0 && row_stride >= d && ((uintptr_t)corpus_sorted & 15) == 0, NLSH_E_INVALID,
-                 "scan_topk: row_stride=%lld must be a multiple of 4 and >= d, corpus 16-byte aligned", (long long)row_stride);
-    NLSH_REQUIRE(q_stride >= d, NLSH_E_INVALID, "scan_topk: q_stride < d");
-    // the task table and the partial lists are read with 16- and 8-byte accesses at 256-byte offsets of the workspace
-    NLSH_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)out_keys & 7) == 0, NLSH_E_INVALID,
-                 "scan_topk: the workspace must be 16-byte aligned and out_keys 8-byte aligned");
-    if (seg_rows == 0) seg_rows = 512;
-    seg_rows = (seg_rows + 63) / 64 * 64;
-    hipStream_t s = (hipStream_t)stream;
-
-    if (algo != NLSH_SCAN_QUERY_MAJOR) {
-        BucketScanCall c = {corpus_sorted, row_stride, d, gid, uniq_keys, offsets, n_buckets, inv_norm, queries, q_stride, Q,
-                            qkeys, nkeys, P, k, metric, seg_rows, out_dist, out_idx, out_keys, out_ncand, status, workspace,
-                            workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end, s, algo == NLSH_SCAN_BUCKET_TILED, bucket_order, phases,
-                            cell_of, cell_offsets, (int)n_cells, plan_blocks, nullptr};
-        if (call_out) { *call_out = c; return NLSH_OK; }
-        return bucket_scan_run(c);
-    }
-    NLSH_REQUIRE(call_out == nullptr, NLSH_E_INVALID, "scan_topk: the query-major schedule has no call descriptor");
-
-    if (metric == NLSH_METRIC_L2_EPS_FOLDED) metric = NLSH_METRIC_L2_EPS;   // the folded form exists in the tiled schedule only; the exact form is inside its tolerance
-    ScanWs w;
-    scan_layout(Q, P, k, max_tasks, &w);
-    NLSH_REQUIRE(workspace_bytes >= w.total, NLSH_E_WORKSPACE, "scan_topk: workspace %zu < %zu", workspace_bytes, w.total);
-    ScanArgs a;
-    a.corpus = corpus_sorted; a.row_stride = row_stride; a.d = d; a.gid = gid; a.uniq = uniq_keys; a.offsets = offsets;
-    a.nb = n_buckets; a.inv_norm = inv_norm; a.queries = queries; a.q_stride = q_stride; a.Q = Q; a.qkeys = qkeys;
-    a.nkeys = nkeys; a.P = P; a.k = k; a.metric = metric; a.seg = seg_rows; a.out_dist = out_dist; a.out_idx = out_idx;
-    a.out_keys = out_keys; a.out_ncand = out_ncand; a.status = status; a.max_tasks = max_tasks;
-    char *base = (char *)workspace;
-    a.pstart = (int32_t *)(base + w.pstart); a.pcum = (int32_t *)(base + w.pcum); a.nseg = (int32_t *)(base + w.nseg);
-    a.tbase = (int32_t *)(base + w.tbase); a.task_q = (int32_t *)(base + w.task_q); a.task_s = (int32_t *)(base + w.task_s);
-    a.partial = (uint64_t *)(base + w.partial);
-
-    if (phases & NLSH_PHASE_PLAN) {
-        NLSH_CHECK_HIP(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), s));
-        hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, a);
-    }
-    if ((phases & NLSH_PHASE_SCAN) && max_tasks > 0) {
-        const unsigned grid = (unsigned)((max_tasks + 3) / 4);
-        const int d4 = (d + 3) / 4;
-        if (ev_scan_begin) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)ev_scan_begin, s));
-        if (metric == NLSH_METRIC_L2_EPS) launch_scan<NLSH_METRIC_L2_EPS>(a, d4, grid, s);
-        else launch_scan<NLSH_METRIC_COSINE>(a, d4, grid, s);
-        if (ev_scan_end) NLSH_CHECK_HIP(hipEventRecord((hipEvent_t)ev_scan_end, s));
-    }
-    if ((phases & NLSH_PHASE_MERGE) && max_tasks > 0)
-        hipLaunchKernelGGL(merge_segments_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, a);
-    NLSH_CHECK_HIP(hipGetLastError());
-    return NLSH_OK;
+    NLSH_TOPK_CALL(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
+    c.phases = phases;
+    return topk_call("scan_topk_cells_phase", c);
 }
 
 extern "C" int nlsh_scan_topk_cells_phase_typed(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
@@ -423,33 +479,10 @@ extern "C" int nlsh_scan_topk_cells_phase_typed(const void *corpus_sorted, int s
                               int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
                               uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
                               int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases) {
-    NLSH_REQUIRE(storage == NLSH_STORE_F32 || storage == NLSH_STORE_F16 || storage == NLSH_STORE_U8, NLSH_E_INVALID,
-                 "scan_topk_typed: storage=%d is none of NLSH_STORE_F32 / F16 / U8", storage);
-    if (storage == NLSH_STORE_F32)
-        return nlsh_scan_topk_cells_phase((const float *)corpus_sorted, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of,
-                                          cell_offsets, n_cells, inv_norm, queries, q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows, out_dist,
-                                          out_idx, out_keys, out_ncand, status, workspace, workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end,
-                                          stream, phases);
-    NLSH_REQUIRE(phases >= 1 && phases <= (NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE), NLSH_E_INVALID, "scan_topk_typed: phases=%d", phases);
-    NLSH_REQUIRE(algo == NLSH_SCAN_QUERY_MAJOR || algo == NLSH_SCAN_BUCKET_MAJOR || algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_INVALID,
-                 "scan_topk_typed: algo=%d", algo);
-    NLSH_REQUIRE(algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_UNSUPPORTED,
-                 "scan_topk_typed: a %s corpus (storage=%d) is read by the tiled schedule only (NLSH_SCAN_BUCKET_TILED), not by algo=%d",
-                 storage == NLSH_STORE_F16 ? "float16" : "uint8", storage, algo);
-    // the pitch in bytes is a multiple of 16: 8 float16 / 16 uint8 elements (the checks below hold row_stride against d and 4)
-    const int per16 = storage == NLSH_STORE_F16 ? 8 : 16;
-    NLSH_REQUIRE(row_stride >= d && row_stride % per16 == 0, NLSH_E_INVALID,
-                 "scan_topk_typed: row_stride=%lld must be >= d=%d and a multiple of %d elements (a pitch of 16-byte units) for storage=%d",
-                 (long long)row_stride, d, per16, storage);
-    NLSH_REQUIRE(((uintptr_t)corpus_sorted & 15) == 0, NLSH_E_INVALID, "scan_topk_typed: corpus_sorted must be 16-byte aligned");
-    BucketScanCall c;
-    const int rc = nlsh::scan_topk_cells_phase_checked((const float *)corpus_sorted, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of,
-                                                       cell_offsets, n_cells, inv_norm, queries, q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows,
-                                                       out_dist, out_idx, out_keys, out_ncand, status, workspace, workspace_bytes, max_tasks,
-                                                       ev_scan_begin, ev_scan_end, stream, phases, 0, &c);
-    if (rc != NLSH_OK || Q == 0) return rc;
-    c.storage = storage;
-    return bucket_scan_run(c);
+    NLSH_TOPK_CALL(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
+    c.phases = phases; c.storage = storage;
+    return topk_call("scan_topk_typed", c);
 }
 
 extern "C" int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
@@ -460,59 +493,11 @@ extern "C" int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, in
                               uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
                               int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
                               const uint32_t *row_filter) {
-    if (!row_filter)   // no filter: the typed call, argument for argument
-        return nlsh_scan_topk_cells_phase_typed(corpus_sorted, storage, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of,
-                                                cell_offsets, n_cells, inv_norm, queries, q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows,
-                                                out_dist, out_idx, out_keys, out_ncand, status, workspace, workspace_bytes, max_tasks,
-                                                ev_scan_begin, ev_scan_end, stream, phases);
-    NLSH_REQUIRE(storage == NLSH_STORE_F32 || storage == NLSH_STORE_F16 || storage == NLSH_STORE_U8, NLSH_E_INVALID,
-                 "scan_topk_filtered: storage=%d is none of NLSH_STORE_F32 / F16 / U8", storage);
-    NLSH_REQUIRE(phases >= 1 && phases <= (NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE), NLSH_E_INVALID, "scan_topk_filtered: phases=%d", phases);
-    NLSH_REQUIRE(algo == NLSH_SCAN_QUERY_MAJOR || algo == NLSH_SCAN_BUCKET_MAJOR || algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_INVALID,
-                 "scan_topk_filtered: algo=%d", algo);
-    NLSH_REQUIRE(algo == NLSH_SCAN_BUCKET_TILED, NLSH_E_UNSUPPORTED,
-                 "scan_topk_filtered: row_filter is read by the tiled schedule only (NLSH_SCAN_BUCKET_TILED), not by algo=%d", algo);
-    NLSH_REQUIRE(((uintptr_t)row_filter & 3) == 0, NLSH_E_INVALID, "scan_topk_filtered: row_filter must be 4-byte aligned");
-    if (storage != NLSH_STORE_F32) {   // the typed call's checks of a compressed copy (the float32 pitch is held against d and 4 below)
-        const int per16 = storage == NLSH_STORE_F16 ? 8 : 16;
-        NLSH_REQUIRE(row_stride >= d && row_stride % per16 == 0, NLSH_E_INVALID,
-                     "scan_topk_filtered: row_stride=%lld must be >= d=%d and a multiple of %d elements (a pitch of 16-byte units) for storage=%d",
-                     (long long)row_stride, d, per16, storage);
-        NLSH_REQUIRE(((uintptr_t)corpus_sorted & 15) == 0, NLSH_E_INVALID, "scan_topk_filtered: corpus_sorted must be 16-byte aligned");
-    }
-    BucketScanCall c;
-    const int rc = nlsh::scan_topk_cells_phase_checked((const float *)corpus_sorted, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of,
-                                                       cell_offsets, n_cells, inv_norm, queries, q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows,
-                                                       out_dist, out_idx, out_keys, out_ncand, status, workspace, workspace_bytes, max_tasks,
-                                                       ev_scan_begin, ev_scan_end, stream, phases, 0, &c);
-    if (rc != NLSH_OK || Q == 0) return rc;
-    c.storage = storage;
-    c.row_filter = row_filter;
-    return bucket_scan_run(c);
-}
-
-extern "C" int nlsh_scan_topk_phase(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid,
-                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
-                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
-                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
-                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
-                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases) {
-    return nlsh_scan_topk_cells_phase(corpus_sorted, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, nullptr, nullptr, 0,
-                                      inv_norm, queries, q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows, out_dist, out_idx, out_keys,
-                                      out_ncand, status, workspace, workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end, stream, phases);
-}
-
-extern "C" int nlsh_scan_topk(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid,
-                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
-                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys,
-                              const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows, float *out_dist,
-                              int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace,
-                              size_t workspace_bytes, int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end,
-                              nlsh_stream_t stream) {
-    return nlsh_scan_topk_phase(corpus_sorted, row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, inv_norm, queries,
-                                q_stride, Q, qkeys, nkeys, P, k, metric, algo, seg_rows, out_dist, out_idx, out_keys, out_ncand,
-                                status, workspace, workspace_bytes, max_tasks, ev_scan_begin, ev_scan_end, stream,
-                                NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE);
+    NLSH_TOPK_CALL(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
+    c.phases = phases; c.storage = storage; c.row_filter = row_filter;
+    // without a filter this IS the typed call (include/nlsh_hip.h), and says so in its refusals
+    return topk_call(row_filter ? "scan_topk_filtered" : "scan_topk_typed", c);
 }
 
 extern "C" int nlsh_merge_topk(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,

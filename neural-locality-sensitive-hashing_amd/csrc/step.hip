@@ -18,6 +18,8 @@
 
 #include "step_nodes.h"
 
+#include "scan_bucket_args.h"   // BucketScanPrep: the lookup's PlanArgs of a scan call
+
 using namespace nlsh;
 
 struct nlsh_step {
@@ -34,13 +36,31 @@ struct nlsh_step {
     bool graph_failed;   // the capture or the instantiation did not work on this runtime: the slot launches its batches eagerly on its stream
 };
 
-// One batch's scan call as the bucket-major descriptor (validated), or -- query-major schedule -- nothing (fused = false).
-static int scan_call(const nlsh_step_desc_t &d, const float *queries, int64_t q_stride, void *ev0, void *ev1, nlsh_stream_t stream, int phases,
-                     int plan_blocks, BucketScanCall *call_out) {
-    return scan_topk_cells_phase_checked(d.corpus_sorted, d.row_stride, d.d, d.gid, d.uniq_keys, d.offsets, d.bucket_order, d.n_buckets, d.cell_of,
-                                         d.cell_offsets, d.n_cells, d.inv_norm, queries, q_stride, d.Q, d.qkeys, d.nkeys, d.n_probes, d.k, d.metric,
-                                         d.algo, d.seg_rows, d.out_dist, d.out_idx, d.out_keys, d.out_ncand, d.status, d.workspace, d.workspace_bytes,
-                                         d.max_tasks, ev0, ev1, stream, phases, plan_blocks, call_out);
+// One batch's scan call: the descriptor's members by name, the batch pointer and the stream.  The caller names what else its call has
+// (events, the workgroups of a fused lookup, a host block) on the descriptor it gets back.
+static BucketScanCall step_scan_call(const nlsh_step_desc_t &d, const float *queries, int64_t q_stride, hipStream_t stream, int phases) {
+    BucketScanCall c = {};
+    c.corpus = d.corpus_sorted; c.row_stride = d.row_stride; c.d = d.d; c.gid = d.gid; c.uniq = d.uniq_keys; c.offsets = d.offsets;
+    c.bucket_order = d.bucket_order; c.nb = d.n_buckets; c.cell_of = d.cell_of; c.cell_offsets = d.cell_offsets; c.n_cells = d.n_cells;
+    c.inv_norm = d.inv_norm; c.queries = queries; c.q_stride = q_stride; c.Q = d.Q; c.qkeys = d.qkeys; c.nkeys = d.nkeys;
+    c.P = d.n_probes; c.k = d.k; c.metric = d.metric; c.algo = d.algo; c.seg = d.seg_rows;
+    c.out_dist = d.out_dist; c.out_idx = d.out_idx; c.out_keys = d.out_keys; c.out_ncand = d.out_ncand; c.status = d.status;
+    c.workspace = d.workspace; c.workspace_bytes = d.workspace_bytes; c.max_tasks = d.max_tasks;
+    c.stream = stream; c.phases = phases;
+    return c;
+}
+constexpr int SCAN_AND_MERGE = NLSH_PHASE_SCAN | NLSH_PHASE_MERGE;   // what follows a batch's plan phase (NLSH_PHASE_PLAN, or _REST behind a fused lookup)
+// the one check of a scan call, with the internal phase bit allowed
+static int step_scan_check(const BucketScanCall &c) { return scan_call_check("scan_topk", c, SCAN_NEEDS_TOPK_OUT | SCAN_ALLOWS_PLAN_REST); }
+// check, and the lookup's arguments for this call's workspace (bucket-major schedules)
+static int step_scan_prepare(const BucketScanCall &c, BucketScanPrep *p) {
+    const int rc = step_scan_check(c);
+    return rc != NLSH_OK ? rc : bucket_scan_args(c, p);
+}
+static int step_scan_run(const BucketScanCall &c) {
+    const int rc = step_scan_check(c);
+    if (rc != NLSH_OK || c.Q == 0) return rc;
+    return scan_call_run(c);
 }
 
 static bool fuses_lookup(const nlsh_step_desc_t &d) { return d.algo != NLSH_SCAN_QUERY_MAJOR && d.n_probes <= 64 && d.n_buckets > 0; }
@@ -51,16 +71,13 @@ static int launch_encode(EncPlan &enc, const nlsh_step_desc_t &d, const float *q
     *plan_phase = NLSH_PHASE_PLAN;
     *plan_blocks = 0;
     if (!fuses_lookup(d)) return encode_plan_launch(enc, queries, q_stride, seed, s);
-    BucketScanCall c;
-    int rc = scan_call(d, queries, q_stride, nullptr, nullptr, (nlsh_stream_t)s, NLSH_PHASE_PLAN_REST, 0, &c);
-    if (rc != NLSH_OK) return rc;
-    PlanArgs pa;
-    rc = bucket_scan_plan_args(c, &pa);
-    if (rc == NLSH_OK) rc = encode_plan_fuse_lookup(enc, pa);   // idempotent: the first call of a slot sizes the coarse table's LDS
+    BucketScanPrep p;
+    int rc = step_scan_prepare(step_scan_call(d, queries, q_stride, s, NLSH_PHASE_PLAN_REST), &p);
+    if (rc == NLSH_OK) rc = encode_plan_fuse_lookup(enc, p.pa);   // idempotent: the first call of a slot sizes the coarse table's LDS
     if (rc != NLSH_OK) return rc;
     *plan_phase = NLSH_PHASE_PLAN_REST;
     *plan_blocks = (int)enc.grid;
-    return encode_plan_launch(enc, queries, q_stride, seed, s, &pa);
+    return encode_plan_launch(enc, queries, q_stride, seed, s, &p.pa);
 }
 
 static int make_event(hipEvent_t *e) {
@@ -98,13 +115,15 @@ static int step_create(const nlsh_step_desc_t *desc, size_t desc_bytes, hipStrea
     // the scan call's own argument checks (workspace alignment and size, strides, limits) run HERE, on a stand-in batch pointer, so
     // that a bad descriptor fails before anything is enqueued (they used to fail inside the first enqueue, behind its encode)
     if (rc == NLSH_OK) {
-        BucketScanCall c;
-        rc = scan_call(s->d, desc->corpus_sorted ? desc->corpus_sorted : (const float *)desc->workspace, desc->row_stride >= desc->d ? desc->row_stride : desc->d,
-                       nullptr, nullptr, (nlsh_stream_t)last, NLSH_PHASE_SCAN, 0, desc->algo != NLSH_SCAN_QUERY_MAJOR ? &c : nullptr);
-        if (rc == NLSH_OK && desc->algo != NLSH_SCAN_QUERY_MAJOR) {
-            PlanArgs pa;
-            rc = bucket_scan_plan_args(c, &pa);
-            if (rc == NLSH_OK && fuses_lookup(s->d)) rc = encode_plan_fuse_lookup(s->enc, pa);
+        const BucketScanCall c = step_scan_call(s->d, desc->corpus_sorted ? desc->corpus_sorted : (const float *)desc->workspace,
+                                                desc->row_stride >= desc->d ? desc->row_stride : desc->d, last, NLSH_PHASE_SCAN);
+        if (desc->algo == NLSH_SCAN_QUERY_MAJOR) {
+            rc = step_scan_check(c);
+            if (rc == NLSH_OK) rc = query_major_workspace(c);
+        } else {
+            BucketScanPrep p;
+            rc = step_scan_prepare(c, &p);
+            if (rc == NLSH_OK && fuses_lookup(s->d)) rc = encode_plan_fuse_lookup(s->enc, p.pa);
         }
     }
     if (rc == NLSH_OK && lane != nullptr && !(fuses_lookup(s->d) && desc->max_tasks > 0)) {
@@ -155,9 +174,6 @@ extern "C" int nlsh_step_set_weights(nlsh_step_t *s, const float *packed) {
     return NLSH_OK;
 }
 
-static int scan_phase(const nlsh_step *s, const float *queries, int64_t q_stride, void *ev0, void *ev1, nlsh_stream_t stream, int phases, int plan_blocks) {
-    return scan_call(s->d, queries, q_stride, ev0, ev1, stream, phases, plan_blocks, nullptr);
-}
 
 // A graph slot's batch: the five launches replayed from the slot's captured graph on the slot's own stream.  Batches of different slots
 // overlap because their streams do (the slot's previous batch precedes this one on the same stream: no event between them).  Per batch the
@@ -168,7 +184,9 @@ static int graph_capture(nlsh_step *s, const float *queries, int64_t q_stride, u
     NLSH_CHECK_HIP(hipStreamBeginCapture(s->lane, hipStreamCaptureModeThreadLocal));
     int plan_phase, plan_blocks;
     int rc = launch_encode(s->enc, s->d, queries, q_stride, seed, s->lane, &plan_phase, &plan_blocks);
-    if (rc == NLSH_OK) rc = scan_call(s->d, queries, q_stride, nullptr, nullptr, (nlsh_stream_t)s->lane, plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, plan_blocks, nullptr);
+    BucketScanCall rest = step_scan_call(s->d, queries, q_stride, s->lane, plan_phase | SCAN_AND_MERGE);
+    rest.plan_blocks = plan_blocks;
+    if (rc == NLSH_OK) rc = step_scan_run(rest);
     hipGraph_t g = nullptr;
     const hipError_t ce = hipStreamEndCapture(s->lane, &g);
     if (rc != NLSH_OK) {
@@ -180,8 +198,8 @@ static int graph_capture(nlsh_step *s, const float *queries, int64_t q_stride, u
     // the two nodes whose arguments change per batch, found by their kernels
     EncNode en;
     ScanNode sn;
-    BucketScanCall c;
-    rc = scan_call(s->d, queries, q_stride, nullptr, nullptr, (nlsh_stream_t)s->lane, NLSH_PHASE_SCAN, 0, &c);
+    const BucketScanCall c = step_scan_call(s->d, queries, q_stride, s->lane, NLSH_PHASE_SCAN);
+    rc = step_scan_check(c);
     if (rc == NLSH_OK) rc = bucket_scan_node(c, &sn);
     if (rc == NLSH_OK) rc = encode_plan_node(s->enc, queries, q_stride, seed, nullptr, &en);
     if (rc != NLSH_OK) return rc;
@@ -231,19 +249,19 @@ static int graph_enqueue(nlsh_step *s, const float *queries, int64_t q_stride, u
     if (ev0 || ev1 || !s->exec) {
         int plan_phase, plan_blocks;
         rc = launch_encode(s->enc, s->d, queries, q_stride, seed, lane, &plan_phase, &plan_blocks);
-        if (rc == NLSH_OK) rc = scan_call(s->d, queries, q_stride, ev0, ev1, (nlsh_stream_t)lane, plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, plan_blocks, nullptr);
+        BucketScanCall rest = step_scan_call(s->d, queries, q_stride, lane, plan_phase | SCAN_AND_MERGE);
+        rest.plan_blocks = plan_blocks; rest.ev_begin = ev0; rest.ev_end = ev1;
+        if (rc == NLSH_OK) rc = step_scan_run(rest);
         if (rc != NLSH_OK) return rc;
     } else {
         // this batch's arguments of the two nodes that carry them
-        BucketScanCall c;
-        rc = scan_call(s->d, queries, q_stride, nullptr, nullptr, (nlsh_stream_t)lane, NLSH_PHASE_SCAN, 0, &c);
-        if (rc != NLSH_OK) return rc;
-        PlanArgs pa;
+        const BucketScanCall c = step_scan_call(s->d, queries, q_stride, lane, NLSH_PHASE_SCAN);
+        BucketScanPrep p;
         EncNode en;
         ScanNode sn;
-        rc = bucket_scan_plan_args(c, &pa);
-        if (rc == NLSH_OK) rc = encode_plan_fuse_lookup(s->enc, pa);
-        if (rc == NLSH_OK) rc = encode_plan_node(s->enc, queries, q_stride, seed, &pa, &en);
+        rc = step_scan_prepare(c, &p);
+        if (rc == NLSH_OK) rc = encode_plan_fuse_lookup(s->enc, p.pa);
+        if (rc == NLSH_OK) rc = encode_plan_node(s->enc, queries, q_stride, seed, &p.pa, &en);
         if (rc == NLSH_OK) rc = bucket_scan_node(c, &sn);
         if (rc != NLSH_OK) return rc;
         NLSH_CHECK_HIP(hipGraphExecKernelNodeSetParams(s->exec, s->enc_node, &en.p));
@@ -285,15 +303,19 @@ extern "C" int nlsh_query_step_enqueue(nlsh_step_t *s, const float *queries, int
         NLSH_CHECK_HIP(hipEventRecord(s->encoded, front));
         NLSH_CHECK_HIP(hipStreamWaitEvent(hp, s->encoded, 0));
     }
-    rc = scan_phase(s, queries, q_stride, nullptr, nullptr, hp, plan_phase, plan_blocks);
+    BucketScanCall c = step_scan_call(s->d, queries, q_stride, hp, plan_phase);
+    c.plan_blocks = plan_blocks;
+    rc = step_scan_run(c);
     if (rc != NLSH_OK) return rc;
     NLSH_CHECK_HIP(hipEventRecord(s->planned, hp));
     NLSH_CHECK_HIP(hipStreamWaitEvent(mid, s->planned, 0));
-    rc = scan_phase(s, queries, q_stride, ev_scan_begin, ev_scan_end, mid, NLSH_PHASE_SCAN, 0);
+    c = step_scan_call(s->d, queries, q_stride, mid, NLSH_PHASE_SCAN);
+    c.ev_begin = ev_scan_begin; c.ev_end = ev_scan_end;
+    rc = step_scan_run(c);
     if (rc != NLSH_OK) return rc;
     NLSH_CHECK_HIP(hipEventRecord(s->scanned, mid));
     NLSH_CHECK_HIP(hipStreamWaitEvent(tail, s->scanned, 0));
-    rc = scan_phase(s, queries, q_stride, nullptr, nullptr, tail, NLSH_PHASE_MERGE, 0);
+    rc = step_scan_run(step_scan_call(s->d, queries, q_stride, tail, NLSH_PHASE_MERGE));
     if (rc != NLSH_OK) return rc;
     if (s->d.hold_done) s->done_pending = true;                       // the caller queues more work on the tail stream (the shard exchange) first
     else NLSH_CHECK_HIP(hipEventRecord(s->done, tail));
@@ -346,7 +368,9 @@ extern "C" int nlsh_query_batch(const nlsh_step_desc_t *desc, size_t desc_bytes,
         if (rc == NLSH_OK) rc = launch_encode(enc, *desc, queries, q_stride, seed, s, &plan_phase, &plan_blocks);
         if (rc != NLSH_OK) return rc;
     }
-    return scan_call(*desc, queries, q_stride, ev_scan_begin, ev_scan_end, stream, plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, plan_blocks, nullptr);
+    BucketScanCall rest = step_scan_call(*desc, queries, q_stride, s, plan_phase | SCAN_AND_MERGE);
+    rest.plan_blocks = plan_blocks; rest.ev_begin = ev_scan_begin; rest.ev_end = ev_scan_end;
+    return step_scan_run(rest);
 }
 
 // The merge's host-writing form stores through the DEVICE's address of the result block: it must be host memory the runtime has mapped
@@ -391,14 +415,11 @@ extern "C" int nlsh_query_batch_host(const nlsh_step_desc_t *desc, size_t desc_b
     int32_t *mapped = nullptr;
     if (const int mrc = host_block_mapped("query_batch_host", host_out, need, &mapped)) return mrc;
     hipStream_t s = (hipStream_t)stream;
-    BucketScanCall c;      // the scan call's own checks, on the host, before the encode is launched
-    int rc = scan_call(*desc, queries, q_stride, nullptr, nullptr, stream, NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, 0, &c);
+    // the scan call's own checks and its workspace size, on the host, before the encode is launched
+    BucketScanCall c = step_scan_call(*desc, queries, q_stride, s, NLSH_PHASE_PLAN | SCAN_AND_MERGE);
+    BucketScanPrep p;
+    int rc = step_scan_prepare(c, &p);
     if (rc != NLSH_OK) return rc;
-    {
-        PlanArgs pa;
-        rc = bucket_scan_plan_args(c, &pa);     // workspace size
-        if (rc != NLSH_OK) return rc;
-    }
     int plan_phase = NLSH_PHASE_PLAN, plan_blocks = 0;
     if (!lookup_done) {
         EncPlan enc;
@@ -407,7 +428,7 @@ extern "C" int nlsh_query_batch_host(const nlsh_step_desc_t *desc, size_t desc_b
         if (rc == NLSH_OK) rc = launch_encode(enc, *desc, queries, q_stride, seed, s, &plan_phase, &plan_blocks);
         if (rc != NLSH_OK) return rc;
     }
-    c.phases = plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE;
+    c.phases = plan_phase | SCAN_AND_MERGE;
     c.plan_blocks = plan_blocks;
     c.host_out = mapped;
     return bucket_scan_run(c);
@@ -474,11 +495,11 @@ extern "C" int nlsh_query_batch_ranked(const nlsh_step_desc_t *desc, size_t desc
     if (host_out)
         if (const int mrc = host_block_mapped("query_batch_ranked", host_out, need, &mapped)) return mrc;
     hipStream_t s = (hipStream_t)stream;
-    BucketScanCall c;      // the scan call's own checks, on the host, before anything is launched
-    int rc = scan_call(*desc, queries, q_stride, ev_scan_begin, ev_scan_end, stream, NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE, 0, &c);
-    if (rc != NLSH_OK) return rc;
-    PlanArgs pa;
-    rc = bucket_scan_plan_args(c, &pa);     // workspace size
+    // the scan call's own checks and its workspace size, on the host, before anything is launched
+    BucketScanCall c = step_scan_call(*desc, queries, q_stride, s, NLSH_PHASE_PLAN | SCAN_AND_MERGE);
+    c.ev_begin = ev_scan_begin; c.ev_end = ev_scan_end;
+    BucketScanPrep p;
+    int rc = step_scan_prepare(c, &p);
     if (rc != NLSH_OK) return rc;
     int plan_phase = NLSH_PHASE_PLAN, plan_blocks = 0;
     if (!lookup_done) {
@@ -490,11 +511,11 @@ extern "C" int nlsh_query_batch_ranked(const nlsh_step_desc_t *desc, size_t desc
                               (int32_t *)(base + w.keys), (int32_t *)(base + w.nkeys));
         if (rc == NLSH_OK) rc = encode_plan_launch(enc, queries, q_stride, 0, s);
         if (rc == NLSH_OK)
-            rc = probe_ranked_plan_launch(z, H, code, H, desc->key_mode, desc->n_multi_rows, budget, pa, desc->qkeys, desc->nkeys, s, &plan_blocks);
+            rc = probe_ranked_plan_launch(z, H, code, H, desc->key_mode, desc->n_multi_rows, budget, p.pa, desc->qkeys, desc->nkeys, s, &plan_blocks);
         if (rc != NLSH_OK) return rc;
         plan_phase = NLSH_PHASE_PLAN_REST;
     }
-    c.phases = plan_phase | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE;
+    c.phases = plan_phase | SCAN_AND_MERGE;
     c.plan_blocks = plan_blocks;
     c.host_out = mapped;
     return bucket_scan_run(c);

@@ -961,7 +961,7 @@ class Indexer:
 
     def _scan_fields(self, Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window=None):
         """The scan's share of a launch -- everything that does not change between batches of one shape -- as plain ints under the
-        field names of `_capi.StepDesc`: `_scan_launch` passes them to `nlsh_scan_topk_cells_phase`, `_step_desc` fills a descriptor
+        field names of `_capi.StepDesc`: `_scan_launch` passes them to `nlsh_scan_topk_cells_phase_filtered`, `_step_desc` fills a descriptor
         from them.  Callers that launch many batches (the kept range plans, nlsh_amd/pipeline.py) build them once per buffer set; a
         call is then one ctypes transition."""
         a = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (the tensors that may be absent)
@@ -993,23 +993,17 @@ class Indexer:
 
     def _scan_launch(self, q, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, phases, events=None,
                      window=None, stream=None, filter=None):
-        """One `nlsh_scan_topk_cells_phase` call on the current stream (`stream`: its handle, when the caller has already looked it up)
-        with caller-owned buffers (any subset of the phases).  `filter` (a checked RowFilter): the filtered form of the call."""
+        """One `nlsh_scan_topk_cells_phase_filtered` call on the current stream (`stream`: its handle, when the caller has already looked it
+        up) with caller-owned buffers (any subset of the phases).  The header defines the call with float32 storage and no filter as the
+        plain `nlsh_scan_topk_cells_phase`, so every index goes through it: the storage code follows the corpus pointer, the words of
+        `filter` (a checked RowFilter) or NULL end the list."""
         Q, d = q.shape
         f = self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window)
         before = _SCAN_ARGS_BEFORE_QUERIES(f)
-        tail = ()
-        if filter is not None:      # the typed call's arguments for every storage, the filter's words behind them
-            call, before = _capi.lib().nlsh_scan_topk_cells_phase_filtered, before[:1] + (_STORAGES[self.storage][1],) + before[1:]
-            tail = (filter.words.data_ptr(),)
-        elif self.compressed:       # the typed form of the same call: the storage code follows the corpus pointer
-            call, before = _capi.lib().nlsh_scan_topk_cells_phase_typed, before[:1] + (_STORAGES[self.storage][1],) + before[1:]
-        else:
-            call = _capi.lib().nlsh_scan_topk_cells_phase
-        _capi.check(call(
-            *before, q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
+        _capi.check(_capi.lib().nlsh_scan_topk_cells_phase_filtered(
+            before[0], _STORAGES[self.storage][1], *before[1:], q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
             events[0].cuda_event if events else None, events[1].cuda_event if events else None,
-            _stream(q.device) if stream is None else stream, phases, *tail))
+            _stream(q.device) if stream is None else stream, phases, None if filter is None else filter.words.data_ptr()))
 
     def _scan_sliced(self, q, keys, nkeys, k, want_keys, check, filter=None):
         """hash_times > 64 (eval.py:148 sweeps n_samples up to 100): the key table is scanned in column slices of
