@@ -66,6 +66,51 @@ if os.environ.get("QCHUNKS"):
         loop = (now() - loop0) / 60
         print(json.dumps({"query_chunks": ch, "call_median_ms": round(1e3 * float(np.median(w)), 4), "call_mean_ms": round(1e3 * float(np.mean(w)), 4),
                           "loop_ms_per_call_incl_free_of_previous": round(1e3 * loop, 4)}))
+    # the same calls with stamps inside them: where the host is while the ranges run.  "shells" = the containers built between the last
+    # launch and the first wait (csrc/fastlists.c rows_alloc), "wait" = what is left of the idle time (event / stream synchronise),
+    # "fill" = the ids and counts stored per range (rows_fill; one-shot: rows_to_lists), "before_wait" = hashing call, launches and the
+    # release of nothing (the result is kept here), "rest" = short-query rule, key sets, Python between the stages.  Both constructions
+    # in one process: "one_shot" is the path with the two-phase helper taken away (the parent commit's).
+    from nlsh_amd import indexer as ixmod
+    helper = ixmod._rows_alloc, ixmod._rows_fill, ixmod._rows_to_lists
+    ev_sync, st_sync = torch.cuda.Event.synchronize, torch.cuda.Stream.synchronize
+    for ch in [int(v) for v in os.environ["QCHUNKS"].split(",")]:
+        for mode in ("one_shot", "two_phase"):
+            if mode == "two_phase" and helper[0] is None:
+                continue
+            ix.query_chunks = ch
+            acc, first_wait = {}, []
+
+            def stamped(fn, key):
+                def inner(*a, **kw):
+                    t = now()
+                    if key == "wait" and not first_wait:
+                        first_wait.append(t)
+                    try:
+                        return fn(*a, **kw)
+                    finally:
+                        acc[key] = acc.get(key, 0.0) + now() - t
+                return inner
+            ixmod._rows_alloc, ixmod._rows_fill = (stamped(helper[0], "shells"), stamped(helper[1], "fill")) if mode == "two_phase" else (None, None)
+            ixmod._rows_to_lists = stamped(helper[2], "fill") if helper[2] is not None else None
+            torch.cuda.Event.synchronize, torch.cuda.Stream.synchronize = stamped(ev_sync, "wait"), stamped(st_sync, "wait")
+            S = {k_: [] for k_ in ("before_wait", "shells", "wait", "fill", "rest", "total")}
+            try:
+                for it in range(45):
+                    acc.clear(); del first_wait[:]
+                    st_sync(torch.cuda.current_stream())
+                    t0 = now(); keep = ix.query(q, 10, 10); t1 = now()
+                    if it < 5:
+                        continue
+                    shells = acc.get("shells", 0.0)
+                    S["before_wait"].append(first_wait[0] - t0 - shells); S["shells"].append(shells); S["wait"].append(acc.get("wait", 0.0))
+                    S["fill"].append(acc.get("fill", 0.0)); S["total"].append(t1 - t0)
+                    S["rest"].append(t1 - t0 - (first_wait[0] - t0) - acc.get("wait", 0.0) - acc.get("fill", 0.0))
+            finally:
+                ixmod._rows_alloc, ixmod._rows_fill, ixmod._rows_to_lists = helper
+                torch.cuda.Event.synchronize, torch.cuda.Stream.synchronize = ev_sync, st_sync
+            print(json.dumps({"query_chunks": ch, "construction": mode} | {k_: round(1e3 * float(np.median(v_)), 4) for k_, v_ in S.items()}))
+    ix.query_chunks = None
 if os.environ.get("QINLINE"):
     from nlsh_amd.hashings import host_key_set
     S = {k: [] for k in ("as_queries", "hash_device", "host_results", "f7_keysets", "plain_lists", "f7_rows", "dealloc_prev", "total")}
