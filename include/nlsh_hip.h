@@ -510,6 +510,61 @@ int nlsh_range_fill(const void *corpus_sorted, int storage, int64_t row_stride, 
                     void *sort_workspace, size_t sort_workspace_bytes, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * sq8 corpus storage: one byte per element with a per-dimension offset and step, for real-valued rows.  No reference counterpart.
+ *
+ * A quantiser is lo[d], step[d], float32, finite, step > 0.  The rule, in separate IEEE float32 operations (no fused multiply-add):
+ *   decode  deq(c, j) = float(c) * step[j] + lo[j]                      -- torch: codes.float() * step + lo
+ *   encode  t = (x - lo[j]) / step[j]; code = clamp(rint(t), 0, 255)    -- torch: ((x - lo) / step).round().clamp(0, 255); ties to even.
+ *           A finite value outside the range SATURATES and the row is counted; a row holding a NaN or an infinity is refused
+ *           (first_bad, as in the typed calls: the smallest such row, -1 for none; the outputs are then to be dropped).
+ *   train   lo = min + 0.0f and hi = max + 0.0f over the rows (a zero of either sign becomes +0), step = (hi - lo) / 255.0f, or 1.0f
+ *           where hi == lo.  A range that overflows float32 gives step = +inf: the caller refuses such a quantiser.
+ * The codes live in the uint8 layout: pitch a multiple of 16 elements from a 16-byte aligned base, columns >= d stored as code 0.  Every
+ * lo / step array a call READS has row_stride (the pitch) entries, 16-byte aligned, padded behind d with lo = 0, step = 1 -- a padded
+ * column decodes to +0 exactly as the float32 index holds it.  An sq8 index is, by definition, the float32 index over deq(codes): every
+ * array and every result bit of the calls below equals what the float32 calls give on those rows.  lo = 0, step = 1 on integers in
+ * [0, 255] is NLSH_STORE_U8.  The typed calls keep refusing every storage code past NLSH_STORE_U8: these are entry points of their own.
+ *
+ * nlsh_sq8_train: rows [dev] of `storage` (NLSH_STORE_F32 | NLSH_STORE_F16) elements, [n, d] with row stride row_stride elements (any
+ *   alignment: 16- / 8-byte loads where the rows allow, element loads otherwise); one read of the rows, per-workgroup partial minima and
+ *   maxima in the workspace (nlsh_sq8_train_workspace: host arithmetic, 0 = invalid sizes) and a small final pass -- no float atomics,
+ *   the result is bit-defined.  lo, step [dev] float [quant_stride], quant_stride >= d: entries >= d are written as the padding; n = 0
+ *   gives lo = 0, step = 1.  first_bad [dev] int32 [1].
+ * nlsh_gather_rows_sq8: nlsh_gather_rows_typed with the encoding destination.  A NLSH_STORE_F32 / F16 source is encoded, a NLSH_STORE_U8
+ *   source is codes and is copied.  inv_norm (nullable) is computed over the DECODED values in nlsh_gather_rows' operation order.
+ *   clamped_rows [dev] int32 [1] (nullable) receives the number of rows with at least one saturated element.
+ * nlsh_csr_update_sq8: nlsh_csr_update_typed on an sq8 index: kept rows move as bytes, new rows of new_storage are encoded on the way in
+ *   (NLSH_STORE_U8: codes, copied), new rows' inv_norm over decoded values; first_bad (nullable for NLSH_STORE_U8 rows) and clamped_rows
+ *   (nullable) count among the new rows.  row_stride == stride_out when both sides have rows.  Workspace: nlsh_csr_update_workspace.
+ * nlsh_scan_topk_cells_phase_sq8: nlsh_scan_topk_cells_phase_filtered over an sq8 index, lo and step behind corpus_sorted; row_filter
+ *   NULL = no filter.  Tiled schedule only (NLSH_E_UNSUPPORTED otherwise), every metric, k <= NLSH_MAX_K_TILED.  lo and step are checked
+ *   like every other pointer (null, 16-byte alignment), the pitch and d by the uint8 rules.  The codes are decoded as they are staged.
+ *   The radius, step, graph-slot and one-call batch entry points take no sq8 index. */
+size_t nlsh_sq8_train_workspace(int64_t n, int d);
+int nlsh_sq8_train(const void *rows, int storage, int64_t row_stride, int d, int64_t n, float *lo, float *step, int64_t quant_stride,
+                   int32_t *first_bad, void *workspace, size_t workspace_bytes, nlsh_stream_t stream);
+int nlsh_gather_rows_sq8(const void *corpus, int src_storage, int64_t src_stride, int d, const int32_t *perm, int64_t n,
+                         uint8_t *sorted, int64_t dst_stride, const float *lo, const float *step, float *inv_norm, int32_t *gid,
+                         int32_t id_base, int32_t *first_bad, int32_t *clamped_rows, nlsh_stream_t stream);
+int nlsh_csr_update_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d, const int32_t *gid,
+                        const float *inv_norm, const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                        const uint8_t *keep, int64_t n_kept,
+                        const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new,
+                        int64_t m_new,
+                        uint8_t *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                        int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad, int32_t *clamped_rows,
+                        void *workspace, size_t workspace_bytes, nlsh_stream_t stream);
+int nlsh_scan_topk_cells_phase_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d,
+                                   const int32_t *gid, const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order,
+                                   int32_t n_buckets, const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                                   const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
+                                   const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows,
+                                   float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand,
+                                   int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
+                                   void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                                   const uint32_t *row_filter);
+
+/* ---------------------------------------------------------------------------------------------
  * One pipelined query batch per call.  Replaces, for a caller that streams batches, the whole body of Indexer.query
  * (nlsh/indexer.py:56-96: hashing.hash on the batch :59 via Indexer.hash :40-54, then the per-query loop :62-95) by ONE
  * enqueue: nlsh_encode_hash + the PLAN, SCAN and MERGE phases of nlsh_scan_topk_cells_phase (five launches since r06: the bucket

@@ -635,6 +635,8 @@ static void update_layout(long long n_old, long long nb_old, long long m_new, Up
 
 }  // namespace nlsh
 
+#include "sq8_rows.h"   // storage="sq8": training, the encoding gather and the update passes, built from the row helpers above
+
 using namespace nlsh;
 
 extern "C" size_t nlsh_build_csr_workspace(int64_t n) {
@@ -797,10 +799,14 @@ static int csr_update_impl(const void *corpus_sorted, int storage, int64_t row_s
                            const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new, int64_t m_new,
                            void *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
                            int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad,
-                           void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+                           void *workspace, size_t workspace_bytes, nlsh_stream_t stream,
+                           bool sq8 = false, const float *lo = nullptr, const float *step = nullptr, int32_t *clamped_rows = nullptr) {
     // ---- host checks: nothing below them runs, and no pointer is read, unless all of them pass
     NLSH_REQUIRE(store_ok(storage) && store_ok(new_storage), NLSH_E_INVALID, "csr_update: storage=%d / new_storage=%d is none of NLSH_STORE_F32 / F16 / U8",
                  storage, new_storage);
+    // nlsh_csr_update_sq8: the uint8 layout (storage is NLSH_STORE_U8) with the quantiser the new rows are encoded and the norms decoded by
+    NLSH_REQUIRE(!sq8 || (lo && step), NLSH_E_INVALID, "csr_update: lo / step is null");
+    NLSH_REQUIRE(!sq8 || ((((uintptr_t)lo | (uintptr_t)step) & 15) == 0), NLSH_E_INVALID, "csr_update: lo and step must be 16-byte aligned");
     const int per16 = store_per16(storage);
     NLSH_REQUIRE(d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "csr_update: d=%d not in [1, NLSH_MAX_DIM = %d]", d, NLSH_MAX_DIM);
     NLSH_REQUIRE(n_old >= 0 && n_old < (1ll << 31), NLSH_E_INVALID, "csr_update: n_old=%lld not in [0, 2^31)", (long long)n_old);
@@ -842,6 +848,7 @@ static int csr_update_impl(const void *corpus_sorted, int storage, int64_t row_s
     // ---- device work
     hipStream_t s = (hipStream_t)stream;
     if (first_bad) NLSH_CHECK_HIP(hipMemsetAsync(first_bad, 0xFF, sizeof(int32_t), s));   // -1: every new row survived its conversion
+    if (clamped_rows) NLSH_CHECK_HIP(hipMemsetAsync(clamped_rows, 0, sizeof(int32_t), s));
     if (n_out == 0) {
         NLSH_CHECK_HIP(hipMemsetAsync(offsets_out, 0, sizeof(int32_t), s));
         NLSH_CHECK_HIP(hipMemsetAsync(n_buckets_out, 0, sizeof(int32_t), s));
@@ -915,6 +922,22 @@ static int csr_update_impl(const void *corpus_sorted, int storage, int64_t row_s
         long long uo = units_old, nold = n_old, sn = new_stride, mn = m_new, no = n_out, ut = units_out, sto = stride_out;
         int vecn = store_vec_ok(rows_new, new_storage, new_stride);      // new rows on chunk boundaries of their storage: one load per chunk
         void *argv[] = {&corpus_sorted, &uo, &nold, &rows_new, &sn, &mn, &d, &src_out, &no, &sorted_out, &ut, &lgu, &first_bad, &vecn};
+        if (sq8) {      // the same two passes with the quantiser: new rows encoded (uint8 ones are codes), norms over decoded values
+            const void *fs = new_storage == NLSH_STORE_F32 ? (const void *)update_rows_sq8_kernel<NLSH_STORE_F32>
+                           : new_storage == NLSH_STORE_F16 ? (const void *)update_rows_sq8_kernel<NLSH_STORE_F16>
+                                                           : (const void *)update_rows_sq8_kernel<NLSH_STORE_U8>;
+            void *args[] = {&corpus_sorted, &uo, &nold, &rows_new, &sn, &mn, &d, &src_out, &no, &sorted_out, &ut, &lgu, &lo, &step, &first_bad,
+                            &clamped_rows, &vecn};
+            NLSH_CHECK_HIP(hipLaunchKernel(fs, dim3((unsigned)ublocks), dim3(256), args, 0, s));
+            if (inv_norm_out) {
+                long long iblocks = ((n_out + 63) / 64 + 3) / 4;
+                if (iblocks > 256 * 8) iblocks = 256 * 8;
+                void *argi[] = {&sorted_out, &sto, &lo, &step, &inv_norm, &nold, &src_out, &no, &inv_norm_out};
+                NLSH_CHECK_HIP(hipLaunchKernel((const void *)update_inv_norm_sq8_kernel, dim3((unsigned)iblocks), dim3(256), argi, 0, s));
+            }
+            NLSH_CHECK_HIP(hipGetLastError());
+            return NLSH_OK;
+        }
         NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)ublocks), dim3(256), argv, 0, s));
         if (inv_norm_out) {
             const void *fi = storage == NLSH_STORE_F32 ? (const void *)update_inv_norm_typed_kernel<NLSH_STORE_F32>
@@ -993,4 +1016,95 @@ extern "C" int nlsh_gather_rows_typed(const void *corpus, int src_storage, int64
     NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, 0, s));
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
+}
+
+// ---- storage="sq8" (sq8_rows.h): entry points of their own beside the typed ones, which refuse every storage code past NLSH_STORE_U8
+static bool sq8_source_ok(int storage) { return storage == NLSH_STORE_F32 || storage == NLSH_STORE_F16; }
+
+extern "C" size_t nlsh_sq8_train_workspace(int64_t n, int d) {
+    if (n < 0 || d < 1 || d > NLSH_MAX_DIM) { set_error("sq8_train_workspace: n=%lld d=%d", (long long)n, d); return 0; }
+    int lgw, blocks;
+    sq8_train_shape(n, d, &lgw, &blocks);
+    return align_up((size_t)blocks * 2 * ((size_t)16 << lgw));
+}
+
+extern "C" int nlsh_sq8_train(const void *rows, int storage, int64_t row_stride, int d, int64_t n, float *lo, float *step, int64_t quant_stride,
+                              int32_t *first_bad, void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+    NLSH_REQUIRE(sq8_source_ok(storage), NLSH_E_INVALID, "sq8_train: storage=%d is neither NLSH_STORE_F32 nor NLSH_STORE_F16", storage);
+    NLSH_REQUIRE(n >= 0 && d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "sq8_train: n=%lld d=%d", (long long)n, d);
+    NLSH_REQUIRE(quant_stride >= d, NLSH_E_INVALID, "sq8_train: quant_stride=%lld < d=%d", (long long)quant_stride, d);
+    NLSH_REQUIRE(lo && step && first_bad, NLSH_E_INVALID, "sq8_train: lo / step / first_bad is null");
+    int lgw, blocks;
+    sq8_train_shape(n, d, &lgw, &blocks);
+    if (n) {
+        NLSH_REQUIRE(rows && workspace, NLSH_E_INVALID, "sq8_train: rows / workspace is null");
+        NLSH_REQUIRE(row_stride >= d, NLSH_E_INVALID, "sq8_train: row_stride=%lld < d=%d", (long long)row_stride, d);
+        NLSH_REQUIRE(((uintptr_t)rows & (storage == NLSH_STORE_F32 ? 3 : 1)) == 0, NLSH_E_INVALID, "sq8_train: rows is not aligned to its element size");
+        NLSH_REQUIRE(((uintptr_t)workspace & 15) == 0, NLSH_E_INVALID, "sq8_train: the workspace must be 16-byte aligned");
+        NLSH_REQUIRE(workspace_bytes >= nlsh_sq8_train_workspace(n, d), NLSH_E_WORKSPACE, "sq8_train: workspace %zu < %zu", workspace_bytes,
+                     nlsh_sq8_train_workspace(n, d));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    NLSH_CHECK_HIP(hipMemsetAsync(first_bad, 0xFF, sizeof(int32_t), s));   // -1: every row is finite
+    long long rs = row_stride, nn = n, qs = quant_stride;
+    if (n) {
+        int vec = store_vec_ok(rows, storage, row_stride);
+        const void *fn = storage == NLSH_STORE_F32 ? (const void *)sq8_train_partial_kernel<NLSH_STORE_F32> : (const void *)sq8_train_partial_kernel<NLSH_STORE_F16>;
+        void *argv[] = {&rows, &rs, &d, &nn, &lgw, &workspace, &first_bad, &vec};
+        NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, 0, s));
+    }
+    const float *part = (const float *)workspace;
+    hipLaunchKernelGGL(sq8_train_final_kernel, dim3((unsigned)((quant_stride + 15) / 16)), dim3(256), 0, s, part, blocks, lgw, d, nn, lo, step, qs);
+    NLSH_CHECK_HIP(hipGetLastError());
+    return NLSH_OK;
+}
+
+extern "C" int nlsh_gather_rows_sq8(const void *corpus, int src_storage, int64_t src_stride, int d, const int32_t *perm, int64_t n,
+                                    uint8_t *sorted, int64_t dst_stride, const float *lo, const float *step, float *inv_norm, int32_t *gid,
+                                    int32_t id_base, int32_t *first_bad, int32_t *clamped_rows, nlsh_stream_t stream) {
+    NLSH_REQUIRE(store_ok(src_storage), NLSH_E_INVALID, "gather_rows_sq8: src_storage=%d is none of NLSH_STORE_F32 / F16 / U8", src_storage);
+    NLSH_REQUIRE(n >= 0 && d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "gather_rows_sq8: n=%lld d=%d", (long long)n, d);
+    NLSH_REQUIRE(first_bad || src_storage == NLSH_STORE_U8, NLSH_E_INVALID, "gather_rows_sq8: first_bad is null but the rows are encoded (src_storage=%d)", src_storage);
+    if (n) {
+        NLSH_REQUIRE(corpus && perm && sorted, NLSH_E_INVALID, "gather_rows_sq8: corpus / perm / sorted is null");
+        NLSH_REQUIRE(lo && step, NLSH_E_INVALID, "gather_rows_sq8: lo / step is null");
+        NLSH_REQUIRE(dst_stride >= d && dst_stride % 16 == 0, NLSH_E_INVALID,
+                     "gather_rows_sq8: dst_stride=%lld must be >= d=%d and a multiple of 16 elements (a pitch of 16-byte units)", (long long)dst_stride, d);
+        NLSH_REQUIRE(((uintptr_t)sorted & 15) == 0, NLSH_E_INVALID, "gather_rows_sq8: sorted must be 16-byte aligned");
+        NLSH_REQUIRE((((uintptr_t)lo | (uintptr_t)step) & 15) == 0, NLSH_E_INVALID, "gather_rows_sq8: lo and step must be 16-byte aligned");
+        NLSH_REQUIRE(src_stride >= d, NLSH_E_INVALID, "gather_rows_sq8: src_stride=%lld < d=%d", (long long)src_stride, d);
+        NLSH_REQUIRE(((uintptr_t)corpus & (src_storage == NLSH_STORE_F32 ? 3 : src_storage == NLSH_STORE_F16 ? 1 : 0)) == 0, NLSH_E_INVALID,
+                     "gather_rows_sq8: corpus is not aligned to its element size");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (first_bad) NLSH_CHECK_HIP(hipMemsetAsync(first_bad, 0xFF, sizeof(int32_t), s));   // -1: every row is finite
+    if (clamped_rows) NLSH_CHECK_HIP(hipMemsetAsync(clamped_rows, 0, sizeof(int32_t), s));
+    if (n == 0) return NLSH_OK;
+    long long blocks = (n + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    const void *fn = src_storage == NLSH_STORE_F32 ? (const void *)gather_rows_sq8_kernel<NLSH_STORE_F32>
+                   : src_storage == NLSH_STORE_F16 ? (const void *)gather_rows_sq8_kernel<NLSH_STORE_F16>
+                                                   : (const void *)gather_rows_sq8_kernel<NLSH_STORE_U8>;
+    long long ss = src_stride, nn = n, ds = dst_stride;
+    int vec = store_vec_ok(corpus, src_storage, src_stride);
+    void *argv[] = {&corpus, &ss, &d, &perm, &nn, &sorted, &ds, &lo, &step, &inv_norm, &gid, &id_base, &first_bad, &clamped_rows, &vec};
+    NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, 0, s));
+    NLSH_CHECK_HIP(hipGetLastError());
+    return NLSH_OK;
+}
+
+extern "C" int nlsh_csr_update_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d, const int32_t *gid,
+                                   const float *inv_norm, const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                                   const uint8_t *keep, int64_t n_kept,
+                                   const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new,
+                                   int64_t m_new,
+                                   uint8_t *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                                   int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad, int32_t *clamped_rows,
+                                   void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+    // one quantiser serves both sides: its arrays cover the wider of the two pitches only if the caller made them so
+    NLSH_REQUIRE(n_old == 0 || m_new == 0 || n_kept + m_new == 0 || row_stride == stride_out, NLSH_E_INVALID,
+                 "csr_update_sq8: row_stride=%lld != stride_out=%lld (lo and step are padded to ONE pitch)", (long long)row_stride, (long long)stride_out);
+    return csr_update_impl(corpus_sorted, NLSH_STORE_U8, row_stride, d, gid, inv_norm, uniq_keys, offsets, n_old, n_buckets_old, keep, n_kept,
+                           rows_new, new_storage, new_stride, keys_new, ids_new, m_new, sorted_out, stride_out, gid_out, inv_norm_out, src_out,
+                           uniq_out, offsets_out, n_buckets_out, first_bad, workspace, workspace_bytes, stream, true, lo, step, clamped_rows);
 }

@@ -85,6 +85,17 @@ struct RangeArgs {
     int mode;                      // NLSH_RANGE_COUNT | NLSH_RANGE_FILL (wave-uniform)
 };
 
+// The corpus storage of the affine kernels (bscana_kernel, scan_bucket_affine.hip; nlsh_scan_topk_cells_phase_sq8): uint8 codes in the
+// uint8 layout, decoded per dimension as the tile is written (Stored<NLSH_STORE_SQ8>).  Internal: the C ABI's storage codes end at
+// NLSH_STORE_U8, an sq8 call is a uint8 call that carries a quantiser (BucketScanCall::affine).
+#define NLSH_STORE_SQ8 3
+// Second parameter of the affine kernels, as RangeArgs is the radius kernels': BArgs keeps its layout.
+struct QuantArgs {
+    const float4 *lo4;             // [row_stride / 4] the quantiser's offsets, padded to the pitch with 0
+    const float4 *step4;           // [row_stride / 4] its steps, padded with 1: a padded column (code 0) decodes to +0
+    const uint32_t *row_filter;    // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: every row allowed
+};
+
 // A call's prepared launch (scan_bucket.hip): the workspace held against the schedule's layout (NLSH_E_WORKSPACE), then what the scan kernels
 // take (bucket_scan_run; the radius calls for their own kernel), what the lookup takes (step.hip, probe_ranked.hip: the launch that does it),
 // the metric the schedule really computes and whether the tiled schedule needs its padded / pre-normalised query copy

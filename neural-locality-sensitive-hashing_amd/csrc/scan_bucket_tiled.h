@@ -2,7 +2,8 @@
 // instantiates the float32 kernels, scan_bucket_typed.hip the float16 / uint8 ones):
 // the hand-scheduled k-blocks, the task bodies built from them (l2_task*), one task start to finish (tiled_task_body) and the kernels
 // bscan3_kernel (k <= 64) and bscanw_kernel (k up to NLSH_MAX_K_TILED) over a float32 corpus, bscant_kernel over a float16 / uint8 one,
-// bscanf_kernel behind a row filter (scan_bucket_filtered.hip instantiates it), bscanr_kernel for radius queries (scan_bucket_range.hip).
+// bscanf_kernel behind a row filter (scan_bucket_filtered.hip instantiates it), bscanr_kernel for radius queries (scan_bucket_range.hip),
+// bscana_kernel over an sq8 corpus (scan_bucket_affine.hip).
 #pragma once
 
 // Diagnostic build only (make EXTRA=-DNLSH_SCAN_TRACE, tools/scan_trace.py): wave 0 of every bscan3 workgroup
@@ -303,6 +304,18 @@ template <> struct Stored<NLSH_STORE_U8> {
     }
     static __device__ __forceinline__ uint32_t zero() { return 0u; }
 };
+// The affine form (storage="sq8"; bscana_kernel): the word is uint8 storage's, and `widen` takes the chunk's four offsets and steps --
+// deq(c, j) = float(c) * step[j] + lo[j], a multiply and an add with a rounding each (the library is built with -ffp-contract=off: no
+// fused multiply-add), which is `codes.float() * step + lo` in torch.  The staging code requests lo4 / step4 of its chunk column beside
+// the row words (the padded arrays are <= 8 KB and stay in the cache); behind the tile the values are float32 like every other storage's.
+template <> struct Stored<NLSH_STORE_SQ8> {
+    typedef uint32_t word;
+    static __device__ __forceinline__ float4 widen(uint32_t w, const float4 lo, const float4 st) {
+        const float4 c = Stored<NLSH_STORE_U8>::widen(w);
+        return make_float4(c.x * st.x + lo.x, c.y * st.y + lo.y, c.z * st.z + lo.z, c.w * st.w + lo.w);
+    }
+    static __device__ __forceinline__ uint32_t zero() { return 0u; }
+};
 
 // All k-blocks of one L2 task for a wave that holds NQ (0..4) of its queries, NTL = tiles of the task (1..4): staging
 // (global -> registers -> LDS, next k-block's loads in flight during the current one) + the hand-scheduled k-blocks.
@@ -316,7 +329,8 @@ template <> struct Stored<NLSH_STORE_U8> {
 template <int NW, int NQ, int NTL, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false, int STORE = NLSH_STORE_F32>
 __device__ __forceinline__ void l2_task(float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
                                         const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4],
-                                        [[maybe_unused]] unsigned long long (&tr)[3]) {
+                                        [[maybe_unused]] unsigned long long (&tr)[3],
+                                        [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr) {
     constexpr int NTH = 64 * NW, KB = NLSH_TILED_KB;
     // A task costs ~15 us before it does any work (r01 trace: 16 us for 1 query x <= 64 rows, 55 us for 16 x 256): one
     // exposed global-load round trip + two barriers per k-block.  Short segments therefore take FATTER k-blocks --
@@ -327,6 +341,9 @@ __device__ __forceinline__ void l2_task(float4 *tile, const typename Stored<STOR
     const int nkb = (d4 + KBt - 1) / KBt;
     const int sc = tid & (KBt - 1), sr = tid / KBt;   // staging map: KBt threads cover 16*KBt contiguous bytes of a row
     typename Stored<STORE>::word stg[SPT];
+    // (NLSH_STORE_SQ8: every staged word of a thread lies in ONE chunk column per stage, so its offsets and steps are one pair of
+    // 16-byte loads per stage, in flight with the row words)
+    [[maybe_unused]] float4 lo_c, step_c;
     // Rows past the end of the segment and chunks past the end of a row are CLAMPED, not zero-filled: the clamped loads read valid
     // memory, rows >= nrows are masked at the epilogue (`valid`) and a k-block only evaluates its `nchunk` real chunks.  Guarded,
     // every staged word sat behind its own exec mask + branch + zero fill: ~22 VALU, 12 SALU and 4 branches per stage and wave.
@@ -339,6 +356,7 @@ __device__ __forceinline__ void l2_task(float4 *tile, const typename Stored<STOR
         const int gc = min(kb * KBt + sc, d4 - 1);
 #pragma unroll
         for (int i = 0; i < SPT; ++i) stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? rowp[i][gc] : Stored<STORE>::zero();
+        if constexpr (STORE == NLSH_STORE_SQ8) { lo_c = qlo[gc]; step_c = qstep[gc]; }
     };
     stage_load(0);
     float qsink = 0.0f;
@@ -349,7 +367,10 @@ __device__ __forceinline__ void l2_task(float4 *tile, const typename Stored<STOR
         NLSH_STAGE_SYNC();  // everyone has finished reading the previous k-block
         [[maybe_unused]] const unsigned long long tb = SCAN_NOW();
 #pragma unroll
-        for (int i = 0; i < SPT; ++i) tile[(sr + RPPt * i) * RSt + sc] = Stored<STORE>::widen(stg[i]);
+        for (int i = 0; i < SPT; ++i) {
+            if constexpr (STORE == NLSH_STORE_SQ8) tile[(sr + RPPt * i) * RSt + sc] = Stored<STORE>::widen(stg[i], lo_c, step_c);
+            else tile[(sr + RPPt * i) * RSt + sc] = Stored<STORE>::widen(stg[i]);
+        }
         NLSH_STAGE_SYNC();
         if (kb + 1 < nkb) stage_load(kb + 1);  // in flight while this k-block is computed
         // (r05: the queries' published bounds requested HERE in front of the last k-block, whose staging registers are free, instead of
@@ -387,7 +408,8 @@ __device__ __forceinline__ void l2_task(float4 *tile, const typename Stored<STOR
 constexpr int SINGLE_STAGE_SLOTS = 1024;   // float4 slots one pass of the 256 threads stages (4 each)
 template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS, int STORE = NLSH_STORE_F32>
 __device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
-                                               const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4]) {
+                                               const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4],
+                                               [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr) {
     constexpr int NTH = 64 * NW, SPT = SINGLE_STAGE_SLOTS / NTH;
     const int RS = d4 | 1;                   // odd LDS row stride (16-byte slots): conflict-free column reads
     const int total = nrows * d4;
@@ -396,6 +418,7 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stor
     // counters did not move -- 289.6 against 289.5 K FETCH_SIZE units per GloVe launch -- and the shift was removed; DESIGN.md appendix A.)
     typename Stored<STORE>::word stg[SPT];
     int dst[SPT];
+    [[maybe_unused]] int col[SPT];   // NLSH_STORE_SQ8: the slot's chunk column, whose offsets and steps are read where the tile is written
 #pragma unroll
     for (int i = 0; i < SPT; ++i) {
         const int idx = min(tid + NTH * i, total - 1);   // slots past the task's last chunk re-read it (valid address, value never written)
@@ -405,6 +428,7 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stor
         const int c = idx - r * d4;
         stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? corpus4[(long long)(row0 + r) * stride4 + c] : Stored<STORE>::zero();
         dst[i] = r * RS + c;
+        if constexpr (STORE == NLSH_STORE_SQ8) col[i] = c;
     }
     float qsink = 0.0f;
     asm volatile("" : "+s"(qsink));
@@ -412,7 +436,10 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stor
     // one task per workgroup: nobody has read the tile before, so the writes need no barrier in front of them
 #pragma unroll
     for (int i = 0; i < SPT; ++i)
-        if (tid + NTH * i < total) tile[dst[i]] = Stored<STORE>::widen(stg[i]);
+        if (tid + NTH * i < total) {
+            if constexpr (STORE == NLSH_STORE_SQ8) tile[dst[i]] = Stored<STORE>::widen(stg[i], qlo[col[i]], qstep[col[i]]);
+            else tile[dst[i]] = Stored<STORE>::widen(stg[i]);
+        }
     NLSH_STAGE_SYNC();
     if (NQ > 0) {
         warm_query_lines_done(qsink);
@@ -428,7 +455,18 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stor
 
 template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false, int STORE = NLSH_STORE_F32>
 __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
-                                           const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4], unsigned long long (&tr)[3]) {
+                                           const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4], unsigned long long (&tr)[3],
+                                           [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr) {
+    if constexpr (STORE == NLSH_STORE_SQ8) {   // the same switch, the quantiser handed on
+        switch (ntile) {
+            case 0: l2_task_single<NW, NQ, METRIC, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, qlo, qstep); break;
+            case 1: l2_task<NW, NQ, 1, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep); break;
+            case 2: l2_task<NW, NQ, 2, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep); break;
+            case 3: l2_task<NW, NQ, 3, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep); break;
+            default: l2_task<NW, NQ, 4, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep); break;
+        }
+        return;
+    }
     switch (ntile) {
         case 0: l2_task_single<NW, NQ, METRIC, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc); break;   // "0 tiles": the single-stage body
         case 1: l2_task<NW, NQ, 1, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr); break;
@@ -463,8 +501,13 @@ template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = N
 __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, long long t, const int4 desc, const int2 qr_all, int tid, int lane,
                                                 int wave, [[maybe_unused]] unsigned long long ts_entry,
                                                 [[maybe_unused]] const uint32_t *row_filter = nullptr,
-                                                [[maybe_unused]] const RangeArgs *range = nullptr) {
+                                                [[maybe_unused]] const RangeArgs *range = nullptr,
+                                                [[maybe_unused]] const QuantArgs *quant = nullptr) {
     static_assert(!(RANGE && (FILT || WIDEK)), "the range epilogue reads its filter from RangeArgs and selects nothing");
+    // AFFINE (STORE == NLSH_STORE_SQ8; nlsh_scan_topk_cells_phase_sq8, bscana_kernel): the staging code decodes with quant->lo4 / step4,
+    // and quant->row_filter (nullable) is the filter, a run-time operand as in the range kernels.  Off, none of it exists in the code.
+    constexpr bool AFFINE = STORE == NLSH_STORE_SQ8;
+    static_assert(!(AFFINE && (FILT || RANGE)), "the affine kernels read their filter from QuantArgs and have no range epilogue");
     static_assert(QW == 4 && TPS == 4 && NW == 4, "the hand-scheduled task bodies (l2_task_nt) are written for 4 waves x 4 queries x 4 row tiles");
 #ifdef NLSH_SCAN_TRACE_CLOCK
     const unsigned long long ts0 = SCAN_NOW();
@@ -521,18 +564,21 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
         myinv[tl] = (METRIC == NLSH_METRIC_COSINE && valid[tl]) ? a.inv_norm[prow] : 0.0f;
         if (FILT) myfw[tl] = row_filter[prow >> 5];
         else if (RANGE) myfw[tl] = range->row_filter ? range->row_filter[prow >> 5] : 0xFFFFFFFFu;
+        else if (AFFINE) myfw[tl] = quant->row_filter ? quant->row_filter[prow >> 5] : 0xFFFFFFFFu;
     }
+    [[maybe_unused]] const float4 *qlo = nullptr, *qstep = nullptr;
+    if constexpr (AFFINE) { qlo = quant->lo4; qstep = quant->step4; }
     [[maybe_unused]] unsigned long long trl[3] = {0, 0, 0};
     [[maybe_unused]] const unsigned long long ts_in = SCAN_NOW();
     // a task whose rows x chunks fit one stage takes the single-stage body (l2_task_single): selected as "0 tiles" of the same switch
     const int nt_sel = (nrows * d4 <= SINGLE_STAGE_SLOTS && nrows <= 64) ? 0 : ntile;   // wave-uniform (task shape)
     // the hand-scheduled form, specialised per (queries of this wave, tiles of the task); same barrier count on every path
     switch (nqw) {
-        case 0: l2_task_nt<NW, 0, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-        case 1: l2_task_nt<NW, 1, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-        case 2: l2_task_nt<NW, 2, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-        case 3: l2_task_nt<NW, 3, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
-        default: l2_task_nt<NW, 4, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl); break;
+        case 0: l2_task_nt<NW, 0, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
+        case 1: l2_task_nt<NW, 1, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
+        case 2: l2_task_nt<NW, 2, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
+        case 3: l2_task_nt<NW, 3, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
+        default: l2_task_nt<NW, 4, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
     }
     if (nqw == 0) return;
     if (NLSH_ABLATE == 5 || NLSH_ABLATE == 6 || NLSH_ABLATE == 12 || NLSH_ABLATE == 13) {   // diagnostic: no epilogue at all (the accumulators are kept alive)
@@ -583,7 +629,7 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
 #pragma unroll
             for (int tl = 0; tl < TPS; ++tl) {
                 bool mine = valid[tl] && (unsigned)(tl * 64 + lane) - r_lo < r_n;
-                if (FILT || RANGE) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
+                if (FILT || RANGE || AFFINE) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
                 uint64_t kk;
                 [[maybe_unused]] float dist_r;   // RANGE: the distance the key is built from, held against the radius
                 if (lean) {
@@ -813,6 +859,33 @@ __global__ __launch_bounds__(64 * NW, 1) void bscanr_kernel(BArgs a, RangeArgs r
     const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
     if (t >= ntasks) return;
     tiled_task_body<METRIC, QW, NW, TPS, false, STORE, false, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, nullptr, &r);
+}
+
+// The tiled scan over an sq8 corpus (AFFINE of tiled_task_body; nlsh_scan_topk_cells_phase_sq8): uint8 codes decoded per dimension as the
+// tile is written, k <= 64 (WIDEK false) and k in 65..NLSH_MAX_K_TILED (true).  One kernel per (metric, k class) serves both filter states
+// -- q.row_filter is a wave-uniform run-time operand, as in the range kernels.  QuantArgs is a SECOND kernel parameter: BArgs and every
+// kernel above keep their layout and their code (profiles/sq8_storage.txt).  Instantiated in scan_bucket_affine.hip, a translation unit
+// of its own.  The task pick is bscan3_kernel's, line for line (see the comments there), written out again for the reason given at
+// bscanw_kernel.
+template <int METRIC, int QW, int NW, int TPS, bool WIDEK>
+__global__ __launch_bounds__(64 * NW, 1) void bscana_kernel(BArgs a, QuantArgs q) {
+    constexpr int RS = NLSH_TILED_KB + 1;
+    __shared__ float4 tile[64 * TPS * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
+    long long ntasks = a.status[0];
+    if (ntasks > a.max_tasks) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
+        ntasks = a.max_tasks;
+    }
+    constexpr int XC = 16;
+    const long long j = blockIdx.x >> 3;
+    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
+    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
+    const int4 desc = a.task[tc];
+    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
+    if (t >= ntasks) return;
+    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, NLSH_STORE_SQ8>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, nullptr, nullptr, &q);
 }
 
 }  // namespace nlsh

@@ -437,6 +437,10 @@ struct BucketScanCall {
                                   // schedule's alone (0 = F32 for every entry without a storage argument)
     const uint32_t *row_filter;   // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: the tiled schedule's alone; the SCAN phase
                                   // then launches a filtered kernel, which takes the pointer as a second parameter (BArgs does not hold it)
+    bool affine;                  // nlsh_scan_topk_cells_phase_sq8: `corpus` holds sq8 codes in the uint8 layout (storage = NLSH_STORE_U8) and the
+                                  // SCAN phase launches an affine kernel, which takes the quantiser (and the filter) as a second parameter
+    const float *quant_lo;        // affine: [row_stride] per-dimension offsets, padded to the pitch with 0 (device, 16-byte aligned)
+    const float *quant_step;      // affine: [row_stride] per-dimension steps, padded with 1
     bool tiled() const { return algo == NLSH_SCAN_BUCKET_TILED; }
 };
 // internal phase bit (not part of the C ABI's phase mask): the PLAN phase WITHOUT the bucket lookup, which the batch's encode_hash
@@ -469,5 +473,7 @@ inline int scan_call_run(const BucketScanCall &c) { return c.algo == NLSH_SCAN_Q
 const void *typed_scan_kernel_of(int storage, int metric, bool wide);
 // the tiled scan kernel behind a row filter (scan_bucket_filtered.hip): any storage; its parameters are (BArgs, const uint32_t *row_filter)
 const void *filtered_scan_kernel_of(int storage, int metric, bool wide);
+// the tiled scan kernel over an sq8 corpus (scan_bucket_affine.hip): its parameters are (BArgs, QuantArgs), the filter inside the second
+const void *affine_scan_kernel_of(int metric, bool wide);
 
 }  // namespace nlsh

@@ -381,8 +381,10 @@ int scan_call_check(const char *who, const BucketScanCall &c, unsigned needs) {
     const char *tiled_only = "the tiled schedule only (NLSH_SCAN_BUCKET_TILED)";
     NLSH_REQUIRE(topk || c.tiled(), NLSH_E_UNSUPPORTED, "%s: a radius query is scanned by %s, not by algo=%d", who, tiled_only, c.algo);
     NLSH_REQUIRE(!c.row_filter || c.tiled(), NLSH_E_UNSUPPORTED, "%s: row_filter is read by %s, not by algo=%d", who, tiled_only, c.algo);
+    NLSH_REQUIRE(!c.affine || c.tiled(), NLSH_E_UNSUPPORTED, "%s: an sq8 corpus is read by %s, not by algo=%d", who, tiled_only, c.algo);
     NLSH_REQUIRE(c.storage == NLSH_STORE_F32 || c.tiled(), NLSH_E_UNSUPPORTED, "%s: a %s corpus (storage=%d) is read by %s, not by algo=%d", who,
                  c.storage == NLSH_STORE_F16 ? "float16" : "uint8", c.storage, tiled_only, c.algo);
+    NLSH_REQUIRE(!c.affine || c.storage == NLSH_STORE_U8, NLSH_E_INVALID, "%s: an sq8 corpus is held in the uint8 layout, not storage=%d", who, c.storage);
     NLSH_REQUIRE(((uintptr_t)c.row_filter & 3) == 0, NLSH_E_INVALID, "%s: row_filter must be 4-byte aligned", who);
     // A compressed copy's pitch is held HERE for the top-k calls, ahead of the limits and of the empty batch, as the typed entry always
     // did; float32 rows and the radius calls have theirs held behind both, below: each entry keeps the code it had.
@@ -405,6 +407,9 @@ int scan_call_check(const char *who, const BucketScanCall &c, unsigned needs) {
     NLSH_REQUIRE(!topk || (c.out_dist && c.out_idx && c.out_ncand), NLSH_E_INVALID, "%s: null pointer (out_dist, out_idx or out_ncand)", who);
     NLSH_REQUIRE(c.nb == 0 || (c.corpus && c.gid && c.uniq && c.offsets), NLSH_E_INVALID, "%s: null index pointer", who);
     NLSH_REQUIRE(c.metric != NLSH_METRIC_COSINE || c.nb == 0 || c.inv_norm, NLSH_E_INVALID, "%s: cosine needs inv_norm", who);
+    // the quantiser of an sq8 corpus: two arrays of row_stride floats, read as the float4 of a chunk column
+    NLSH_REQUIRE(!c.affine || (c.quant_lo && c.quant_step), NLSH_E_INVALID, "%s: null pointer (lo or step)", who);
+    NLSH_REQUIRE(!c.affine || ((((uintptr_t)c.quant_lo | (uintptr_t)c.quant_step) & 15) == 0), NLSH_E_INVALID, "%s: lo and step must be 16-byte aligned", who);
     if (!pitch_first && (rc = corpus_pitch_check(who, c)) != NLSH_OK) return rc;
     NLSH_REQUIRE(c.q_stride >= c.d, NLSH_E_INVALID, "%s: q_stride=%lld < d=%d", who, c.q_stride, c.d);
     // the task table and the partial lists are read with 16- and 8-byte accesses at 256-byte offsets of the workspace
@@ -498,6 +503,23 @@ extern "C" int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, in
     c.phases = phases; c.storage = storage; c.row_filter = row_filter;
     // without a filter this IS the typed call (include/nlsh_hip.h), and says so in its refusals
     return topk_call(row_filter ? "scan_topk_filtered" : "scan_topk_typed", c);
+}
+
+// The filtered call over an sq8 corpus: uint8 layout, the quantiser behind the filter.  Not a fourth storage code of the typed calls
+// (they answer NLSH_E_INVALID to anything past NLSH_STORE_U8): an entry of its own.
+extern "C" int nlsh_scan_topk_cells_phase_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d,
+                              const int32_t *gid, const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
+                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
+                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
+                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                              const uint32_t *row_filter) {
+    NLSH_TOPK_CALL(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
+    c.phases = phases; c.storage = NLSH_STORE_U8; c.row_filter = row_filter;
+    c.affine = true; c.quant_lo = lo; c.quant_step = step;
+    return topk_call("scan_topk_sq8", c);
 }
 
 extern "C" int nlsh_merge_topk(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,

@@ -46,6 +46,7 @@ SYMBOLS = (
     "nlsh_row_filter_words", "nlsh_row_filter_build", "nlsh_scan_topk_cells_phase_filtered",
     "nlsh_merge_topk_unique",
     "nlsh_range_workspace", "nlsh_range_sort_workspace", "nlsh_range_count", "nlsh_range_fill",
+    "nlsh_sq8_train_workspace", "nlsh_sq8_train", "nlsh_gather_rows_sq8", "nlsh_csr_update_sq8", "nlsh_scan_topk_cells_phase_sq8",
 )
 
 
@@ -163,6 +164,19 @@ def lib():
     L.nlsh_range_count.argtypes = range_head + [vp, vp, vp, vp, sz, i64, vp, vp, vp]
     L.nlsh_range_fill.restype = i32      # ... row_offsets, total, cursor | out_keys, out_dist, out_idx | status, workspace, bytes, max_tasks | sort workspace, bytes | scan events, stream
     L.nlsh_range_fill.argtypes = range_head + [vp, i64, vp, vp, vp, vp, vp, vp, sz, i64, vp, sz, vp, vp, vp]
+    # storage="sq8": the uint8 layout plus (lo, step); entry points of their own, the typed calls keep refusing storage codes past STORE_U8
+    L.nlsh_sq8_train_workspace.restype = sz
+    L.nlsh_sq8_train_workspace.argtypes = [i64, i32]
+    L.nlsh_sq8_train.restype = i32             # rows, storage, row_stride, d, n | lo, step, quant_stride | first_bad | workspace, bytes, stream
+    L.nlsh_sq8_train.argtypes = [vp, i32, i64, i32, i64, vp, vp, i64, vp, vp, sz, vp]
+    L.nlsh_gather_rows_sq8.restype = i32       # (corpus, storage) ... sorted, dst_stride, lo, step ... first_bad, clamped_rows, stream
+    L.nlsh_gather_rows_sq8.argtypes = [vp, i32, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]
+    L.nlsh_csr_update_sq8.restype = i32        # the typed update with (lo, step) in place of the storage code and clamped_rows behind first_bad
+    L.nlsh_csr_update_sq8.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, i64,  vp, i64,  vp, i32, i64, vp, vp, i64,
+                                      vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,  vp, sz, vp]
+    L.nlsh_scan_topk_cells_phase_sq8.restype = i32     # the filtered call with (lo, step) in place of the storage code
+    L.nlsh_scan_topk_cells_phase_sq8.argtypes = (L.nlsh_scan_topk_cells_phase_filtered.argtypes[:1] + [vp, vp]
+                                                 + L.nlsh_scan_topk_cells_phase_filtered.argtypes[2:])
     L.nlsh_row_filter_words.restype = sz
     L.nlsh_row_filter_words.argtypes = [i64]
     L.nlsh_row_filter_build.restype = i32      # gid, n_rows | ids, n_ids | dense, n_dense, id_base | invert | row_filter, n_allowed, stream

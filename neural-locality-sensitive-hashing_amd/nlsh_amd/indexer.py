@@ -166,8 +166,31 @@ def build_index(indexes, cuda=True) -> Dict[int, torch.Tensor]:
 
 
 # `storage=`: element type of the bucket-sorted corpus copy -> (torch dtype, NLSH_STORE_* code, elements per 16 bytes)
-_STORAGES = {"float32": (torch.float32, _capi.STORE_F32, 4), "float16": (torch.float16, _capi.STORE_F16, 8), "uint8": (torch.uint8, _capi.STORE_U8, 16)}
+#   "sq8" holds uint8 CODES in the uint8 layout and decodes them with the index's per-dimension quantiser: its calls
+#   are the *_sq8 entry points, the typed ones never see it
+_STORAGES = {"float32": (torch.float32, _capi.STORE_F32, 4), "float16": (torch.float16, _capi.STORE_F16, 8), "uint8": (torch.uint8, _capi.STORE_U8, 16),
+             "sq8": (torch.uint8, _capi.STORE_U8, 16)}
 _STORE_CODE_OF_DTYPE = {dt: code for dt, code, _ in _STORAGES.values()}
+
+
+def checked_quantiser(quantiser, d):
+    """`quantiser=` of an sq8 index, checked on the host before anything touches a device -> (lo, step) float32 [d] host tensors."""
+    if not isinstance(quantiser, (tuple, list)) or len(quantiser) != 2:
+        raise ValueError("quantiser must be a pair (lo, step) of float32 [d] arrays")
+    out = []
+    for name, v in zip(("lo", "step"), quantiser):
+        t = torch.as_tensor(v)
+        if t.dtype != torch.float32:
+            raise ValueError(f"quantiser {name} must be float32, got {t.dtype}")
+        if tuple(t.shape) != (d,):
+            raise ValueError(f"quantiser {name} must have shape ({d},), got {tuple(t.shape)}")
+        t = t.detach().cpu().contiguous()
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"quantiser {name} must be finite")
+        out.append(t)
+    if not bool((out[1] > 0).all()):
+        raise ValueError("quantiser step must be > 0 in every dimension")
+    return out[0], out[1]
 
 
 class RowFilter:
@@ -207,15 +230,26 @@ class Indexer:
                  seg_rows: int = 0, id_base: int = 0, algo: Optional[str] = None,
                  row_ids: Optional[torch.Tensor] = None, schedule_stats: Optional[Tuple[float, float]] = None,
                  corpus_keys: Optional[torch.Tensor] = None, l2_form: str = "exact", window_rows: Optional[int] = None,
-                 row_align: int = 4, storage: Optional[str] = None):
+                 row_align: int = 4, storage: Optional[str] = None, quantiser=None):
         # storage: None / "float32" = the float32 copy (any other corpus dtype is converted with `.float()`, as ever); "float16" /
-        # "uint8" = a compressed copy, read by the tiled schedule only (checked before anything touches a device)
+        # "uint8" / "sq8" = a compressed copy, read by the tiled schedule only (checked before anything touches a device)
         if storage is not None and storage not in _STORAGES:
             raise ValueError(f"storage must be None or one of {tuple(_STORAGES)}, got {storage!r}")
         self.storage = storage or "float32"
         if self.compressed and algo in ("query", "bucket"):
             raise ValueError(f"algo={algo!r} cannot read storage={self.storage!r}: a compressed index is scanned by the tiled schedule only "
                              "(algo=None or 'tiled')")
+        # quantiser (storage="sq8" only): None = train on the (float) corpus; (lo, step), float32 [d] = use it.  A uint8 corpus is codes
+        # and has nothing to train on.
+        if quantiser is not None and self.storage != "sq8":
+            raise ValueError(f"quantiser= belongs to storage='sq8', not storage={self.storage!r}")
+        self._quantiser_given = None
+        if self.storage == "sq8":
+            if quantiser is not None:
+                self._quantiser_given = checked_quantiser(quantiser, int(candidate_vectors_gpu.shape[1]))
+            elif candidate_vectors_gpu.dtype == torch.uint8:
+                raise ValueError("a uint8 corpus is sq8 codes: storage='sq8' needs quantiser=(lo, step) to decode them")
+        self.last_clamped_rows = 0  # sq8: rows of the last encode (build / add / update) with at least one saturated element
         self._hashing = hashing
         self._candidate_vectors_gpu = candidate_vectors_gpu
         self._distance_func = distance_func
@@ -268,14 +302,71 @@ class Indexer:
     def compressed(self):
         return self.storage != "float32"
 
-    def _dequantised(self, rows):
+    def _dequantised(self, rows, row_base=0):
         """Rows as the index holds them, in float32: `rows.to(storage).float()` (both steps exact on representable values)."""
+        if self.storage == "sq8":
+            # codes decode as they are; anything else is encoded first (the library's kernel: the one statement of the rule on the
+            # device) -- deq(c, j) = float(c) * step[j] + lo[j] as two separately rounded torch operations
+            codes = rows if rows.dtype == torch.uint8 else self._sq8_encode(rows, "corpus", row_base)[:, :self.dim]
+            return codes.float() * self._qstep[:self.dim] + self._qlo[:self.dim]
         dtype = _STORAGES[self.storage][0]
         return (rows if rows.dtype == dtype else rows.to(dtype)).float()
+
+    @property
+    def quantiser(self):
+        """(lo, step) of an sq8 index: float32 [d], on the device (views of the pitch-padded arrays the kernels read)."""
+        if self.storage != "sq8":
+            raise AttributeError(f"storage={self.storage!r} has no quantiser")
+        return self._qlo[:self.dim], self._qstep[:self.dim]
+
+    def _sq8_set_quantiser(self, corpus, d, stride, dev):
+        """The pitch-padded quantiser arrays (lo = 0, step = 1 behind d): the given one, or trained on `corpus` by `nlsh_sq8_train`."""
+        L = _capi.lib()
+        self._qlo = torch.zeros((stride,), dtype=torch.float32, device=dev)
+        self._qstep = torch.ones((stride,), dtype=torch.float32, device=dev)
+        if self._quantiser_given is not None:
+            self._qlo[:d], self._qstep[:d] = self._quantiser_given[0].to(dev), self._quantiser_given[1].to(dev)
+            return
+        N = int(corpus.shape[0])
+        wb = L.nlsh_sq8_train_workspace(N, d)
+        if wb == 0:
+            _capi.check(_capi.E_INVALID)
+        ws = torch.empty((wb,), dtype=torch.uint8, device=dev)
+        first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
+        _capi.check(L.nlsh_sq8_train(_capi.ptr(corpus), _STORE_CODE_OF_DTYPE[corpus.dtype], corpus.stride(0) if N else d, d, N, _capi.ptr(self._qlo),
+                                     _capi.ptr(self._qstep), stride, _capi.ptr(first_bad), _capi.ptr(ws), wb, _stream(dev)))
+        bad = int(first_bad.item())
+        if bad >= 0:
+            self._raise_unrepresentable(bad, self.storage, "corpus")
+        wide = torch.nonzero(~torch.isfinite(self._qstep[:d])).reshape(-1)
+        if wide.numel():
+            raise ValueError(f"corpus column {int(wide[0])}: max - min overflows float32, no sq8 step can span it")
+
+    def _sq8_encode(self, rows, what, row_base=0):
+        """Float rows [M, d] (float32 / float16, unit column stride) -> their codes uint8 [M, row_stride] by the index's quantiser
+        (`nlsh_gather_rows_sq8`, identity order).  A row with a NaN or an infinity raises ValueError naming it; saturated rows are
+        counted in `last_clamped_rows`."""
+        dev, M = rows.device, int(rows.shape[0])
+        if rows.dtype not in (torch.float32, torch.float16):
+            rows = rows.float()
+        if rows.dim() != 2 or rows.stride(1) != 1:
+            rows = rows.contiguous()
+        held = torch.empty((M, self.row_stride), dtype=torch.uint8, device=dev)
+        flags = torch.empty((2,), dtype=torch.int32, device=dev)
+        _capi.check(_capi.lib().nlsh_gather_rows_sq8(
+            _capi.ptr(rows), _STORE_CODE_OF_DTYPE[rows.dtype], rows.stride(0) if M else self.dim, self.dim,
+            _capi.ptr(torch.arange(M, dtype=torch.int32, device=dev)), M, _capi.ptr(held), self.row_stride, _capi.ptr(self._qlo),
+            _capi.ptr(self._qstep), None, None, 0, _capi.ptr(flags[0:1]), _capi.ptr(flags[1:2]), _stream(dev)))
+        bad, clamped = flags.cpu().tolist()
+        if bad >= 0:
+            self._raise_unrepresentable(row_base + bad, self.storage, what)
+        self.last_clamped_rows = int(clamped)
+        return held
 
     @staticmethod
     def _raise_unrepresentable(bad_row, storage, what):
         rule = ("a finite value that float16 rounds to an infinity" if storage == "float16"
+                else "a NaN or an infinity" if storage == "sq8"
                 else "a value that is not an integer in [0, 255]")
         raise ValueError(f"{what} row {bad_row} holds {rule}: it cannot be stored as storage={storage!r} (nothing was changed)")
 
@@ -295,6 +386,14 @@ class Indexer:
         if corpus.stride(1) != 1:
             corpus = corpus.contiguous()
         dev = corpus.device
+        if self.storage == "sq8":
+            # the quantiser comes first: the keys below are those of the DECODED rows (one read of the corpus trains it; the chunks
+            # that are hashed are encoded and decoded HASH_BATCH rows at a time, the sorted copy is encoded from the caller's rows)
+            self.dim = d
+            align = max(4, int(self.row_align))
+            align = align * per16 // np.gcd(align, per16)
+            self.row_stride = int((d + align - 1) // align * align)
+            self._sq8_set_quantiser(corpus, d, self.row_stride, dev)
         if self._given_keys is not None:
             keys = self._given_keys
             if keys.shape != (N,) or keys.dtype != torch.int32 or keys.device != dev:
@@ -310,7 +409,7 @@ class Indexer:
             per_batch = needs_train is not None and needs_train()
             keys = torch.empty((N, 1), dtype=torch.int32, device=dev)
             for lo in range(0, N, HASH_BATCH):
-                part = self._dequantised(corpus[lo:lo + HASH_BATCH])
+                part = self._dequantised(corpus[lo:lo + HASH_BATCH], row_base=lo)
                 keys[lo:lo + HASH_BATCH] = self.hash_device(part, hash_times=1, seed=None if (lo == 0 or per_batch) else 0)[0]
         self.corpus_keys = keys.view(-1)
         self.perm, self.uniq_keys, self.offsets = build_csr_device(self.corpus_keys)
@@ -323,9 +422,17 @@ class Indexer:
         self.gid = torch.empty((N,), dtype=torch.int32, device=dev)
         self.inv_norm = torch.empty((N,), dtype=torch.float32, device=dev) if self.metric == "cosine" else None
         first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
-        _capi.check(L.nlsh_gather_rows_typed(_capi.ptr(corpus), _STORE_CODE_OF_DTYPE[corpus.dtype], corpus.stride(0) if N else d, d,
-                                             _capi.ptr(self.perm), N, _capi.ptr(self.corpus_sorted), code, self.row_stride,
-                                             _capi.ptr(self.inv_norm), _capi.ptr(self.gid), self.id_base, _capi.ptr(first_bad), _stream(dev)))
+        if self.storage == "sq8":
+            clamped = torch.empty((1,), dtype=torch.int32, device=dev)
+            _capi.check(L.nlsh_gather_rows_sq8(_capi.ptr(corpus), _STORE_CODE_OF_DTYPE[corpus.dtype], corpus.stride(0) if N else d, d,
+                                               _capi.ptr(self.perm), N, _capi.ptr(self.corpus_sorted), self.row_stride, _capi.ptr(self._qlo),
+                                               _capi.ptr(self._qstep), _capi.ptr(self.inv_norm), _capi.ptr(self.gid), self.id_base,
+                                               _capi.ptr(first_bad), _capi.ptr(clamped), _stream(dev)))
+            self.last_clamped_rows = int(clamped.item())
+        else:
+            _capi.check(L.nlsh_gather_rows_typed(_capi.ptr(corpus), _STORE_CODE_OF_DTYPE[corpus.dtype], corpus.stride(0) if N else d, d,
+                                                 _capi.ptr(self.perm), N, _capi.ptr(self.corpus_sorted), code, self.row_stride,
+                                                 _capi.ptr(self.inv_norm), _capi.ptr(self.gid), self.id_base, _capi.ptr(first_bad), _stream(dev)))
         bad = int(first_bad.item())
         if bad >= 0:
             self._raise_unrepresentable(bad, self.storage, "corpus")
@@ -455,6 +562,15 @@ class Indexer:
                 _capi.ptr(vectors), vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
                 _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
                 _capi.ptr(nb_out), _capi.ptr(ws), ws_bytes, _stream(dev)))
+        elif self.storage == "sq8":
+            # kept rows move as bytes; the new rows arrive as codes (`_new_rows` has encoded float ones and counted the saturated rows);
+            # new rows' inv_norm over the decoded values
+            _capi.check(L.nlsh_csr_update_sq8(
+                _capi.ptr(self.corpus_sorted), _capi.ptr(self._qlo), _capi.ptr(self._qstep), stride, self.dim, _capi.ptr(self.gid),
+                _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys), _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
+                _capi.ptr(vectors), _capi.STORE_U8, vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
+                _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
+                _capi.ptr(nb_out), None, None, _capi.ptr(ws), ws_bytes, _stream(dev)))
         else:
             # kept rows move as bytes; the new rows arrive in the storage's dtype (`_new_rows` has converted and checked float32 ones).  The
             # call itself also converts -- C callers hand it rows of another storage -- and reports through `first_bad`; out of place, so
@@ -515,12 +631,20 @@ class Indexer:
         if add.dim() != 2 or add.shape[1] != self.dim:
             raise ValueError(f"added rows must be [M, {self.dim}], got {tuple(add.shape)}")
         if add.dtype != torch.float32 and not (self.compressed and add.dtype == _STORAGES[self.storage][0]):
-            raise ValueError(f"added rows must be float32{' or ' + self.storage if self.compressed else ''}, got {add.dtype}")
+            own = "uint8 (codes)" if self.storage == "sq8" else self.storage
+            raise ValueError(f"added rows must be float32{' or ' + own if self.compressed else ''}, got {add.dtype}")
         M = int(add.shape[0])
         if M == 0:
             return None, None, None
         vectors = add if add.stride(1) == 1 else add.contiguous()
-        if self.compressed and vectors.dtype == torch.float32:
+        if self.storage == "sq8":
+            # float32 rows are encoded FIRST by the index's quantiser (saturating: `last_clamped_rows`; a NaN or an infinity is refused
+            # before the hasher is touched); uint8 rows are codes.  What is hashed and merged below is the rows as the index holds them.
+            if vectors.dtype == torch.float32:
+                vectors = self._sq8_encode(vectors, "added")[:, :self.dim]
+            else:
+                self.last_clamped_rows = 0
+        elif self.compressed and vectors.dtype == torch.float32:
             # float32 rows into a compressed index are converted and checked FIRST (the typed gather with the identity permutation: the
             # one conversion rule, one device flag): a refusal comes before the hasher is touched, and what is hashed and merged below
             # is the rows as the index will hold them
@@ -1004,8 +1128,11 @@ class Indexer:
         Q, d = q.shape
         f = self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window)
         before = _SCAN_ARGS_BEFORE_QUERIES(f)
-        _capi.check(_capi.lib().nlsh_scan_topk_cells_phase_filtered(
-            before[0], _STORAGES[self.storage][1], *before[1:], q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
+        # an sq8 index has the call of its own: the quantiser's two arrays stand where the storage code does
+        call, store = ((_capi.lib().nlsh_scan_topk_cells_phase_sq8, (self._qlo.data_ptr(), self._qstep.data_ptr())) if self.storage == "sq8"
+                       else (_capi.lib().nlsh_scan_topk_cells_phase_filtered, (_STORAGES[self.storage][1],)))
+        _capi.check(call(
+            before[0], *store, *before[1:], q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
             events[0].cuda_event if events else None, events[1].cuda_event if events else None,
             _stream(q.device) if stream is None else stream, phases, None if filter is None else filter.words.data_ptr()))
 
@@ -1056,6 +1183,11 @@ class Indexer:
             r32 = np.full((Q,), radius, dtype=np.float64).astype(np.float32)    # the float32 the kernel compares with (beyond its range: +-inf)
         return torch.as_tensor(r32).to(dev)
 
+    def _refuse_range_on_sq8(self):
+        if self.storage == "sq8":
+            raise NotImplementedError("radius (range) queries are not built for storage='sq8': the range kernels read float32, float16 "
+                                      "and uint8 rows only (DESIGN.md 7)")
+
     def _metric_code(self):
         return (_capi.METRIC_L2_EPS_FOLDED if self.l2_form == "folded" else _capi.METRIC_L2_EPS) if self.metric == "l2" else _capi.METRIC_COSINE
 
@@ -1082,6 +1214,7 @@ class Indexer:
         limit (None = off): ValueError once the counts are known and before any output is allocated, if T > limit.
         Two scan launches with one host read between them (`nlsh_range_count`, `nlsh_range_fill`): the call synchronises.  Always the
         tiled schedule, as filtered and compressed calls; key tables wider than 64 probes are refused."""
+        self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("range queries need metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
@@ -1145,6 +1278,7 @@ class Indexer:
                       want_keys=False):
         """Device-resident radius query: the hash by the two-step route (`last_query_path == "two_step"`; probes / candidate_budget as in
         `query_tensors`), then `range_scan_tensors`.  hash_times <= 64."""
+        self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("range queries need metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
@@ -1175,6 +1309,7 @@ class Indexer:
 
     def range_query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], radius, filter=None, return_distances=False):
         """`range_query` on caller-supplied key lists, like `query_with_keys`."""
+        self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
         key_lists = [list(dict.fromkeys(int(key) for key in ks)) for ks in key_lists]
         Q = len(key_lists)

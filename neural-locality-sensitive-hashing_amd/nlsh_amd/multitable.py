@@ -57,7 +57,9 @@ class MultiTableIndexer:
 
     def __init__(self, hashings, candidate_vectors_gpu, distance_func, metric: Optional[str] = None, storage: Optional[str] = None,
                  l2_form: str = "exact", row_align: int = 4, window_rows: Optional[int] = None, corpus_keys=None,
-                 row_ids: Optional[torch.Tensor] = None, id_base: int = 0):
+                 row_ids: Optional[torch.Tensor] = None, id_base: int = 0, quantiser=None):
+        if quantiser is not None and storage != "sq8":
+            raise ValueError(f"quantiser= belongs to storage='sq8', not storage={storage!r}")
         hashings = list(hashings)
         if not hashings:
             raise ValueError("hashings is empty: a multi-table index needs at least one hasher")
@@ -77,11 +79,14 @@ class MultiTableIndexer:
         self.metric = metric or metric_of(distance_func)
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("a multi-table index needs metric 'l2' or 'cosine': its merge rests on the tiled schedule's distance bits")
-        self.tables: List[Indexer] = [
-            Indexer(h, candidate_vectors_gpu, distance_func, compat=False, metric=self.metric, algo="tiled", storage=storage,
-                    l2_form=l2_form, row_align=row_align, window_rows=window_rows, row_ids=row_ids, id_base=id_base,
-                    corpus_keys=None if corpus_keys is None else corpus_keys[t])
-            for t, h in enumerate(hashings)]
+        # storage="sq8": ONE quantiser for all tables -- the given one, or the one the first table trains on the corpus -- so that every
+        # table holds the same decoded rows and a row's distance has one value whichever table finds it (the merge rests on that)
+        self.tables: List[Indexer] = []
+        for t, h in enumerate(hashings):
+            kw = {} if storage != "sq8" else {"quantiser": quantiser if t == 0 else self.tables[0].quantiser}
+            self.tables.append(Indexer(h, candidate_vectors_gpu, distance_func, compat=False, metric=self.metric, algo="tiled", storage=storage,
+                                       l2_form=l2_form, row_align=row_align, window_rows=window_rows, row_ids=row_ids, id_base=id_base,
+                                       corpus_keys=None if corpus_keys is None else corpus_keys[t], **kw))
         self.storage = self.tables[0].storage
         self.generation = 0         # +1 per effective add / remove / update: a MultiRowFilter of an older one is stale
 

@@ -9,10 +9,13 @@ Workloads (the generators bench.py uses, the learned hashes of checkpoints/):
   clusters  synth.sift_like (SURVEY 8(d)'s generator), 10^6 x 128, L2, 16-bit hash; raw integers, as above.
   glove     synth.glove_manifold, 1,183,514 x 100, cosine, 24-bit hash.  Real-valued: float16 holds the rounded rows, float32 holds the SAME
             rounded rows (dequantised), uint8 does not apply.
+  deep      synth.deep_like, 10^6 x 96, L2-normalised rows, L2, a seeded random 16-bit hash.  Real-valued, as glove.
 Every storage of a workload gets the same `corpus_keys=` and the same query key table, so the task tables are identical and the results
-are compared bit for bit before anything is timed.
+are compared bit for bit before anything is timed.  `--sq8` adds an sq8 index of the same rows to every workload (same keys, same task
+table, its own distances): recall@10 against the float32 lists and the training pass beside a device copy are reported with the times
+(profiles/sq8_storage.txt is made from it).
 
-    python tools/storage_bench.py [--workloads sift1m,clusters,glove] [--rounds 7] [--iters 10] [--steps 20] [--out FILE]
+    python tools/storage_bench.py [--workloads sift1m,clusters,glove,deep] [--sq8] [--rounds 7] [--iters 10] [--steps 20] [--out FILE]
 
 Prints one JSON line per workload and a table; `--out` also writes the table to a file (profiles/corpus_storage.txt is made from it).
 """
@@ -38,49 +41,101 @@ WORKLOADS = {
     "sift1m": dict(gen="sift_manifold", N=1_000_000, d=128, ckpt="sift1m_manifold_h16.npz", metric="l2", compat=True, storages=("float32", "float16", "uint8")),
     "clusters": dict(gen="sift_like", N=1_000_000, d=128, ckpt="sift1m_clusters_h16.npz", metric="l2", compat=True, storages=("float32", "float16", "uint8")),
     "glove": dict(gen="glove_manifold", N=1_183_514, d=100, ckpt="glove_manifold_h24.npz", metric="cosine", compat=False, storages=("float32", "float16")),
+    # Deep-shaped: synth.deep_like, L2-normalised 96-d rows.  No checkpoint was trained on this generator: a seeded random 16-bit MLP hash
+    # (synth.make_weights) gives the buckets -- the storages are compared on one task table, the hash's quality does not enter.
+    "deep": dict(gen="deep_like", N=1_000_000, d=96, ckpt=None, metric="l2", compat=False, storages=("float32", "float16")),
 }
 DTYPE = {"float32": torch.float32, "float16": torch.float16, "uint8": torch.uint8}
+# `--sq8`: every workload also gets an sq8 index built from the SAME rows with the same corpus_keys= and timed in the same
+# interleaved rounds.  Its rows are deq(enc(x)), not x: it is not held to the float32 bits here (tests/test_gpu_sq8_storage.py holds it to
+# its own float32 twin); what is reported instead is recall@10 of its lists against the float32 index's at the same probes, and the
+# training pass's time beside a plain device copy of the same bytes.
 
 
-def build(tag, n_rows, Q, dev):
-    """-> ({storage: Indexer}, query batch, key table, (distinct candidate rows, candidates) of the batch)."""
+def train_vs_copy(rows, stride, rounds=7):
+    """(median ms of `nlsh_sq8_train` over `rows`, median ms of a device copy of the same bytes), interleaved."""
+    from nlsh_amd import _capi
+    L, (n, d), dev = _capi.lib(), rows.shape, rows.device
+    lo, step = torch.empty((stride,), device=dev), torch.empty((stride,), device=dev)
+    bad = torch.empty((1,), dtype=torch.int32, device=dev)
+    wb = L.nlsh_sq8_train_workspace(n, d)
+    ws = torch.empty((wb,), dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(rows)
+    s = torch.cuda.current_stream().cuda_stream
+    t_train, t_copy = [], []
+    for r in range(rounds + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        _capi.check(L.nlsh_sq8_train(rows.data_ptr(), _capi.STORE_F32, rows.stride(0), d, n, lo.data_ptr(), step.data_ptr(), stride,
+                                     bad.data_ptr(), ws.data_ptr(), wb, s))
+        ev[1].record()
+        dst.copy_(rows)
+        ev[2].record()
+        torch.cuda.synchronize()
+        if r:       # the first round warms up
+            t_train.append(ev[0].elapsed_time(ev[1])); t_copy.append(ev[1].elapsed_time(ev[2]))
+    return float(np.median(t_train)), float(np.median(t_copy))
+
+
+def recall_at_k(got_idx, ref_idx):
+    """Mean fraction of the reference lists' ids (padding excluded) that the other lists hold."""
+    g, r = got_idx.cpu().numpy(), ref_idx.cpu().numpy()
+    hits = sum(len(set(a[a >= 0].tolist()) & set(b[b >= 0].tolist())) for a, b in zip(g, r))
+    return hits / max(int((r >= 0).sum()), 1)
+
+
+def build(tag, n_rows, Q, dev, sq8=False):
+    """-> ({storage: Indexer}, query batch, key table, (distinct candidate rows, candidates) of the batch, sq8 extras or None)."""
     w = WORKLOADS[tag]
     N, d = n_rows or w["N"], w["d"]
     gen = getattr(synth, w["gen"])
     corpus_h, queries_h = gen(N, d, seed=synth.SEED_DATA), gen(Q, d, seed=synth.SEED_QUERY)
-    Ws, bs = io.load_hasher_weights(os.path.join(ROOT, "neural-locality-sensitive-hashing_amd", "checkpoints", w["ckpt"]))
+    if w["ckpt"]:
+        Ws, bs = io.load_hasher_weights(os.path.join(ROOT, "neural-locality-sensitive-hashing_amd", "checkpoints", w["ckpt"]))
+    else:
+        Ws, bs = synth.make_weights([d, 256, 16], gain=4.0)
     Ws, bs = [np.asarray(W, np.float32) for W in Ws], [np.asarray(b, np.float32) for b in bs]
-    if w["metric"] == "l2":     # raw integral rows: the hash's standardisation moves into its first layer, W (x - m) / s + b = (W / s) x + (b - (W / s) m)
+    if w["metric"] == "l2" and w["ckpt"]:     # raw integral rows: the hash's standardisation moves into its first layer, W (x - m) / s + b = (W / s) x + (b - (W / s) m)
         _, mean, std = synth.standardise(corpus_h)
         Ws[0] = (Ws[0] / std[None, :]).astype(np.float32)
         bs[0] = (bs[0] - Ws[0] @ mean).astype(np.float32)
         assert np.array_equal(corpus_h, np.rint(corpus_h)) and corpus_h.min() >= 0 and corpus_h.max() <= 255
         stored = torch.from_numpy(corpus_h).to(dev)
     else:                       # real-valued rows: every storage holds the float16-rounded values
+        if not w["ckpt"]:       # the seeded hash sees standardised rows, folded into its first layer as above
+            _, mean, std = synth.standardise(corpus_h)
+            Ws[0] = (Ws[0] / std[None, :]).astype(np.float32)
+            bs[0] = (bs[0] - Ws[0] @ mean).astype(np.float32)
         stored = torch.from_numpy(corpus_h).to(dev).half().float()
     hashing = io.hashing_from_weights(Ws, bs, compat=w["compat"])
     dist = SIFT.distance if w["metric"] == "l2" else Glove.distance
     q = torch.from_numpy(queries_h).to(dev)
     ixs, keys_of_rows = {}, None
-    for storage in w["storages"]:
-        src = stored if storage == "float32" else stored.to(DTYPE[storage])
+    for storage in w["storages"] + (("sq8",) if sq8 else ()):
+        src = stored if storage in ("float32", "sq8") else stored.to(DTYPE[storage])
         ix = Indexer(hashing, src, dist, compat=w["compat"], storage=storage, algo="tiled" if storage == "float32" else None, corpus_keys=keys_of_rows)
         keys_of_rows = ix.corpus_keys
         ixs[storage] = ix
         del src
     keys, nkeys = ixs["float32"].hash_device(q, hash_times=P, seed=7)
-    ref = None
+    ref, extras = None, None
     for storage, ix in ixs.items():                 # sizes the task tables (checked calls) and holds every storage to the float32 bits
         out = ix.scan_tensors(q, keys, nkeys, k=K)
         if ref is None:
             ref = out
-        assert torch.equal(out[0].view(torch.int32), ref[0].view(torch.int32)) and torch.equal(out[1], ref[1]) and torch.equal(out[2], ref[2]), storage
+        if storage == "sq8":                        # other rows, by design: the same candidates, its own distances
+            assert torch.equal(out[2], ref[2]), storage
+            t_train, t_copy = train_vs_copy(stored, ix.row_stride)
+            extras = {"recall_at_k_vs_float32": recall_at_k(out[1], ref[1]), "clamped_rows": ix.last_clamped_rows,
+                      "train_ms": t_train, "copy_ms": t_copy, "train_bytes": int(stored.numel() * 4)}
+        else:
+            assert torch.equal(out[0].view(torch.int32), ref[0].view(torch.int32)) and torch.equal(out[1], ref[1]) and torch.equal(out[2], ref[2]), storage
         ix.query_tensors(q, k=K, hash_times=P, seed=7)
     ix = ixs["float32"]
     pos = torch.searchsorted(ix.uniq_keys, keys.clamp(min=int(ix.uniq_keys[0]), max=int(ix.uniq_keys[-1]))).clamp(max=ix.n_buckets - 1)
     hit = (ix.uniq_keys[pos] == keys) & (torch.arange(keys.shape[1], device=dev)[None, :] < nkeys[:, None])
     rows = (ix.offsets[1:] - ix.offsets[:-1]).long()
-    return ixs, q, keys, nkeys, (int(rows[torch.unique(pos[hit])].sum().item()), int(ref[2].long().sum().item()))
+    return ixs, q, keys, nkeys, (int(rows[torch.unique(pos[hit])].sum().item()), int(ref[2].long().sum().item())), extras
 
 
 def time_round(ix, q, keys, nkeys, iters, steps):
@@ -114,6 +169,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7, help="interleaved rounds (A B C A B C ...): medians and the min..max spread are over the rounds")
     ap.add_argument("--iters", type=int, default=10, help="scan launches per storage and round")
     ap.add_argument("--steps", type=int, default=20, help="device-resident batches per storage and round")
+    ap.add_argument("--sq8", action="store_true", help="also build and time an sq8 index of every workload (recall and training time reported)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -121,7 +177,7 @@ def main():
     dev = torch.device("cuda", 0)
     lines = []
     for tag in args.workloads.split(","):
-        ixs, q, keys, nkeys, (uniq_rows, sum_c) = build(tag, args.rows, args.queries, dev)
+        ixs, q, keys, nkeys, (uniq_rows, sum_c), extras = build(tag, args.rows, args.queries, dev, sq8=args.sq8)
         d = ixs["float32"].dim
         for ix in ixs.values():     # warm-up round, untimed
             time_round(ix, q, keys, nkeys, 3, 3)
@@ -140,6 +196,8 @@ def main():
             res["storages"][s] = {"index_bytes": int(ix.corpus_sorted.numel() * elem), "row_pitch_bytes": int(ix.row_stride * elem), "scan_ms": scan,
                                   "batch_ms": batch, "route": ix.last_query_path, "scan_vs_float32": scan["median"] / base,
                                   "hbm_frac_of_distinct_candidate_rows": uniq_rows * row_bytes / (scan["median"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+        if extras:
+            res["sq8"] = extras
         print(json.dumps(res), flush=True)
         lines.append(f"{tag}: N={res['N']} d={d} Q={args.queries} k={K} hash_times={P}, {res['n_buckets']} buckets, {uniq_rows} distinct candidate rows, "
                      f"{sum_c} candidates per batch; {args.rounds} interleaved rounds x ({args.iters} scans, {args.steps} batches)")
@@ -149,6 +207,12 @@ def main():
             lines.append(f"  {s:8} {r['index_bytes'] / 2 ** 20:10.1f} {r['row_pitch_bytes']:8d} "
                          f"{r['scan_ms']['median']:10.4f} ({r['scan_ms']['min']:.4f}..{r['scan_ms']['max']:.4f}) {r['scan_vs_float32']:10.3f} "
                          f"{r['hbm_frac_of_distinct_candidate_rows']:9.3f} {r['batch_ms']['median']:10.4f} ({r['batch_ms']['min']:.4f}..{r['batch_ms']['max']:.4f})  {r['route']}")
+        if extras:
+            gbps = lambda ms, passes: extras["train_bytes"] * passes / (ms * 1e-3) / 1e9   # noqa: E731
+            lines.append(f"  sq8: recall@{K} against the float32 index at the same probes {extras['recall_at_k_vs_float32']:.4f}; "
+                         f"{extras['clamped_rows']} rows saturated; training pass {extras['train_ms']:.3f} ms ({gbps(extras['train_ms'], 1):.0f} GB/s read) "
+                         f"beside a device copy of the same {extras['train_bytes'] / 2 ** 20:.0f} MiB {extras['copy_ms']:.3f} ms "
+                         f"({gbps(extras['copy_ms'], 2):.0f} GB/s read + written)")
         del ixs, q, keys, nkeys
         torch.cuda.empty_cache()
     table = "\n".join(lines)
