@@ -532,7 +532,8 @@ int nlsh_range_fill(const void *corpus_sorted, int storage, int64_t row_stride, 
  *   gives lo = 0, step = 1.  first_bad [dev] int32 [1].
  * nlsh_gather_rows_sq8: nlsh_gather_rows_typed with the encoding destination.  A NLSH_STORE_F32 / F16 source is encoded, a NLSH_STORE_U8
  *   source is codes and is copied.  inv_norm (nullable) is computed over the DECODED values in nlsh_gather_rows' operation order.
- *   clamped_rows [dev] int32 [1] (nullable) receives the number of rows with at least one saturated element.
+ *   clamped_rows [dev] int32 [1] (nullable) receives the number of rows with at least one saturated element (a refused row is not
+ *   counted, here or in nlsh_csr_update_sq8).
  * nlsh_csr_update_sq8: nlsh_csr_update_typed on an sq8 index: kept rows move as bytes, new rows of new_storage are encoded on the way in
  *   (NLSH_STORE_U8: codes, copied), new rows' inv_norm over decoded values; first_bad (nullable for NLSH_STORE_U8 rows) and clamped_rows
  *   (nullable) count among the new rows.  row_stride == stride_out when both sides have rows.  Workspace: nlsh_csr_update_workspace.

@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void update_rows_kernel(const float *sorted_ol
     }
 }
 
-// ---- typed storage (NLSH_STORE_*): rows of float32 / float16 / uint8 elements in, rows of any of the three out -------------------------
+// ---- stored rows (NLSH_STORE_* and sq8): rows of float32 / float16 / uint8 elements in, rows of any storage out -----------------------
 // The unit is the 4-element chunk of the float32 kernels above -- one float4 of the dequantised row, 16 / 8 / 4 bytes stored -- dealt to
 // the lanes as there (chunk c to lane c % 64, or to lane c of the row's lane group), so a row's sum of squares is the same fmaf chain and
 // the same butterfly over the same values: inv_norm has the bits the float32 kernels give on the dequantised rows.  A wider pitch only
@@ -456,13 +456,42 @@ __device__ __forceinline__ void report_bad_row(int32_t *first_bad, bool bad, lon
     if (first_bad && bad) atomicMin(reinterpret_cast<unsigned int *>(first_bad), (unsigned int)row);
 }
 
-// gather_rows_kernel between storages: one wavefront per destination row, chunk c of the row on lane c % 64.
-template <int SRC, int DST>
-__global__ __launch_bounds__(256) void gather_rows_typed_kernel(const void *corpus, long long src_stride, int d, const int32_t *perm, long long n,
-                                                                 void *sorted, long long dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
-                                                                 int32_t *first_bad, int vec) {
+// ---- the destination codec: how a row is held.  A codec gives the stored `word` of a chunk, `encode<SRC>` (chunk c of a d-element source
+// row of storage SRC -> its word, with the float4 that word stands for beside it: the encoder has it in hand, and decode(pack(v)) of a
+// uint8 word costs the gather four conversions the compiler cannot fold; sets `bad` when the row must be refused and `clamped` when a
+// value saturated), `decode` (the word of chunk c -> that float4, for a pass that has only the stored row) and `counts_clamped` (are
+// saturated rows counted?).  StoreCodec<DST> is the stateless one of NLSH_STORE_F32 / F16 / U8; Sq8Codec (sq8_rows.h) carries its
+// quantiser.  The three row kernels below are written once on it.
+template <class W> struct HeldChunk { W word; float4 values; };
+template <int DST> struct StoreCodec {
+    typedef typename StoreElem<DST>::word word;
+    static constexpr bool counts_clamped = false;
+    template <int SRC> __device__ __forceinline__ HeldChunk<word> encode(const void *row, int c, int d, bool vec, bool &bad, bool &) const {
+        const float4 v = requantise4<DST>(load_chunk_as_f32<SRC>(row, c, d, vec), bad);
+        return {pack_chunk<DST>(v), v};
+    }
+    __device__ __forceinline__ float4 decode(word w, int) const { return unpack_chunk<DST>(w); }
+};
+
+// One 16-byte unit of a row as the codec holds it: 1, 2 or 4 chunks, encoded from SRC elements.
+template <int SRC, class Codec>
+__device__ __forceinline__ uint4 encode_unit(const Codec &codec, const void *row, int u, int d, bool vec, bool &bad, bool &clamped) {
+    constexpr int CHUNKS = 16 / (int)sizeof(typename Codec::word);
+    struct { typename Codec::word w[CHUNKS]; } unit;
+#pragma unroll
+    for (int j = 0; j < CHUNKS; ++j) unit.w[j] = codec.template encode<SRC>(row, CHUNKS * u + j, d, vec, bad, clamped).word;
+    return __builtin_bit_cast(uint4, unit);
+}
+
+// gather_rows_kernel between storages: one wavefront per destination row, chunk c of the row on lane c % 64.  The sum of squares runs over
+// the values the stored words stand for, in that lane assignment and chain, so inv_norm has the bits nlsh_gather_rows gives on the
+// dequantised rows.
+template <int SRC, class Codec>
+__global__ __launch_bounds__(256) void gather_rows_to_kernel(const void *corpus, long long src_stride, int d, const int32_t *perm, long long n,
+                                                              void *sorted, long long dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
+                                                              int32_t *first_bad, int vec, int32_t *clamped_rows, const Codec codec) {
     typedef typename StoreElem<SRC>::elem src_t;
-    typedef typename StoreElem<DST>::word word_t;
+    typedef typename Codec::word word_t;
     const int lane = threadIdx.x & 63;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
@@ -472,11 +501,11 @@ __global__ __launch_bounds__(256) void gather_rows_typed_kernel(const void *corp
         const src_t *s = static_cast<const src_t *>(corpus) + src * src_stride;
         word_t *dst = static_cast<word_t *>(sorted) + i * (long long)d4;
         float ss = 0.0f;
-        bool bad = false;
+        bool bad = false, clamped = false;
         for (int c = lane; c < d4; c += 64) {
-            const float4 v = requantise4<DST>(load_chunk_as_f32<SRC>(s, c, d, vec != 0), bad);
-            dst[c] = pack_chunk<DST>(v);
-            ss = sumsq_chain(v, ss);
+            const HeldChunk<word_t> h = codec.template encode<SRC>(s, c, d, vec != 0, bad, clamped);
+            dst[c] = h.word;
+            ss = sumsq_chain(h.values, ss);
         }
         if (inv_norm) {
             ss = sumsq_lanes(ss, 64);
@@ -484,49 +513,36 @@ __global__ __launch_bounds__(256) void gather_rows_typed_kernel(const void *corp
         }
         if (gid && lane == 0) gid[i] = (int32_t)src + id_base;
         report_bad_row(first_bad, bad, src);
+        if (Codec::counts_clamped) {
+            const bool row_clamped = __any(clamped) && !__any(bad);      // wave-uniform: the row is the wave's; a refused row is not counted
+            if (clamped_rows && row_clamped && lane == 0) atomicAdd(clamped_rows, 1);
+        }
     }
 }
 
-// One 16-byte unit of a new row (E = 4 / 8 / 16 elements of storage DST = E / 4 chunks), converted from NEW elements.
-template <int NEW, int DST>
-__device__ __forceinline__ uint4 convert_unit(const void *row, int u, int d, bool vec, bool &bad) {
-    if (DST == NLSH_STORE_F32) {
-        const float4 v = requantise4<NLSH_STORE_F32>(load_chunk_as_f32<NEW>(row, u, d, vec), bad);
-        return __builtin_bit_cast(uint4, v);
-    } else if (DST == NLSH_STORE_F16) {
-        const uint2 a = pack_chunk<NLSH_STORE_F16>(requantise4<NLSH_STORE_F16>(load_chunk_as_f32<NEW>(row, 2 * u, d, vec), bad));
-        const uint2 b = pack_chunk<NLSH_STORE_F16>(requantise4<NLSH_STORE_F16>(load_chunk_as_f32<NEW>(row, 2 * u + 1, d, vec), bad));
-        return make_uint4(a.x, a.y, b.x, b.y);
-    } else {
-        uint32_t w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = pack_chunk<NLSH_STORE_U8>(requantise4<NLSH_STORE_U8>(load_chunk_as_f32<NEW>(row, 4 * u + j, d, vec), bad));
-        return make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-// update_rows_kernel on a typed index, generalised from "d floats" to "row bytes": the unit is 16 bytes of the stored row (strides in
+// update_rows_kernel on a stored index, generalised from "d floats" to "row bytes": the unit is 16 bytes of the stored row (strides in
 // 16-byte units), a row has 2^lg lanes covering its units.  Kept rows are moved as bytes; new rows (NEW elements, any alignment) are
-// converted on the way in (columns >= d zero) and the smallest new row that does not survive is reported.  inv_norm is not this
-// kernel's: a lane holds one, two or four chunks of a new row here, which is not the lane assignment the sum of squares is defined
-// on -- update_inv_norm_typed_kernel computes it from the rows this kernel wrote.
-template <int NEW, int DST>
-__global__ __launch_bounds__(256) void update_rows_typed_kernel(const uint4 *sorted_old, long long units_old, long long n_old,
-                                                                 const void *rows_new, long long stride_new, long long m_new, int d,
-                                                                 const int32_t *src, long long n_out, uint4 *sorted_out, long long units_out,
-                                                                 int lg, int32_t *first_bad, int vec) {
+// encoded on the way in (columns >= d zero), the smallest new row that does not survive is reported and the saturated ones are counted.
+// inv_norm is not this kernel's: a lane holds one, two or four chunks of a new row here, which is not the lane assignment the sum of
+// squares is defined on -- update_inv_norm_of_kernel computes it from the rows this kernel wrote.
+template <int NEW, class Codec>
+__global__ __launch_bounds__(256) void update_rows_to_kernel(const uint4 *sorted_old, long long units_old, long long n_old,
+                                                              const void *rows_new, long long stride_new, long long m_new, int d,
+                                                              const int32_t *src, long long n_out, uint4 *sorted_out, long long units_out,
+                                                              int lg, int32_t *first_bad, int vec, int32_t *clamped_rows, const Codec codec) {
     typedef typename StoreElem<NEW>::elem new_t;
     const int lane = threadIdx.x & 63;
     const int lanes = 1 << lg, g = lane & (lanes - 1), rows_per_inst = 64 >> lg;
+    const unsigned long long group = lanes == 64 ? ~0ull : (((1ull << lanes) - 1) << (lane - g));   // the lanes of this lane's row
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
     const long long step = (long long)rows_per_inst * ROWS_IN_FLIGHT;
-    for (long long base = wave * step; base < n_out; base += nwaves * step) {
+    for (long long base = wave * step; base < n_out; base += nwaves * step) {     // wave-uniform
         const uint4 *so[ROWS_IN_FLIGHT];
         const new_t *sn[ROWS_IN_FLIGHT];
         long long p[ROWS_IN_FLIGHT];
         int32_t from[ROWS_IN_FLIGHT];
-        bool bad[ROWS_IN_FLIGHT];
+        bool bad[ROWS_IN_FLIGHT], clamped[ROWS_IN_FLIGHT];
 #pragma unroll
         for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
             p[r] = base + (long long)r * rows_per_inst + (lane >> lg);
@@ -537,14 +553,14 @@ __global__ __launch_bounds__(256) void update_rows_typed_kernel(const uint4 *sor
             const bool ok = p[r] < n_out && j < (is_old ? n_old : m_new);
             so[r] = (ok && is_old) ? sorted_old + j * units_old : nullptr;
             sn[r] = (ok && !is_old) ? static_cast<const new_t *>(rows_new) + j * stride_new : nullptr;
-            bad[r] = false;
+            bad[r] = clamped[r] = false;
         }
         for (int u = g; u < units_out; u += 64) {
             uint4 w[ROWS_IN_FLIGHT];
 #pragma unroll
             for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
                 if (so[r]) w[r] = u < units_old ? so[r][u] : make_uint4(0u, 0u, 0u, 0u);
-                else if (sn[r]) w[r] = convert_unit<NEW, DST>(sn[r], u, d, vec != 0, bad[r]);
+                else if (sn[r]) w[r] = encode_unit<NEW>(codec, sn[r], u, d, vec != 0, bad[r], clamped[r]);
                 else w[r] = make_uint4(0u, 0u, 0u, 0u);
             }
 #pragma unroll
@@ -552,17 +568,23 @@ __global__ __launch_bounds__(256) void update_rows_typed_kernel(const uint4 *sor
                 if (p[r] < n_out) sorted_out[p[r] * units_out + u] = w[r];
         }
 #pragma unroll
-        for (int r = 0; r < ROWS_IN_FLIGHT; ++r) report_bad_row(first_bad, bad[r], (long long)~from[r]);
+        for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
+            report_bad_row(first_bad, bad[r], (long long)~from[r]);
+            if (Codec::counts_clamped) {
+                const unsigned long long cm = __ballot(clamped[r] && !bad[r]), bm = __ballot(bad[r]);
+                if (clamped_rows && g == 0 && (cm & group) && !(bm & group)) atomicAdd(clamped_rows, 1);    // one add per saturated row
+            }
+        }
     }
 }
 
-// inv_norm of the updated typed index: a kept row's value is copied (one lane per row, 64 consecutive rows per wave), a new row's is
-// computed from the row update_rows_typed_kernel stored -- by the whole wave, chunk c on lane c % 64, the 64-lane butterfly: the chain
-// and the bits of gather_rows_typed_kernel (and of the float32 kernels on the dequantised row).
-template <int DST>
-__global__ __launch_bounds__(256) void update_inv_norm_typed_kernel(const void *sorted_out, long long stride_out, const float *inv_old, long long n_old,
-                                                                     const int32_t *src, long long n_out, float *inv_out) {
-    typedef typename StoreElem<DST>::word word_t;
+// inv_norm of the updated stored index: a kept row's value is copied (one lane per row, 64 consecutive rows per wave), a new row's is
+// computed from the row update_rows_to_kernel stored -- by the whole wave, chunk c on lane c % 64, the 64-lane butterfly: the chain
+// and the bits of gather_rows_to_kernel (and of the float32 kernels on the dequantised row).
+template <class Codec>
+__global__ __launch_bounds__(256) void update_inv_norm_of_kernel(const void *sorted_out, long long stride_out, const float *inv_old, long long n_old,
+                                                                  const int32_t *src, long long n_out, float *inv_out, const Codec codec) {
+    typedef typename Codec::word word_t;
     const int lane = threadIdx.x & 63;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
@@ -577,7 +599,7 @@ __global__ __launch_bounds__(256) void update_inv_norm_typed_kernel(const void *
             todo &= todo - 1;
             const word_t *row = static_cast<const word_t *>(sorted_out) + (p0 + l) * (long long)d4;
             float ss = 0.0f;
-            for (int c = lane; c < d4; c += 64) ss = sumsq_chain(unpack_chunk<DST>(row[c]), ss);
+            for (int c = lane; c < d4; c += 64) ss = sumsq_chain(codec.decode(row[c], c), ss);
             ss = sumsq_lanes(ss, 64);
             if (lane == 0) inv_out[p0 + l] = inv_norm_of(ss);
         }
@@ -635,7 +657,7 @@ static void update_layout(long long n_old, long long nb_old, long long m_new, Up
 
 }  // namespace nlsh
 
-#include "sq8_rows.h"   // storage="sq8": training, the encoding gather and the update passes, built from the row helpers above
+#include "sq8_rows.h"   // storage="sq8": its codec and training, built from the row helpers above
 
 using namespace nlsh;
 
@@ -758,29 +780,6 @@ extern "C" int nlsh_build_cells(const int32_t *offsets, int64_t n_buckets, int w
     return nlsh_bucket_order(cell_offsets, n_buckets, cell_order, base + w.order, workspace_bytes - w.order, stream);
 }
 
-extern "C" int nlsh_gather_rows(const float *corpus, int64_t src_stride, int d, const int32_t *perm, int64_t n,
-                                float *sorted, int64_t dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
-                                nlsh_stream_t stream) {
-    NLSH_REQUIRE(n >= 0 && d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "gather_rows: n=%lld d=%d", (long long)n, d);
-    if (n == 0) return NLSH_OK;
-    NLSH_REQUIRE(corpus && perm && sorted, NLSH_E_INVALID, "gather_rows: null pointer");
-    NLSH_REQUIRE(dst_stride >= d && (dst_stride & 3) == 0 && ((uintptr_t)sorted & 15) == 0, NLSH_E_INVALID,
-                 "gather_rows: dst_stride=%lld must be >= d, a multiple of 4, and `sorted` 16-byte aligned", (long long)dst_stride);
-    NLSH_REQUIRE(src_stride >= d, NLSH_E_INVALID, "gather_rows: src_stride < d");
-    hipStream_t s = (hipStream_t)stream;
-    long long blocks = (n + 3) / 4;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    bool vec = ((src_stride & 3) == 0) && (((uintptr_t)corpus & 15) == 0);
-    if (vec)
-        hipLaunchKernelGGL(gather_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, corpus, (long long)src_stride, d, perm,
-                           (long long)n, sorted, (long long)dst_stride, inv_norm, gid, id_base);
-    else
-        hipLaunchKernelGGL(gather_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, corpus, (long long)src_stride, d, perm,
-                           (long long)n, sorted, (long long)dst_stride, inv_norm, gid, id_base);
-    NLSH_CHECK_HIP(hipGetLastError());
-    return NLSH_OK;
-}
-
 extern "C" size_t nlsh_csr_update_workspace(int64_t n_old, int64_t n_buckets_old, int64_t m_new) {
     if (!update_args_ok(n_old, n_buckets_old, m_new)) {
         set_error("csr_update_workspace: n_old=%lld n_buckets_old=%lld m_new=%lld", (long long)n_old, (long long)n_buckets_old, (long long)m_new);
@@ -791,71 +790,148 @@ extern "C" size_t nlsh_csr_update_workspace(int64_t n_old, int64_t n_buckets_old
     return w.total;
 }
 
-// nlsh_csr_update and nlsh_csr_update_typed: `storage` = elements of corpus_sorted and sorted_out (strides in elements), `new_storage` =
-// elements of rows_new; float32 on both sides is the float32 row kernel, untouched.
-static int csr_update_impl(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
-                           const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
-                           const uint8_t *keep, int64_t n_kept,
-                           const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new, int64_t m_new,
-                           void *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
-                           int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad,
-                           void *workspace, size_t workspace_bytes, nlsh_stream_t stream,
-                           bool sq8 = false, const float *lo = nullptr, const float *step = nullptr, int32_t *clamped_rows = nullptr) {
-    // ---- host checks: nothing below them runs, and no pointer is read, unless all of them pass
-    NLSH_REQUIRE(store_ok(storage) && store_ok(new_storage), NLSH_E_INVALID, "csr_update: storage=%d / new_storage=%d is none of NLSH_STORE_F32 / F16 / U8",
-                 storage, new_storage);
-    // nlsh_csr_update_sq8: the uint8 layout (storage is NLSH_STORE_U8) with the quantiser the new rows are encoded and the norms decoded by
-    NLSH_REQUIRE(!sq8 || (lo && step), NLSH_E_INVALID, "csr_update: lo / step is null");
-    NLSH_REQUIRE(!sq8 || ((((uintptr_t)lo | (uintptr_t)step) & 15) == 0), NLSH_E_INVALID, "csr_update: lo and step must be 16-byte aligned");
-    const int per16 = store_per16(storage);
-    NLSH_REQUIRE(d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "csr_update: d=%d not in [1, NLSH_MAX_DIM = %d]", d, NLSH_MAX_DIM);
-    NLSH_REQUIRE(n_old >= 0 && n_old < (1ll << 31), NLSH_E_INVALID, "csr_update: n_old=%lld not in [0, 2^31)", (long long)n_old);
-    NLSH_REQUIRE(n_buckets_old >= 0 && n_buckets_old <= n_old, NLSH_E_INVALID, "csr_update: n_buckets_old=%lld not in [0, n_old=%lld]",
-                 (long long)n_buckets_old, (long long)n_old);
-    NLSH_REQUIRE(m_new >= 0 && m_new < (1ll << 31), NLSH_E_INVALID, "csr_update: m_new=%lld not in [0, 2^31)", (long long)m_new);
-    NLSH_REQUIRE(n_kept >= 0 && n_kept <= n_old, NLSH_E_INVALID, "csr_update: n_kept=%lld not in [0, n_old=%lld]", (long long)n_kept, (long long)n_old);
-    NLSH_REQUIRE(keep || n_kept == n_old, NLSH_E_INVALID, "csr_update: keep is null (every row kept) but n_kept=%lld != n_old=%lld",
-                 (long long)n_kept, (long long)n_old);
-    const long long n_out = (long long)n_kept + (long long)m_new;
-    NLSH_REQUIRE(n_out <= 0x7FFFFFFFll, NLSH_E_INVALID, "csr_update: n_kept + m_new = %lld rows > 2^31 - 1 (int32 row positions)", n_out);
-    NLSH_REQUIRE(offsets_out && n_buckets_out, NLSH_E_INVALID, "csr_update: offsets_out / n_buckets_out is null");
-    if (n_old) {
-        NLSH_REQUIRE(row_stride >= d && row_stride % per16 == 0, NLSH_E_INVALID, "csr_update: row_stride=%lld must be >= d=%d and a multiple of %d",
-                     (long long)row_stride, d, per16);
-        NLSH_REQUIRE(corpus_sorted && gid && uniq_keys && offsets, NLSH_E_INVALID, "csr_update: corpus_sorted / gid / uniq_keys / offsets is null with n_old=%lld",
-                     (long long)n_old);
-        NLSH_REQUIRE(((uintptr_t)corpus_sorted & 15) == 0, NLSH_E_INVALID, "csr_update: corpus_sorted must be 16-byte aligned");
-        NLSH_REQUIRE(n_buckets_old >= 1, NLSH_E_INVALID, "csr_update: n_buckets_old=0 with n_old=%lld rows", (long long)n_old);
+// ---- the row calls: nlsh_gather_rows / _typed / _sq8 and nlsh_csr_update / _typed / _sq8 are fill, check, run on one description ---------
+// Start from `RowCall c = {}`.
+struct RowCall {
+    int d;
+    // the rows that arrive: the corpus of a gather (n_src = n, picked by perm), the new rows of an update (n_src = m_new)
+    const void *src; int src_storage; long long src_stride, n_src;
+    // the rows that are written: `sorted` of a gather, `sorted_out` of an update (n_kept + m_new rows), with inv_norm and gid beside them
+    void *dst; int dst_storage; long long dst_stride;
+    float *inv_norm; int32_t *gid;
+    // how they are held: the stateless codec of dst_storage, or (sq8; dst_storage is NLSH_STORE_U8 then) the codec of this quantiser
+    bool sq8; const float *lo, *step;
+    int32_t *first_bad, *clamped_rows;      // the optional flags of a conversion
+    hipStream_t stream;
+    // a gather only
+    const int32_t *perm; int32_t id_base;
+    // an update only: the index that is read, the new rows' keys and ids, the tables of the result, the workspace
+    const void *old_rows; long long old_stride, n_old, nb_old, n_kept;
+    const int32_t *gid_old; const float *inv_old; const int32_t *uniq_old, *offs_old; const uint8_t *keep;
+    const int32_t *keys_new, *ids_new;
+    int32_t *src_out, *uniq_out, *offsets_out, *n_buckets_out; void *workspace; size_t workspace_bytes;
+};
+
+// what an entry needs of the check
+enum : unsigned {
+    ROW_UPDATE = 1u,                // an update: the counts, the old index, the tables of the result and the workspace are held too
+    ROW_SRC_ELEMENT_ALIGNED = 2u,   // the arriving rows are read with element loads: their pointer is held to its element size
+};
+
+// The one argument check of the six entries.  Nothing behind it runs, and no pointer is read, unless all of it passes.
+static int row_call_check(const char *who, const RowCall &c, unsigned needs) {
+    const bool upd = (needs & ROW_UPDATE) != 0;
+    // the arguments under the names the entry's header gives them
+    const char *src_storage = upd ? "new_storage" : "src_storage", *dst_storage = upd ? "storage" : "dst_storage";
+    const char *src_rows = upd ? "rows_new / keys_new / ids_new" : "corpus / perm", *dst_rows = upd ? "sorted_out" : "sorted";
+    const char *src_stride = upd ? "new_stride" : "src_stride", *dst_stride = upd ? "stride_out" : "dst_stride";
+    const int d = c.d;
+    NLSH_REQUIRE(store_ok(c.src_storage) && store_ok(c.dst_storage), NLSH_E_INVALID, "%s: %s=%d / %s=%d is none of NLSH_STORE_F32 / F16 / U8", who,
+                 src_storage, c.src_storage, dst_storage, c.dst_storage);
+    const int per16 = store_per16(c.dst_storage);
+    // the quantiser: an update holds it whatever the counts, a gather of no rows looks at no pointer
+    const bool quant = c.sq8 && (upd || c.n_src);
+    NLSH_REQUIRE(!quant || (c.lo && c.step), NLSH_E_INVALID, "%s: lo / step is null", who);
+    NLSH_REQUIRE(!quant || ((((uintptr_t)c.lo | (uintptr_t)c.step) & 15) == 0), NLSH_E_INVALID, "%s: lo and step must be 16-byte aligned", who);
+    NLSH_REQUIRE(d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "%s: d=%d not in [1, NLSH_MAX_DIM = %d]", who, d, NLSH_MAX_DIM);
+    long long n_dst = c.n_src;
+    if (!upd) {
+        NLSH_REQUIRE(c.n_src >= 0, NLSH_E_INVALID, "%s: n=%lld", who, c.n_src);
+    } else {
+        NLSH_REQUIRE(c.n_old >= 0 && c.n_old < (1ll << 31), NLSH_E_INVALID, "%s: n_old=%lld not in [0, 2^31)", who, c.n_old);
+        NLSH_REQUIRE(c.nb_old >= 0 && c.nb_old <= c.n_old, NLSH_E_INVALID, "%s: n_buckets_old=%lld not in [0, n_old=%lld]", who, c.nb_old, c.n_old);
+        NLSH_REQUIRE(c.n_src >= 0 && c.n_src < (1ll << 31), NLSH_E_INVALID, "%s: m_new=%lld not in [0, 2^31)", who, c.n_src);
+        NLSH_REQUIRE(c.n_kept >= 0 && c.n_kept <= c.n_old, NLSH_E_INVALID, "%s: n_kept=%lld not in [0, n_old=%lld]", who, c.n_kept, c.n_old);
+        NLSH_REQUIRE(c.keep || c.n_kept == c.n_old, NLSH_E_INVALID, "%s: keep is null (every row kept) but n_kept=%lld != n_old=%lld", who, c.n_kept, c.n_old);
+        n_dst = c.n_kept + c.n_src;
+        NLSH_REQUIRE(n_dst <= 0x7FFFFFFFll, NLSH_E_INVALID, "%s: n_kept + m_new = %lld rows > 2^31 - 1 (int32 row positions)", who, n_dst);
+        NLSH_REQUIRE(c.offsets_out && c.n_buckets_out, NLSH_E_INVALID, "%s: offsets_out / n_buckets_out is null", who);
+        if (c.n_old) {
+            NLSH_REQUIRE(c.old_stride >= d && c.old_stride % per16 == 0, NLSH_E_INVALID, "%s: row_stride=%lld must be >= d=%d and a multiple of %d", who,
+                         c.old_stride, d, per16);
+            NLSH_REQUIRE(c.old_rows && c.gid_old && c.uniq_old && c.offs_old, NLSH_E_INVALID, "%s: corpus_sorted / gid / uniq_keys / offsets is null with n_old=%lld",
+                         who, c.n_old);
+            NLSH_REQUIRE(((uintptr_t)c.old_rows & 15) == 0, NLSH_E_INVALID, "%s: corpus_sorted must be 16-byte aligned", who);
+            NLSH_REQUIRE(c.nb_old >= 1, NLSH_E_INVALID, "%s: n_buckets_old=0 with n_old=%lld rows", who, c.n_old);
+        }
     }
-    if (m_new) {
-        NLSH_REQUIRE(new_stride >= d, NLSH_E_INVALID, "csr_update: new_stride=%lld < d=%d", (long long)new_stride, d);
-        NLSH_REQUIRE(rows_new && keys_new && ids_new, NLSH_E_INVALID, "csr_update: rows_new / keys_new / ids_new is null with m_new=%lld", (long long)m_new);
-        NLSH_REQUIRE(first_bad || new_storage == storage, NLSH_E_INVALID, "csr_update: first_bad is null but the new rows (new_storage=%d) are converted to storage=%d",
-                     new_storage, storage);
+    // a conversion must be able to report (a gather says so even for no rows)
+    NLSH_REQUIRE(c.first_bad || c.src_storage == c.dst_storage || (upd && c.n_src == 0), NLSH_E_INVALID,
+                 "%s: first_bad is null but the rows are converted (%s=%d, %s=%d)", who, src_storage, c.src_storage, dst_storage, c.dst_storage);
+    if (c.n_src) {
+        NLSH_REQUIRE(c.src && (upd ? c.keys_new && c.ids_new : c.perm != nullptr), NLSH_E_INVALID, "%s: %s is null", who, src_rows);
+        NLSH_REQUIRE(c.src_stride >= d, NLSH_E_INVALID, "%s: %s=%lld < d=%d", who, src_stride, c.src_stride, d);
+        NLSH_REQUIRE(!(needs & ROW_SRC_ELEMENT_ALIGNED) || ((uintptr_t)c.src & (c.src_storage == NLSH_STORE_F32 ? 3 : c.src_storage == NLSH_STORE_F16 ? 1 : 0)) == 0,
+                     NLSH_E_INVALID, "%s: %s is not aligned to its element size", who, upd ? "rows_new" : "corpus");
     }
-    UpdateWs w;
-    update_layout(n_old, n_buckets_old, m_new, &w);
-    if (n_out) {
-        NLSH_REQUIRE(stride_out >= d && stride_out % per16 == 0, NLSH_E_INVALID, "csr_update: stride_out=%lld must be >= d=%d and a multiple of %d",
-                     (long long)stride_out, d, per16);
-        NLSH_REQUIRE(sorted_out && gid_out && src_out && uniq_out, NLSH_E_INVALID, "csr_update: sorted_out / gid_out / src_out / uniq_out is null");
-        NLSH_REQUIRE(((uintptr_t)sorted_out & 15) == 0, NLSH_E_INVALID, "csr_update: sorted_out must be 16-byte aligned");
-        NLSH_REQUIRE(!inv_norm_out || inv_norm || n_kept == 0, NLSH_E_INVALID, "csr_update: inv_norm_out is wanted but inv_norm (the kept rows') is null");
-        NLSH_REQUIRE(workspace, NLSH_E_INVALID, "csr_update: workspace is null");
-        NLSH_REQUIRE(((uintptr_t)workspace & 15) == 0, NLSH_E_INVALID, "csr_update: the workspace must be 16-byte aligned");
-        NLSH_REQUIRE(workspace_bytes >= w.total, NLSH_E_INVALID, "csr_update: workspace_bytes=%zu < nlsh_csr_update_workspace = %zu", workspace_bytes, w.total);
+    if (n_dst) {
+        NLSH_REQUIRE(c.dst && (!upd || (c.gid && c.src_out && c.uniq_out)), NLSH_E_INVALID, "%s: %s is null", who, upd ? "sorted_out / gid_out / src_out / uniq_out" : dst_rows);
+        NLSH_REQUIRE(c.dst_stride >= d && c.dst_stride % per16 == 0, NLSH_E_INVALID, "%s: %s=%lld must be >= d=%d and a multiple of %d elements (a pitch of 16-byte units)",
+                     who, dst_stride, c.dst_stride, d, per16);
+        NLSH_REQUIRE(((uintptr_t)c.dst & 15) == 0, NLSH_E_INVALID, "%s: %s must be 16-byte aligned", who, dst_rows);
     }
-    // ---- device work
-    hipStream_t s = (hipStream_t)stream;
-    if (first_bad) NLSH_CHECK_HIP(hipMemsetAsync(first_bad, 0xFF, sizeof(int32_t), s));   // -1: every new row survived its conversion
-    if (clamped_rows) NLSH_CHECK_HIP(hipMemsetAsync(clamped_rows, 0, sizeof(int32_t), s));
+    if (upd && n_dst) {
+        NLSH_REQUIRE(!c.inv_norm || c.inv_old || c.n_kept == 0, NLSH_E_INVALID, "%s: inv_norm_out is wanted but inv_norm (the kept rows') is null", who);
+        NLSH_REQUIRE(c.workspace, NLSH_E_INVALID, "%s: workspace is null", who);
+        NLSH_REQUIRE(((uintptr_t)c.workspace & 15) == 0, NLSH_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
+        UpdateWs w;
+        update_layout(c.n_old, c.nb_old, c.n_src, &w);
+        NLSH_REQUIRE(c.workspace_bytes >= w.total, NLSH_E_INVALID, "%s: workspace_bytes=%zu < nlsh_csr_update_workspace = %zu", who, c.workspace_bytes, w.total);
+    }
+    return NLSH_OK;
+}
+
+struct RowKernels { const void *gather, *update, *inv_norm; };
+static RowKernels row_kernels(const RowCall &c);      // defined behind the two calls: the float32 kernels keep their place in the code object
+
+// -1: every row survived its conversion; 0 saturated rows
+static int row_flags_clear(const RowCall &c) {
+    if (c.first_bad) NLSH_CHECK_HIP(hipMemsetAsync(c.first_bad, 0xFF, sizeof(int32_t), c.stream));
+    if (c.clamped_rows) NLSH_CHECK_HIP(hipMemsetAsync(c.clamped_rows, 0, sizeof(int32_t), c.stream));
+    return NLSH_OK;
+}
+
+static int gather_call(const char *who, RowCall c, unsigned needs) {
+    int rc = row_call_check(who, c, needs);
+    if (rc != NLSH_OK || (rc = row_flags_clear(c)) != NLSH_OK || c.n_src == 0) return rc;
+    hipStream_t s = c.stream;
+    long long blocks = (c.n_src + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    int vec = store_vec_ok(c.src, c.src_storage, c.src_stride);      // rows on chunk boundaries of their storage: one load per chunk
+    const RowKernels k = row_kernels(c);
+    if (!k.gather) {
+        const float *corpus = (const float *)c.src;
+        float *sorted = (float *)c.dst;
+        if (vec)
+            hipLaunchKernelGGL(gather_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, corpus, c.src_stride, c.d, c.perm, c.n_src, sorted,
+                               c.dst_stride, c.inv_norm, c.gid, c.id_base);
+        else
+            hipLaunchKernelGGL(gather_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, corpus, c.src_stride, c.d, c.perm, c.n_src, sorted,
+                               c.dst_stride, c.inv_norm, c.gid, c.id_base);
+    } else {
+        Sq8Codec codec = {(const float4 *)c.lo, (const float4 *)c.step};     // a stateless codec is an empty argument: nothing of this is read
+        void *argv[] = {&c.src, &c.src_stride, &c.d, &c.perm, &c.n_src, &c.dst, &c.dst_stride, &c.inv_norm, &c.gid, &c.id_base, &c.first_bad, &vec,
+                        &c.clamped_rows, &codec};
+        NLSH_CHECK_HIP(hipLaunchKernel(k.gather, dim3((unsigned)blocks), dim3(256), argv, 0, s));
+    }
+    NLSH_CHECK_HIP(hipGetLastError());
+    return NLSH_OK;
+}
+
+static int update_call(const char *who, RowCall c) {
+    int rc = row_call_check(who, c, ROW_UPDATE);
+    if (rc != NLSH_OK || (rc = row_flags_clear(c)) != NLSH_OK) return rc;
+    hipStream_t s = c.stream;
+    long long n_old = c.n_old, m_new = c.n_src, n_out = c.n_kept + c.n_src;
     if (n_out == 0) {
-        NLSH_CHECK_HIP(hipMemsetAsync(offsets_out, 0, sizeof(int32_t), s));
-        NLSH_CHECK_HIP(hipMemsetAsync(n_buckets_out, 0, sizeof(int32_t), s));
+        NLSH_CHECK_HIP(hipMemsetAsync(c.offsets_out, 0, sizeof(int32_t), s));
+        NLSH_CHECK_HIP(hipMemsetAsync(c.n_buckets_out, 0, sizeof(int32_t), s));
         return NLSH_OK;
     }
-    char *base = (char *)workspace;
-    int32_t *kex = keep ? (int32_t *)(base + w.kex) : nullptr, *shift_old = (int32_t *)(base + w.shift_old);
+    UpdateWs w;
+    update_layout(n_old, c.nb_old, m_new, &w);
+    char *base = (char *)c.workspace;
+    int32_t *kex = c.keep ? (int32_t *)(base + w.kex) : nullptr, *shift_old = (int32_t *)(base + w.shift_old);
     int32_t *key_out = (int32_t *)(base + w.key_out), *flags = (int32_t *)(base + w.flags), *rank = (int32_t *)(base + w.rank);
     int32_t *perm_n = (int32_t *)(base + w.perm_n), *uniq_n = (int32_t *)(base + w.uniq_n), *offs_n = (int32_t *)(base + w.offs_n);
     int32_t *nb_n = (int32_t *)(base + w.nb_n), *shift_new = (int32_t *)(base + w.shift_new);
@@ -865,92 +941,117 @@ static int csr_update_impl(const void *corpus_sorted, int storage, int64_t row_s
     size_t t_sort = 0, t_scan = 0;      // what rocPRIM really asks for on this device, against the bound the workspace was sized by
     if (m_new) NLSH_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, t_sort, nul, nul, nul, nul, (size_t)m_new, 0, 32, s));
     NLSH_CHECK_HIP(rocprim::inclusive_scan(nullptr, t_scan, nul, nul, n_scan, rocprim::plus<int32_t>(), s));
-    NLSH_REQUIRE(t_sort <= w.tmp_bytes && t_scan <= w.tmp_bytes, NLSH_E_WORKSPACE, "csr_update: rocPRIM scratch (sort %zu, scan %zu bytes) exceeds the %zu bytes "
-                 "the workspace formula reserves for it", t_sort, t_scan, w.tmp_bytes);
+    NLSH_REQUIRE(t_sort <= w.tmp_bytes && t_scan <= w.tmp_bytes, NLSH_E_WORKSPACE, "%s: rocPRIM scratch (sort %zu, scan %zu bytes) exceeds the %zu bytes "
+                 "the workspace formula reserves for it", who, t_sort, t_scan, w.tmp_bytes);
     auto grid_of = [](long long n) { long long g = (n + 255) / 256; return dim3((unsigned)(g < 1 ? 1 : g > 2048 ? 2048 : g)); };
     if (m_new) {
-        int rc = build_csr_on(keys_new, (long long)m_new, perm_n, uniq_n, offs_n, nb_n, (int32_t *)(base + w.sk), (int32_t *)(base + w.iota),
-                              (int32_t *)(base + w.flags_n), (int32_t *)(base + w.rank_n), tmp, w.tmp_bytes, s);
+        rc = build_csr_on(c.keys_new, m_new, perm_n, uniq_n, offs_n, nb_n, (int32_t *)(base + w.sk), (int32_t *)(base + w.iota),
+                          (int32_t *)(base + w.flags_n), (int32_t *)(base + w.rank_n), tmp, w.tmp_bytes, s);
         if (rc != NLSH_OK) return rc;
     }
-    if (keep) {         // kex[0] = 0, kex[i + 1] = keep[0] + ... + keep[i]
-        hipLaunchKernelGGL(keep_flags_kernel, grid_of(n_old), dim3(256), 0, s, keep, (long long)n_old, flags);
+    if (c.keep) {         // kex[0] = 0, kex[i + 1] = keep[0] + ... + keep[i]
+        hipLaunchKernelGGL(keep_flags_kernel, grid_of(n_old), dim3(256), 0, s, c.keep, n_old, flags);
         NLSH_CHECK_HIP(hipMemsetAsync(kex, 0, sizeof(int32_t), s));
         size_t tb = w.tmp_bytes;
         NLSH_CHECK_HIP(rocprim::inclusive_scan(tmp, tb, flags, kex + 1, (size_t)n_old, rocprim::plus<int32_t>(), s));
     }
-    hipLaunchKernelGGL(update_shifts_kernel, grid_of(n_buckets_old + m_new), dim3(256), 0, s, uniq_keys, offsets, (int)n_buckets_old, (int)n_old, kex,
+    hipLaunchKernelGGL(update_shifts_kernel, grid_of(c.nb_old + m_new), dim3(256), 0, s, c.uniq_old, c.offs_old, (int)c.nb_old, (int)n_old, kex,
                        uniq_n, offs_n, nb_n, (int)m_new, shift_old, shift_new);
-    hipLaunchKernelGGL(update_index_kernel, grid_of(n_old + m_new), dim3(256), 0, s, gid, uniq_keys, offsets, (int)n_buckets_old, (int)n_old, keep, kex,
-                       shift_old, perm_n, uniq_n, offs_n, nb_n, ids_new, shift_new, (int)m_new, n_out, src_out, gid_out, key_out);
+    hipLaunchKernelGGL(update_index_kernel, grid_of(n_old + m_new), dim3(256), 0, s, c.gid_old, c.uniq_old, c.offs_old, (int)c.nb_old, (int)n_old, c.keep, kex,
+                       shift_old, perm_n, uniq_n, offs_n, nb_n, c.ids_new, shift_new, (int)m_new, n_out, c.src_out, c.gid, key_out);
     // the bucket table of the result: the run-length encoding of the keys at their destinations (emptied buckets vanish, new ones appear)
     hipLaunchKernelGGL(head_flags_kernel, grid_of(n_out), dim3(256), 0, s, key_out, n_out, flags);
     size_t tb = w.tmp_bytes;
     NLSH_CHECK_HIP(rocprim::inclusive_scan(tmp, tb, flags, rank, (size_t)n_out, rocprim::plus<int32_t>(), s));
-    hipLaunchKernelGGL(emit_buckets_kernel, grid_of(n_out), dim3(256), 0, s, key_out, flags, rank, n_out, uniq_out, offsets_out, n_buckets_out);
-    // the rows
-    const int d4 = (int)(stride_out >> 2);
+    hipLaunchKernelGGL(emit_buckets_kernel, grid_of(n_out), dim3(256), 0, s, key_out, flags, rank, n_out, c.uniq_out, c.offsets_out, c.n_buckets_out);
+    // the rows: 2^lg lanes per row of `units` 16-byte units (float32 rows into a float32 index: of float4s), ROWS_IN_FLIGHT rows per lane group
+    const RowKernels k = row_kernels(c);
+    const int per16 = store_per16(c.dst_storage);
+    long long units_old = c.old_stride / per16, units_out = k.update ? c.dst_stride / per16 : c.dst_stride >> 2;
     int lg = 0;
-    while ((1 << lg) < d4 && lg < 6) ++lg;
+    while ((1 << lg) < units_out && lg < 6) ++lg;
     const long long rows_per_wave = (long long)(64 >> lg) * ROWS_IN_FLIGHT;
     long long blocks = ((n_out + rows_per_wave - 1) / rows_per_wave + 3) / 4;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    if (storage == NLSH_STORE_F32 && new_storage == NLSH_STORE_F32) {
-        const float *old_f = (const float *)corpus_sorted, *new_f = (const float *)rows_new;
-        float *out_f = (float *)sorted_out;
-        const bool vec = ((new_stride & 3) == 0) && (((uintptr_t)rows_new & 15) == 0);
+    int vec = store_vec_ok(c.src, c.src_storage, c.src_stride);      // new rows on chunk boundaries of their storage: one load per chunk
+    if (!k.update) {      // one pass, inv_norm fused
+        const float *old_f = (const float *)c.old_rows, *new_f = (const float *)c.src;
+        float *out_f = (float *)c.dst;
         if (vec)
-            hipLaunchKernelGGL(update_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, old_f, (long long)row_stride, inv_norm, (long long)n_old,
-                               new_f, (long long)new_stride, (long long)m_new, d, src_out, n_out, out_f, (long long)stride_out, inv_norm_out, lg);
+            hipLaunchKernelGGL(update_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, old_f, c.old_stride, c.inv_old, n_old, new_f, c.src_stride,
+                               m_new, c.d, c.src_out, n_out, out_f, c.dst_stride, c.inv_norm, lg);
         else
-            hipLaunchKernelGGL(update_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, old_f, (long long)row_stride, inv_norm, (long long)n_old,
-                               new_f, (long long)new_stride, (long long)m_new, d, src_out, n_out, out_f, (long long)stride_out, inv_norm_out, lg);
-    } else {
-        // typed storage: the row pass in 16-byte units, then the inv_norm pass over what it wrote
-        const long long units_old = row_stride / per16, units_out = stride_out / per16;
-        int lgu = 0;
-        while ((1 << lgu) < units_out && lgu < 6) ++lgu;
-        const long long rows_per_wave_u = (long long)(64 >> lgu) * ROWS_IN_FLIGHT;
-        long long ublocks = ((n_out + rows_per_wave_u - 1) / rows_per_wave_u + 3) / 4;
-        if (ublocks > 256 * 8) ublocks = 256 * 8;
-        const void *fn = nullptr;
-#define NLSH_UPD(N, D) if (new_storage == N && storage == D) fn = (const void *)update_rows_typed_kernel<N, D>;
-        NLSH_UPD(NLSH_STORE_F16, NLSH_STORE_F32) NLSH_UPD(NLSH_STORE_U8, NLSH_STORE_F32)
-        NLSH_UPD(NLSH_STORE_F32, NLSH_STORE_F16) NLSH_UPD(NLSH_STORE_F16, NLSH_STORE_F16) NLSH_UPD(NLSH_STORE_U8, NLSH_STORE_F16)
-        NLSH_UPD(NLSH_STORE_F32, NLSH_STORE_U8) NLSH_UPD(NLSH_STORE_F16, NLSH_STORE_U8) NLSH_UPD(NLSH_STORE_U8, NLSH_STORE_U8)
-#undef NLSH_UPD
-        long long uo = units_old, nold = n_old, sn = new_stride, mn = m_new, no = n_out, ut = units_out, sto = stride_out;
-        int vecn = store_vec_ok(rows_new, new_storage, new_stride);      // new rows on chunk boundaries of their storage: one load per chunk
-        void *argv[] = {&corpus_sorted, &uo, &nold, &rows_new, &sn, &mn, &d, &src_out, &no, &sorted_out, &ut, &lgu, &first_bad, &vecn};
-        if (sq8) {      // the same two passes with the quantiser: new rows encoded (uint8 ones are codes), norms over decoded values
-            const void *fs = new_storage == NLSH_STORE_F32 ? (const void *)update_rows_sq8_kernel<NLSH_STORE_F32>
-                           : new_storage == NLSH_STORE_F16 ? (const void *)update_rows_sq8_kernel<NLSH_STORE_F16>
-                                                           : (const void *)update_rows_sq8_kernel<NLSH_STORE_U8>;
-            void *args[] = {&corpus_sorted, &uo, &nold, &rows_new, &sn, &mn, &d, &src_out, &no, &sorted_out, &ut, &lgu, &lo, &step, &first_bad,
-                            &clamped_rows, &vecn};
-            NLSH_CHECK_HIP(hipLaunchKernel(fs, dim3((unsigned)ublocks), dim3(256), args, 0, s));
-            if (inv_norm_out) {
-                long long iblocks = ((n_out + 63) / 64 + 3) / 4;
-                if (iblocks > 256 * 8) iblocks = 256 * 8;
-                void *argi[] = {&sorted_out, &sto, &lo, &step, &inv_norm, &nold, &src_out, &no, &inv_norm_out};
-                NLSH_CHECK_HIP(hipLaunchKernel((const void *)update_inv_norm_sq8_kernel, dim3((unsigned)iblocks), dim3(256), argi, 0, s));
-            }
-            NLSH_CHECK_HIP(hipGetLastError());
-            return NLSH_OK;
-        }
-        NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)ublocks), dim3(256), argv, 0, s));
-        if (inv_norm_out) {
-            const void *fi = storage == NLSH_STORE_F32 ? (const void *)update_inv_norm_typed_kernel<NLSH_STORE_F32>
-                           : storage == NLSH_STORE_F16 ? (const void *)update_inv_norm_typed_kernel<NLSH_STORE_F16>
-                                                       : (const void *)update_inv_norm_typed_kernel<NLSH_STORE_U8>;
+            hipLaunchKernelGGL(update_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, old_f, c.old_stride, c.inv_old, n_old, new_f, c.src_stride,
+                               m_new, c.d, c.src_out, n_out, out_f, c.dst_stride, c.inv_norm, lg);
+    } else {              // the row pass in 16-byte units, then the inv_norm pass over what it wrote
+        Sq8Codec codec = {(const float4 *)c.lo, (const float4 *)c.step};     // a stateless codec is an empty argument: nothing of this is read
+        void *argv[] = {&c.old_rows, &units_old, &n_old, &c.src, &c.src_stride, &m_new, &c.d, &c.src_out, &n_out, &c.dst, &units_out, &lg, &c.first_bad, &vec,
+                        &c.clamped_rows, &codec};
+        NLSH_CHECK_HIP(hipLaunchKernel(k.update, dim3((unsigned)blocks), dim3(256), argv, 0, s));
+        if (c.inv_norm) {
             long long iblocks = ((n_out + 63) / 64 + 3) / 4;
             if (iblocks > 256 * 8) iblocks = 256 * 8;
-            void *argi[] = {&sorted_out, &sto, &inv_norm, &nold, &src_out, &no, &inv_norm_out};
-            NLSH_CHECK_HIP(hipLaunchKernel(fi, dim3((unsigned)iblocks), dim3(256), argi, 0, s));
+            void *argi[] = {&c.dst, &c.dst_stride, &c.inv_old, &n_old, &c.src_out, &n_out, &c.inv_norm, &codec};
+            NLSH_CHECK_HIP(hipLaunchKernel(k.inv_norm, dim3((unsigned)iblocks), dim3(256), argi, 0, s));
         }
     }
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
+}
+
+// The one place a (source storage, destination codec) pair becomes kernels.  Float32 rows into a float32 index have none here: they
+// are gather_rows_kernel's and update_rows_kernel's.
+template <int SRC, class Codec> static RowKernels row_kernels_of() {
+    return {(const void *)gather_rows_to_kernel<SRC, Codec>, (const void *)update_rows_to_kernel<SRC, Codec>, (const void *)update_inv_norm_of_kernel<Codec>};
+}
+template <> RowKernels row_kernels_of<NLSH_STORE_F32, StoreCodec<NLSH_STORE_F32>>() { return {nullptr, nullptr, nullptr}; }
+template <class Codec> static RowKernels row_kernels_to(int src_storage) {
+    return src_storage == NLSH_STORE_F32 ? row_kernels_of<NLSH_STORE_F32, Codec>()
+         : src_storage == NLSH_STORE_F16 ? row_kernels_of<NLSH_STORE_F16, Codec>() : row_kernels_of<NLSH_STORE_U8, Codec>();
+}
+static RowKernels row_kernels(const RowCall &c) {
+    if (c.sq8) return row_kernels_to<Sq8Codec>(c.src_storage);
+    return c.dst_storage == NLSH_STORE_F32 ? row_kernels_to<StoreCodec<NLSH_STORE_F32>>(c.src_storage)
+         : c.dst_storage == NLSH_STORE_F16 ? row_kernels_to<StoreCodec<NLSH_STORE_F16>>(c.src_storage) : row_kernels_to<StoreCodec<NLSH_STORE_U8>>(c.src_storage);
+}
+
+// The descriptor of a gather / of an update with what their three entries all have, under the header's parameter names.
+#define NLSH_GATHER_CALL(c)                                                                                                          \
+    RowCall c = {};                                                                                                                  \
+    c.d = d; c.src = corpus; c.src_stride = src_stride; c.n_src = n; c.perm = perm; c.dst = sorted; c.dst_stride = dst_stride;      \
+    c.inv_norm = inv_norm; c.gid = gid; c.id_base = id_base; c.stream = (hipStream_t)stream
+#define NLSH_UPDATE_CALL(c)                                                                                                          \
+    RowCall c = {};                                                                                                                  \
+    c.d = d; c.src = rows_new; c.src_stride = new_stride; c.n_src = m_new; c.keys_new = keys_new; c.ids_new = ids_new;              \
+    c.old_rows = corpus_sorted; c.old_stride = row_stride; c.n_old = n_old; c.nb_old = n_buckets_old; c.n_kept = n_kept; c.keep = keep; \
+    c.gid_old = gid; c.inv_old = inv_norm; c.uniq_old = uniq_keys; c.offs_old = offsets;                                             \
+    c.dst = sorted_out; c.dst_stride = stride_out; c.gid = gid_out; c.inv_norm = inv_norm_out; c.src_out = src_out; c.uniq_out = uniq_out; \
+    c.offsets_out = offsets_out; c.n_buckets_out = n_buckets_out; c.workspace = workspace; c.workspace_bytes = workspace_bytes;     \
+    c.stream = (hipStream_t)stream
+
+extern "C" int nlsh_gather_rows(const float *corpus, int64_t src_stride, int d, const int32_t *perm, int64_t n,
+                                float *sorted, int64_t dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
+                                nlsh_stream_t stream) {
+    NLSH_GATHER_CALL(c);
+    c.src_storage = c.dst_storage = NLSH_STORE_F32;
+    return gather_call("gather_rows", c, 0);      // any alignment of `corpus`, as ever
+}
+
+extern "C" int nlsh_gather_rows_typed(const void *corpus, int src_storage, int64_t src_stride, int d, const int32_t *perm, int64_t n,
+                                      void *sorted, int dst_storage, int64_t dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
+                                      int32_t *first_bad, nlsh_stream_t stream) {
+    NLSH_GATHER_CALL(c);
+    c.src_storage = src_storage; c.dst_storage = dst_storage; c.first_bad = first_bad;
+    return gather_call("gather_rows_typed", c, ROW_SRC_ELEMENT_ALIGNED);
+}
+
+extern "C" int nlsh_gather_rows_sq8(const void *corpus, int src_storage, int64_t src_stride, int d, const int32_t *perm, int64_t n,
+                                    uint8_t *sorted, int64_t dst_stride, const float *lo, const float *step, float *inv_norm, int32_t *gid,
+                                    int32_t id_base, int32_t *first_bad, int32_t *clamped_rows, nlsh_stream_t stream) {
+    NLSH_GATHER_CALL(c);
+    c.src_storage = src_storage; c.dst_storage = NLSH_STORE_U8; c.first_bad = first_bad;
+    c.sq8 = true; c.lo = lo; c.step = step; c.clamped_rows = clamped_rows;
+    return gather_call("gather_rows_sq8", c, ROW_SRC_ELEMENT_ALIGNED);
 }
 
 extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
@@ -960,11 +1061,12 @@ extern "C" int nlsh_csr_update(const float *corpus_sorted, int64_t row_stride, i
                                float *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
                                int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out,
                                void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
-    return csr_update_impl(corpus_sorted, NLSH_STORE_F32, row_stride, d, gid, inv_norm, uniq_keys, offsets, n_old, n_buckets_old, keep, n_kept,
-                           rows_new, NLSH_STORE_F32, new_stride, keys_new, ids_new, m_new, sorted_out, stride_out, gid_out, inv_norm_out, src_out,
-                           uniq_out, offsets_out, n_buckets_out, nullptr, workspace, workspace_bytes, stream);
+    NLSH_UPDATE_CALL(c);
+    c.src_storage = c.dst_storage = NLSH_STORE_F32;
+    return update_call("csr_update", c);
 }
 
+// `storage` = elements of corpus_sorted and sorted_out (strides in elements), `new_storage` = elements of rows_new
 extern "C" int nlsh_csr_update_typed(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid, const float *inv_norm,
                                      const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
                                      const uint8_t *keep, int64_t n_kept,
@@ -973,52 +1075,29 @@ extern "C" int nlsh_csr_update_typed(const void *corpus_sorted, int storage, int
                                      void *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
                                      int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad,
                                      void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
-    return csr_update_impl(corpus_sorted, storage, row_stride, d, gid, inv_norm, uniq_keys, offsets, n_old, n_buckets_old, keep, n_kept,
-                           rows_new, new_storage, new_stride, keys_new, ids_new, m_new, sorted_out, stride_out, gid_out, inv_norm_out, src_out,
-                           uniq_out, offsets_out, n_buckets_out, first_bad, workspace, workspace_bytes, stream);
+    NLSH_UPDATE_CALL(c);
+    c.src_storage = new_storage; c.dst_storage = storage; c.first_bad = first_bad;
+    return update_call("csr_update", c);
 }
 
-extern "C" int nlsh_gather_rows_typed(const void *corpus, int src_storage, int64_t src_stride, int d, const int32_t *perm, int64_t n,
-                                      void *sorted, int dst_storage, int64_t dst_stride, float *inv_norm, int32_t *gid, int32_t id_base,
-                                      int32_t *first_bad, nlsh_stream_t stream) {
-    NLSH_REQUIRE(store_ok(src_storage) && store_ok(dst_storage), NLSH_E_INVALID,
-                 "gather_rows_typed: src_storage=%d / dst_storage=%d is none of NLSH_STORE_F32 / F16 / U8", src_storage, dst_storage);
-    NLSH_REQUIRE(n >= 0 && d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "gather_rows_typed: n=%lld d=%d", (long long)n, d);
-    NLSH_REQUIRE(first_bad || src_storage == dst_storage, NLSH_E_INVALID,
-                 "gather_rows_typed: first_bad is null but the rows are converted (src_storage=%d, dst_storage=%d)", src_storage, dst_storage);
-    if (n) {
-        NLSH_REQUIRE(corpus && perm && sorted, NLSH_E_INVALID, "gather_rows_typed: corpus / perm / sorted is null");
-        NLSH_REQUIRE(dst_stride >= d && dst_stride % store_per16(dst_storage) == 0, NLSH_E_INVALID,
-                     "gather_rows_typed: dst_stride=%lld must be >= d=%d and a multiple of %d elements (a pitch of 16-byte units) for dst_storage=%d",
-                     (long long)dst_stride, d, store_per16(dst_storage), dst_storage);
-        NLSH_REQUIRE(((uintptr_t)sorted & 15) == 0, NLSH_E_INVALID, "gather_rows_typed: sorted must be 16-byte aligned");
-        NLSH_REQUIRE(src_stride >= d, NLSH_E_INVALID, "gather_rows_typed: src_stride=%lld < d=%d", (long long)src_stride, d);
-        // an element pointer is read with element loads: it must be aligned to its element
-        NLSH_REQUIRE(((uintptr_t)corpus & (src_storage == NLSH_STORE_F32 ? 3 : src_storage == NLSH_STORE_F16 ? 1 : 0)) == 0, NLSH_E_INVALID,
-                     "gather_rows_typed: corpus is not aligned to its element size");
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (first_bad) NLSH_CHECK_HIP(hipMemsetAsync(first_bad, 0xFF, sizeof(int32_t), s));   // -1: every row survived its conversion
-    if (n == 0) return NLSH_OK;
-    if (src_storage == NLSH_STORE_F32 && dst_storage == NLSH_STORE_F32)
-        return nlsh_gather_rows((const float *)corpus, src_stride, d, perm, n, (float *)sorted, dst_stride, inv_norm, gid, id_base, stream);
-    long long blocks = (n + 3) / 4;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    const void *fn = nullptr;
-#define NLSH_GAT(S, D) if (src_storage == S && dst_storage == D) fn = (const void *)gather_rows_typed_kernel<S, D>;
-    NLSH_GAT(NLSH_STORE_F16, NLSH_STORE_F32) NLSH_GAT(NLSH_STORE_U8, NLSH_STORE_F32)
-    NLSH_GAT(NLSH_STORE_F32, NLSH_STORE_F16) NLSH_GAT(NLSH_STORE_F16, NLSH_STORE_F16) NLSH_GAT(NLSH_STORE_U8, NLSH_STORE_F16)
-    NLSH_GAT(NLSH_STORE_F32, NLSH_STORE_U8) NLSH_GAT(NLSH_STORE_F16, NLSH_STORE_U8) NLSH_GAT(NLSH_STORE_U8, NLSH_STORE_U8)
-#undef NLSH_GAT
-    long long ss = src_stride, nn = n, ds = dst_stride;
-    int vec = store_vec_ok(corpus, src_storage, src_stride);             // rows on chunk boundaries of their storage: one load per chunk
-    void *argv[] = {&corpus, &ss, &d, &perm, &nn, &sorted, &ds, &inv_norm, &gid, &id_base, &first_bad, &vec};
-    NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, 0, s));
-    NLSH_CHECK_HIP(hipGetLastError());
-    return NLSH_OK;
+extern "C" int nlsh_csr_update_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d, const int32_t *gid,
+                                   const float *inv_norm, const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
+                                   const uint8_t *keep, int64_t n_kept,
+                                   const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new,
+                                   int64_t m_new,
+                                   uint8_t *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
+                                   int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad, int32_t *clamped_rows,
+                                   void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
+    // one quantiser serves both sides: its arrays cover the wider of the two pitches only if the caller made them so
+    NLSH_REQUIRE(n_old == 0 || m_new == 0 || n_kept + m_new == 0 || row_stride == stride_out, NLSH_E_INVALID,
+                 "csr_update_sq8: row_stride=%lld != stride_out=%lld (lo and step are padded to ONE pitch)", (long long)row_stride, (long long)stride_out);
+    NLSH_UPDATE_CALL(c);
+    c.src_storage = new_storage; c.dst_storage = NLSH_STORE_U8; c.first_bad = first_bad;
+    c.sq8 = true; c.lo = lo; c.step = step; c.clamped_rows = clamped_rows;
+    return update_call("csr_update", c);
 }
 
-// ---- storage="sq8" (sq8_rows.h): entry points of their own beside the typed ones, which refuse every storage code past NLSH_STORE_U8
+// ---- storage="sq8" (sq8_rows.h): training the quantiser
 static bool sq8_source_ok(int storage) { return storage == NLSH_STORE_F32 || storage == NLSH_STORE_F16; }
 
 extern "C" size_t nlsh_sq8_train_workspace(int64_t n, int d) {
@@ -1057,54 +1136,4 @@ extern "C" int nlsh_sq8_train(const void *rows, int storage, int64_t row_stride,
     hipLaunchKernelGGL(sq8_train_final_kernel, dim3((unsigned)((quant_stride + 15) / 16)), dim3(256), 0, s, part, blocks, lgw, d, nn, lo, step, qs);
     NLSH_CHECK_HIP(hipGetLastError());
     return NLSH_OK;
-}
-
-extern "C" int nlsh_gather_rows_sq8(const void *corpus, int src_storage, int64_t src_stride, int d, const int32_t *perm, int64_t n,
-                                    uint8_t *sorted, int64_t dst_stride, const float *lo, const float *step, float *inv_norm, int32_t *gid,
-                                    int32_t id_base, int32_t *first_bad, int32_t *clamped_rows, nlsh_stream_t stream) {
-    NLSH_REQUIRE(store_ok(src_storage), NLSH_E_INVALID, "gather_rows_sq8: src_storage=%d is none of NLSH_STORE_F32 / F16 / U8", src_storage);
-    NLSH_REQUIRE(n >= 0 && d >= 1 && d <= NLSH_MAX_DIM, NLSH_E_INVALID, "gather_rows_sq8: n=%lld d=%d", (long long)n, d);
-    NLSH_REQUIRE(first_bad || src_storage == NLSH_STORE_U8, NLSH_E_INVALID, "gather_rows_sq8: first_bad is null but the rows are encoded (src_storage=%d)", src_storage);
-    if (n) {
-        NLSH_REQUIRE(corpus && perm && sorted, NLSH_E_INVALID, "gather_rows_sq8: corpus / perm / sorted is null");
-        NLSH_REQUIRE(lo && step, NLSH_E_INVALID, "gather_rows_sq8: lo / step is null");
-        NLSH_REQUIRE(dst_stride >= d && dst_stride % 16 == 0, NLSH_E_INVALID,
-                     "gather_rows_sq8: dst_stride=%lld must be >= d=%d and a multiple of 16 elements (a pitch of 16-byte units)", (long long)dst_stride, d);
-        NLSH_REQUIRE(((uintptr_t)sorted & 15) == 0, NLSH_E_INVALID, "gather_rows_sq8: sorted must be 16-byte aligned");
-        NLSH_REQUIRE((((uintptr_t)lo | (uintptr_t)step) & 15) == 0, NLSH_E_INVALID, "gather_rows_sq8: lo and step must be 16-byte aligned");
-        NLSH_REQUIRE(src_stride >= d, NLSH_E_INVALID, "gather_rows_sq8: src_stride=%lld < d=%d", (long long)src_stride, d);
-        NLSH_REQUIRE(((uintptr_t)corpus & (src_storage == NLSH_STORE_F32 ? 3 : src_storage == NLSH_STORE_F16 ? 1 : 0)) == 0, NLSH_E_INVALID,
-                     "gather_rows_sq8: corpus is not aligned to its element size");
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (first_bad) NLSH_CHECK_HIP(hipMemsetAsync(first_bad, 0xFF, sizeof(int32_t), s));   // -1: every row is finite
-    if (clamped_rows) NLSH_CHECK_HIP(hipMemsetAsync(clamped_rows, 0, sizeof(int32_t), s));
-    if (n == 0) return NLSH_OK;
-    long long blocks = (n + 3) / 4;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    const void *fn = src_storage == NLSH_STORE_F32 ? (const void *)gather_rows_sq8_kernel<NLSH_STORE_F32>
-                   : src_storage == NLSH_STORE_F16 ? (const void *)gather_rows_sq8_kernel<NLSH_STORE_F16>
-                                                   : (const void *)gather_rows_sq8_kernel<NLSH_STORE_U8>;
-    long long ss = src_stride, nn = n, ds = dst_stride;
-    int vec = store_vec_ok(corpus, src_storage, src_stride);
-    void *argv[] = {&corpus, &ss, &d, &perm, &nn, &sorted, &ds, &lo, &step, &inv_norm, &gid, &id_base, &first_bad, &clamped_rows, &vec};
-    NLSH_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, 0, s));
-    NLSH_CHECK_HIP(hipGetLastError());
-    return NLSH_OK;
-}
-
-extern "C" int nlsh_csr_update_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d, const int32_t *gid,
-                                   const float *inv_norm, const int32_t *uniq_keys, const int32_t *offsets, int64_t n_old, int64_t n_buckets_old,
-                                   const uint8_t *keep, int64_t n_kept,
-                                   const void *rows_new, int new_storage, int64_t new_stride, const int32_t *keys_new, const int32_t *ids_new,
-                                   int64_t m_new,
-                                   uint8_t *sorted_out, int64_t stride_out, int32_t *gid_out, float *inv_norm_out, int32_t *src_out,
-                                   int32_t *uniq_out, int32_t *offsets_out, int32_t *n_buckets_out, int32_t *first_bad, int32_t *clamped_rows,
-                                   void *workspace, size_t workspace_bytes, nlsh_stream_t stream) {
-    // one quantiser serves both sides: its arrays cover the wider of the two pitches only if the caller made them so
-    NLSH_REQUIRE(n_old == 0 || m_new == 0 || n_kept + m_new == 0 || row_stride == stride_out, NLSH_E_INVALID,
-                 "csr_update_sq8: row_stride=%lld != stride_out=%lld (lo and step are padded to ONE pitch)", (long long)row_stride, (long long)stride_out);
-    return csr_update_impl(corpus_sorted, NLSH_STORE_U8, row_stride, d, gid, inv_norm, uniq_keys, offsets, n_old, n_buckets_old, keep, n_kept,
-                           rows_new, new_storage, new_stride, keys_new, ids_new, m_new, sorted_out, stride_out, gid_out, inv_norm_out, src_out,
-                           uniq_out, offsets_out, n_buckets_out, first_bad, workspace, workspace_bytes, stream, true, lo, step, clamped_rows);
 }

@@ -1,5 +1,5 @@
-// sq8 corpus storage, the row side (included by build_csr.hip behind its row helpers, which these kernels are built from): training the
-// per-dimension quantiser, the encoding gather, and the row and inv_norm passes of nlsh_csr_update_sq8.
+// sq8 corpus storage, the row side (included by build_csr.hip behind its row helpers, which this is built from): the codec that
+// build_csr.hip's row kernels encode and decode an sq8 index by, and training the per-dimension quantiser.
 //
 // THE RULE (include/nlsh_hip.h states it; tests hold the kernels to it bit for bit).  A quantiser is lo[d], step[d], float32, step > 0.
 //   decode  deq(c, j) = float(c) * step[j] + lo[j]                       two roundings, never a fused multiply-add
@@ -24,131 +24,27 @@ __device__ __forceinline__ uint32_t sq8_code(float x, float lo, float st, bool l
     return live ? (uint32_t)fminf(fmaxf(r, 0.0f), 255.0f) : 0u;     // a NaN (refused above) comes out as 0
 }
 
-// chunk c of a source row as its four codes.  A uint8 source IS codes: copied.
-template <int SRC>
-__device__ __forceinline__ uint32_t sq8_encode_chunk(const void *row, int c, int d, bool vec, const float4 *lo4, const float4 *st4, bool &bad, bool &clamped) {
-    const float4 v = load_chunk_as_f32<SRC>(row, c, d, vec);        // columns >= d: zero
-    if (SRC == NLSH_STORE_U8) return pack_chunk<NLSH_STORE_U8>(v);
-    const float4 lo = lo4[c], st = st4[c];
-    return sq8_code(v.x, lo.x, st.x, c * 4 + 0 < d, bad, clamped) | (sq8_code(v.y, lo.y, st.y, c * 4 + 1 < d, bad, clamped) << 8) |
-           (sq8_code(v.z, lo.z, st.z, c * 4 + 2 < d, bad, clamped) << 16) | (sq8_code(v.w, lo.w, st.w, c * 4 + 3 < d, bad, clamped) << 24);
-}
-
-// gather_rows_typed_kernel with the encoding destination: one wavefront per destination row, chunk c of the row on lane c % 64.  The sum
-// of squares runs over the DECODED values in that lane assignment and chain, so inv_norm has the bits nlsh_gather_rows gives on deq(codes).
-template <int SRC>
-__global__ __launch_bounds__(256) void gather_rows_sq8_kernel(const void *corpus, long long src_stride, int d, const int32_t *perm, long long n,
-                                                               uint32_t *sorted, long long dst_stride, const float4 *lo4, const float4 *st4,
-                                                               float *inv_norm, int32_t *gid, int32_t id_base, int32_t *first_bad,
-                                                               int32_t *clamped_rows, int vec) {
-    typedef typename StoreElem<SRC>::elem src_t;
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
-    const int d4 = (int)(dst_stride >> 2);
-    for (long long i = wave; i < n; i += nwaves) {
-        const long long src = perm[i];
-        const src_t *s = static_cast<const src_t *>(corpus) + src * src_stride;
-        uint32_t *dst = sorted + i * (long long)d4;
-        float ss = 0.0f;
-        bool bad = false, clamped = false;
-        for (int c = lane; c < d4; c += 64) {
-            const uint32_t w = sq8_encode_chunk<SRC>(s, c, d, vec != 0, lo4, st4, bad, clamped);
-            dst[c] = w;
-            ss = sumsq_chain(sq8_decode4(w, lo4[c], st4[c]), ss);
-        }
-        if (inv_norm) {
-            ss = sumsq_lanes(ss, 64);
-            if (lane == 0) inv_norm[i] = inv_norm_of(ss);
-        }
-        if (gid && lane == 0) gid[i] = (int32_t)src + id_base;
-        report_bad_row(first_bad, bad, src);
-        const bool row_clamped = __any(clamped && !bad);             // wave-uniform: the row is the wave's
-        if (clamped_rows && row_clamped && lane == 0) atomicAdd(clamped_rows, 1);
+// The sq8 destination codec (the policy of build_csr.hip's row kernels): codes in the uint8 layout, encoded and decoded by lo4 / st4, the
+// pitch-padded quantiser as the float4 of a chunk column.  A uint8 source IS codes: copied.
+struct Sq8Codec {
+    const float4 *lo4, *st4;
+    typedef uint32_t word;
+    static constexpr bool counts_clamped = true;
+    template <int SRC> __device__ __forceinline__ HeldChunk<word> encode(const void *row, int c, int d, bool vec, bool &bad, bool &clamped) const {
+        const float4 v = load_chunk_as_f32<SRC>(row, c, d, vec);        // columns >= d: zero
+        const float4 lo = lo4[c], st = st4[c];
+        const word w = SRC == NLSH_STORE_U8 ? pack_chunk<NLSH_STORE_U8>(v)
+                     : sq8_code(v.x, lo.x, st.x, c * 4 + 0 < d, bad, clamped) | (sq8_code(v.y, lo.y, st.y, c * 4 + 1 < d, bad, clamped) << 8) |
+                       (sq8_code(v.z, lo.z, st.z, c * 4 + 2 < d, bad, clamped) << 16) | (sq8_code(v.w, lo.w, st.w, c * 4 + 3 < d, bad, clamped) << 24);
+        return {w, sq8_decode4(w, lo, st)};
     }
-}
+    __device__ __forceinline__ float4 decode(word w, int c) const { return sq8_decode4(w, lo4[c], st4[c]); }
+};
 
-// update_rows_typed_kernel for an sq8 index: 16-byte units of 16 codes, kept rows moved as bytes, new rows encoded on the way in (a uint8
-// new row is codes: copied).  inv_norm is update_inv_norm_sq8_kernel's, for the reason given at update_rows_typed_kernel.
-template <int NEW>
-__global__ __launch_bounds__(256) void update_rows_sq8_kernel(const uint4 *sorted_old, long long units_old, long long n_old,
-                                                               const void *rows_new, long long stride_new, long long m_new, int d,
-                                                               const int32_t *src, long long n_out, uint4 *sorted_out, long long units_out,
-                                                               int lg, const float4 *lo4, const float4 *st4, int32_t *first_bad,
-                                                               int32_t *clamped_rows, int vec) {
-    typedef typename StoreElem<NEW>::elem new_t;
-    const int lane = threadIdx.x & 63;
-    const int lanes = 1 << lg, g = lane & (lanes - 1), rows_per_inst = 64 >> lg;
-    const unsigned long long group = lanes == 64 ? ~0ull : (((1ull << lanes) - 1) << (lane - g));   // the lanes of this lane's row
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
-    const long long step = (long long)rows_per_inst * ROWS_IN_FLIGHT;
-    for (long long base = wave * step; base < n_out; base += nwaves * step) {     // wave-uniform
-        const uint4 *so[ROWS_IN_FLIGHT];
-        const new_t *sn[ROWS_IN_FLIGHT];
-        long long p[ROWS_IN_FLIGHT];
-        int32_t from[ROWS_IN_FLIGHT];
-        bool bad[ROWS_IN_FLIGHT], clamped[ROWS_IN_FLIGHT];
-#pragma unroll
-        for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
-            p[r] = base + (long long)r * rows_per_inst + (lane >> lg);
-            from[r] = p[r] < n_out ? src[p[r]] : 0;
-            const bool is_old = from[r] >= 0;
-            const long long j = is_old ? (long long)from[r] : (long long)~from[r];
-            const bool ok = p[r] < n_out && j < (is_old ? n_old : m_new);
-            so[r] = (ok && is_old) ? sorted_old + j * units_old : nullptr;
-            sn[r] = (ok && !is_old) ? static_cast<const new_t *>(rows_new) + j * stride_new : nullptr;
-            bad[r] = clamped[r] = false;
-        }
-        for (int u = g; u < units_out; u += 64) {
-            uint4 w[ROWS_IN_FLIGHT];
-#pragma unroll
-            for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
-                if (so[r]) w[r] = u < units_old ? so[r][u] : make_uint4(0u, 0u, 0u, 0u);
-                else if (sn[r]) {
-                    uint32_t q[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) q[j] = sq8_encode_chunk<NEW>(sn[r], 4 * u + j, d, vec != 0, lo4, st4, bad[r], clamped[r]);
-                    w[r] = make_uint4(q[0], q[1], q[2], q[3]);
-                } else w[r] = make_uint4(0u, 0u, 0u, 0u);
-            }
-#pragma unroll
-            for (int r = 0; r < ROWS_IN_FLIGHT; ++r)
-                if (p[r] < n_out) sorted_out[p[r] * units_out + u] = w[r];
-        }
-#pragma unroll
-        for (int r = 0; r < ROWS_IN_FLIGHT; ++r) {
-            report_bad_row(first_bad, bad[r], (long long)~from[r]);
-            const unsigned long long cm = __ballot(clamped[r] && !bad[r]), bm = __ballot(bad[r]);
-            if (clamped_rows && g == 0 && (cm & group) && !(bm & group)) atomicAdd(clamped_rows, 1);    // one add per saturated row
-        }
-    }
-}
-
-// update_inv_norm_typed_kernel over decoded codes.
-__global__ __launch_bounds__(256) void update_inv_norm_sq8_kernel(const uint32_t *sorted_out, long long stride_out, const float4 *lo4, const float4 *st4,
-                                                                   const float *inv_old, long long n_old, const int32_t *src, long long n_out,
-                                                                   float *inv_out) {
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
-    const int d4 = (int)(stride_out >> 2);
-    for (long long p0 = wave * 64; p0 < n_out; p0 += nwaves * 64) {     // wave-uniform
-        const long long p = p0 + lane;
-        const int32_t from = p < n_out ? src[p] : 0;
-        if (p < n_out && from >= 0) inv_out[p] = from < n_old ? inv_old[from] : inv_norm_of(0.0f);
-        unsigned long long todo = __ballot(p < n_out && from < 0);
-        while (todo) {                                                   // wave-uniform: every lane reaches the butterfly
-            const int l = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const uint32_t *row = sorted_out + (p0 + l) * (long long)d4;
-            float ss = 0.0f;
-            for (int c = lane; c < d4; c += 64) ss = sumsq_chain(sq8_decode4(row[c], lo4[c], st4[c]), ss);
-            ss = sumsq_lanes(ss, 64);
-            if (lane == 0) inv_out[p0 + l] = inv_norm_of(ss);
-        }
-    }
-}
+// The inv_norm pass of an sq8 update, instantiated here: it takes the place in the code object that update_inv_norm_sq8_kernel had, so the
+// kernels behind it keep the function ordinal their branch labels spell (profiles/row_codec.txt).
+template __global__ void update_inv_norm_of_kernel<Sq8Codec>(const void *, long long, const float *, long long, const int32_t *, long long, float *,
+                                                             const Sq8Codec);
 
 // ---- training: per-column minimum and maximum of [n, d] rows (float32 / float16, any row stride), one read of the corpus.
 // A workgroup is W x (256 / W) threads: W (a power of two >= ceil(d / 4), <= 256) chunk columns by 256 / W rows; a thread walks rows

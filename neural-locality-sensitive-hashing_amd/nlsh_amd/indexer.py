@@ -307,7 +307,7 @@ class Indexer:
         if self.storage == "sq8":
             # codes decode as they are; anything else is encoded first (the library's kernel: the one statement of the rule on the
             # device) -- deq(c, j) = float(c) * step[j] + lo[j] as two separately rounded torch operations
-            codes = rows if rows.dtype == torch.uint8 else self._sq8_encode(rows, "corpus", row_base)[:, :self.dim]
+            codes = rows if rows.dtype == torch.uint8 else self._held_rows(rows, "corpus", row_base)[:, :self.dim]
             return codes.float() * self._qstep[:self.dim] + self._qlo[:self.dim]
         dtype = _STORAGES[self.storage][0]
         return (rows if rows.dtype == dtype else rows.to(dtype)).float()
@@ -342,25 +342,46 @@ class Indexer:
         if wide.numel():
             raise ValueError(f"corpus column {int(wide[0])}: max - min overflows float32, no sq8 step can span it")
 
-    def _sq8_encode(self, rows, what, row_base=0):
-        """Float rows [M, d] (float32 / float16, unit column stride) -> their codes uint8 [M, row_stride] by the index's quantiser
-        (`nlsh_gather_rows_sq8`, identity order).  A row with a NaN or an infinity raises ValueError naming it; saturated rows are
-        counted in `last_clamped_rows`."""
-        dev, M = rows.device, int(rows.shape[0])
-        if rows.dtype not in (torch.float32, torch.float16):
-            rows = rows.float()
-        if rows.dim() != 2 or rows.stride(1) != 1:
-            rows = rows.contiguous()
-        held = torch.empty((M, self.row_stride), dtype=torch.uint8, device=dev)
-        flags = torch.empty((2,), dtype=torch.int32, device=dev)
-        _capi.check(_capi.lib().nlsh_gather_rows_sq8(
-            _capi.ptr(rows), _STORE_CODE_OF_DTYPE[rows.dtype], rows.stride(0) if M else self.dim, self.dim,
-            _capi.ptr(torch.arange(M, dtype=torch.int32, device=dev)), M, _capi.ptr(held), self.row_stride, _capi.ptr(self._qlo),
-            _capi.ptr(self._qstep), None, None, 0, _capi.ptr(flags[0:1]), _capi.ptr(flags[1:2]), _stream(dev)))
+    def _pitch(self, d):
+        """Row stride of the sorted copy, in elements: d rounded up to `row_align` (4 = 16-byte rows, the default; 32 floats = every
+        float32 row starts on a 128-byte line) and to whole 16-byte units of the storage (4 / 8 / 16 elements)."""
+        per16 = _STORAGES[self.storage][2]
+        align = max(4, int(self.row_align))
+        align = align * per16 // int(np.gcd(align, per16))
+        return int((d + align - 1) // align * align)
+
+    def _gather(self, rows, perm, out, what, row_base=0, inv_norm=None, gid=None, id_base=0):
+        """Rows [*, d] (unit column stride, a dtype the library reads) picked by `perm` [M] -> `out` [M, row_stride] as the storage holds
+        them, by the storage's C entry.  A compressed storage reads one pair of flags back: a row it cannot hold raises ValueError
+        naming it (`what` row `row_base` + its number), the saturated rows of sq8 are counted in `last_clamped_rows`."""
+        L, dev, M, d = _capi.lib(), out.device, int(perm.shape[0]), self.dim
+        src = (_capi.ptr(rows), _STORE_CODE_OF_DTYPE[rows.dtype], rows.stride(0) if M else d, d, _capi.ptr(perm), M, _capi.ptr(out))
+        tail = (_capi.ptr(inv_norm), _capi.ptr(gid), id_base)
+        if not self.compressed:
+            _capi.check(L.nlsh_gather_rows(src[0], *src[2:], self.row_stride, *tail, _stream(dev)))
+            return
+        flags = torch.zeros((2,), dtype=torch.int32, device=dev)      # first_bad (set by the call), clamped_rows (sq8 only)
+        if self.storage == "sq8":
+            _capi.check(L.nlsh_gather_rows_sq8(*src, self.row_stride, _capi.ptr(self._qlo), _capi.ptr(self._qstep), *tail,
+                                               _capi.ptr(flags[0:1]), _capi.ptr(flags[1:2]), _stream(dev)))
+        else:
+            _capi.check(L.nlsh_gather_rows_typed(*src, _STORAGES[self.storage][1], self.row_stride, *tail, _capi.ptr(flags[0:1]), _stream(dev)))
         bad, clamped = flags.cpu().tolist()
         if bad >= 0:
             self._raise_unrepresentable(row_base + bad, self.storage, what)
-        self.last_clamped_rows = int(clamped)
+        if self.storage == "sq8":
+            self.last_clamped_rows = int(clamped)
+
+    def _held_rows(self, rows, what, row_base=0):
+        """Rows [M, d] -> the rows as a compressed index will hold them, [M, row_stride] of the storage's dtype (`_gather` in identity
+        order: the library's conversion is the one statement of each storage's rule)."""
+        if rows.dtype not in _STORE_CODE_OF_DTYPE:
+            rows = rows.float()
+        if rows.dim() != 2 or rows.stride(1) != 1:
+            rows = rows.contiguous()
+        M = int(rows.shape[0])
+        held = torch.empty((M, self.row_stride), dtype=_STORAGES[self.storage][0], device=rows.device)
+        self._gather(rows, torch.arange(M, dtype=torch.int32, device=rows.device), held, what, row_base)
         return held
 
     @staticmethod
@@ -371,107 +392,54 @@ class Indexer:
         raise ValueError(f"{what} row {bad_row} holds {rule}: it cannot be stored as storage={storage!r} (nothing was changed)")
 
     # ------------------------------------------------------------------ build
-    def _build_index_compressed(self):
-        """`_build_index` with a float16 / uint8 sorted copy and no float32 copy of the corpus: the keys come from encoding the
-        dequantised rows HASH_BATCH at a time (so they are the keys of `S.float()`, not of the caller's un-rounded float32), the typed
-        gather reads the caller's tensor in its own dtype.  Peak extra memory: the sorted copy, the int32 arrays and O(HASH_BATCH) rows."""
-        corpus = self._candidate_vectors_gpu
-        if corpus.device.type != "cuda":
-            raise _capi.NlshHipError(_capi.E_INVALID, "Indexer needs a device-resident corpus; there is no CPU path")
-        L = _capi.lib()
-        N, d = corpus.shape
-        dtype, code, per16 = _STORAGES[self.storage]
-        if corpus.dtype not in _STORE_CODE_OF_DTYPE:
-            corpus = corpus.float()
-        if corpus.stride(1) != 1:
-            corpus = corpus.contiguous()
-        dev = corpus.device
-        if self.storage == "sq8":
-            # the quantiser comes first: the keys below are those of the DECODED rows (one read of the corpus trains it; the chunks
-            # that are hashed are encoded and decoded HASH_BATCH rows at a time, the sorted copy is encoded from the caller's rows)
-            self.dim = d
-            align = max(4, int(self.row_align))
-            align = align * per16 // np.gcd(align, per16)
-            self.row_stride = int((d + align - 1) // align * align)
-            self._sq8_set_quantiser(corpus, d, self.row_stride, dev)
+    def _corpus_keys(self, corpus):
+        """Bucket key of every corpus row, int32 [N]: `corpus_keys=` if given, else the hasher's on the rows as the index holds them."""
+        N, dev = int(corpus.shape[0]), corpus.device
         if self._given_keys is not None:
             keys = self._given_keys
             if keys.shape != (N,) or keys.dtype != torch.int32 or keys.device != dev:
                 raise ValueError("corpus_keys must be int32 [N] on the corpus device")
-            keys = keys.contiguous()
-        elif N <= HASH_BATCH:
-            keys, _ = self.hash_device(self._dequantised(corpus), hash_times=1)
-        else:
-            # One probe per row is the hard key: no draw is made, so the chunks need no seeds of their own.  The first call takes the
-            # hasher's next seed as the float32 build's single call does (the call counter ends where that build leaves it); a BatchNorm
-            # encoder in train mode sees the same HASH_BATCH-row batches `hash_device` would cut.
-            needs_train = getattr(self._hashing, "_needs_train_forward", None)
-            per_batch = needs_train is not None and needs_train()
-            keys = torch.empty((N, 1), dtype=torch.int32, device=dev)
-            for lo in range(0, N, HASH_BATCH):
-                part = self._dequantised(corpus[lo:lo + HASH_BATCH], row_base=lo)
-                keys[lo:lo + HASH_BATCH] = self.hash_device(part, hash_times=1, seed=None if (lo == 0 or per_batch) else 0)[0]
-        self.corpus_keys = keys.view(-1)
-        self.perm, self.uniq_keys, self.offsets = build_csr_device(self.corpus_keys)
-        self.n_buckets = int(self.uniq_keys.shape[0])
-        self.dim = d
-        align = max(4, int(self.row_align))
-        align = align * per16 // np.gcd(align, per16)       # elements: a pitch of whole 16-byte units (4 / 8 / 16 elements at the least)
-        self.row_stride = int((d + align - 1) // align * align)
-        self.corpus_sorted = torch.empty((N, self.row_stride), dtype=dtype, device=dev)
-        self.gid = torch.empty((N,), dtype=torch.int32, device=dev)
-        self.inv_norm = torch.empty((N,), dtype=torch.float32, device=dev) if self.metric == "cosine" else None
-        first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
-        if self.storage == "sq8":
-            clamped = torch.empty((1,), dtype=torch.int32, device=dev)
-            _capi.check(L.nlsh_gather_rows_sq8(_capi.ptr(corpus), _STORE_CODE_OF_DTYPE[corpus.dtype], corpus.stride(0) if N else d, d,
-                                               _capi.ptr(self.perm), N, _capi.ptr(self.corpus_sorted), self.row_stride, _capi.ptr(self._qlo),
-                                               _capi.ptr(self._qstep), _capi.ptr(self.inv_norm), _capi.ptr(self.gid), self.id_base,
-                                               _capi.ptr(first_bad), _capi.ptr(clamped), _stream(dev)))
-            self.last_clamped_rows = int(clamped.item())
-        else:
-            _capi.check(L.nlsh_gather_rows_typed(_capi.ptr(corpus), _STORE_CODE_OF_DTYPE[corpus.dtype], corpus.stride(0) if N else d, d,
-                                                 _capi.ptr(self.perm), N, _capi.ptr(self.corpus_sorted), code, self.row_stride,
-                                                 _capi.ptr(self.inv_norm), _capi.ptr(self.gid), self.id_base, _capi.ptr(first_bad), _stream(dev)))
-        bad = int(first_bad.item())
-        if bad >= 0:
-            self._raise_unrepresentable(bad, self.storage, "corpus")
-        if self.row_ids is not None:
-            if self.row_ids.shape[0] != N or self.row_ids.dtype != torch.int32:
-                raise ValueError("row_ids must be int32 [N]")
-            self.gid = self.row_ids[self.perm.long()].contiguous()
-        self._refresh_bucket_tables()
+            return keys.contiguous()
+        if not self.compressed:
+            # indexer.py:36-38: hash(candidates, hash_times=1), in 4096-row batches when the module's mode makes batches matter
+            return self.hash_device(corpus, hash_times=1)[0].view(-1)
+        if N <= HASH_BATCH:
+            return self.hash_device(self._dequantised(corpus), hash_times=1)[0].view(-1)
+        # A compressed index hashes the dequantised rows HASH_BATCH at a time (the keys of `S.float()`, not of the caller's un-rounded
+        # float32; no float32 copy of the corpus).  One probe per row is the hard key: no draw is made, so the chunks need no seeds of
+        # their own.  The first call takes the hasher's next seed as the float32 build's single call does (the call counter ends where
+        # that build leaves it); a BatchNorm encoder in train mode sees the same HASH_BATCH-row batches `hash_device` would cut.
+        needs_train = getattr(self._hashing, "_needs_train_forward", None)
+        per_batch = needs_train is not None and needs_train()
+        keys = torch.empty((N, 1), dtype=torch.int32, device=dev)
+        for lo in range(0, N, HASH_BATCH):
+            part = self._dequantised(corpus[lo:lo + HASH_BATCH], row_base=lo)
+            keys[lo:lo + HASH_BATCH] = self.hash_device(part, hash_times=1, seed=None if (lo == 0 or per_batch) else 0)[0]
+        return keys.view(-1)
 
     def _build_index(self):
-        if self.compressed:
-            return self._build_index_compressed()
+        """The CSR index and the bucket-sorted copy in the index's storage.  A compressed copy is gathered from the caller's tensor in
+        its own dtype: peak extra memory is the sorted copy, the int32 arrays and O(HASH_BATCH) rows."""
         corpus = self._candidate_vectors_gpu
         if corpus.device.type != "cuda":
             raise _capi.NlshHipError(_capi.E_INVALID, "Indexer needs a device-resident corpus; there is no CPU path")
-        L = _capi.lib()
         N, d = corpus.shape
-        if corpus.dtype != torch.float32 or corpus.stride(1) != 1:
-            corpus = corpus.float().contiguous()
-        if self._given_keys is not None:
-            keys = self._given_keys
-            if keys.shape != (N,) or keys.dtype != torch.int32 or keys.device != corpus.device:
-                raise ValueError("corpus_keys must be int32 [N] on the corpus device")
-            keys = keys.contiguous()
-        else:
-            keys, _ = self.hash_device(corpus, hash_times=1)       # indexer.py:36-38: hash(candidates, hash_times=1), in 4096-row batches when the module's mode makes batches matter
-        self.corpus_keys = keys.view(-1)
+        if corpus.dtype not in (_STORE_CODE_OF_DTYPE if self.compressed else (torch.float32,)):
+            corpus = corpus.float()
+        if corpus.stride(1) != 1:
+            corpus = corpus.contiguous()
+        dev = corpus.device
+        self.dim, self.row_stride = d, self._pitch(d)
+        if self.storage == "sq8":
+            # the quantiser comes first: the keys are those of the DECODED rows (one read of the corpus trains it)
+            self._sq8_set_quantiser(corpus, d, self.row_stride, dev)
+        self.corpus_keys = self._corpus_keys(corpus)
         self.perm, self.uniq_keys, self.offsets = build_csr_device(self.corpus_keys)
         self.n_buckets = int(self.uniq_keys.shape[0])
-        self.dim = d
-        align = max(4, int(self.row_align))       # floats; 4 = 16-byte rows (the default), 32 = every row starts on a 128-byte line
-        self.row_stride = (d + align - 1) // align * align
-        dev = corpus.device
-        self.corpus_sorted = torch.empty((N, self.row_stride), dtype=torch.float32, device=dev)
+        self.corpus_sorted = torch.empty((N, self.row_stride), dtype=_STORAGES[self.storage][0], device=dev)
         self.gid = torch.empty((N,), dtype=torch.int32, device=dev)
         self.inv_norm = torch.empty((N,), dtype=torch.float32, device=dev) if self.metric == "cosine" else None
-        _capi.check(L.nlsh_gather_rows(_capi.ptr(corpus), corpus.stride(0) if N else d, d, _capi.ptr(self.perm), N,
-                                       _capi.ptr(self.corpus_sorted), self.row_stride, _capi.ptr(self.inv_norm),
-                                       _capi.ptr(self.gid), self.id_base, _stream(dev)))
+        self._gather(corpus, self.perm, self.corpus_sorted, "corpus", inv_norm=self.inv_norm, gid=self.gid, id_base=self.id_base)
         if self.row_ids is not None:
             if self.row_ids.shape[0] != N or self.row_ids.dtype != torch.int32:
                 raise ValueError("row_ids must be int32 [N]")
@@ -555,38 +523,22 @@ class Indexer:
             _capi.check(_capi.E_INVALID)
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         keep_u8 = None if keep is None else keep.to(torch.uint8)
+        # One call: the old index | the new rows | the outputs | the workspace, with what the storage's entry adds.  Kept rows move as
+        # bytes; the new rows of a compressed index arrive as it holds them (`_new_rows` has converted, checked and counted float32
+        # ones), so the call converts nothing and needs no flags.  Out of place: a refusal leaves every array of the index the old one.
+        code = _STORAGES[self.storage][1]
         if not self.compressed:
-            _capi.check(L.nlsh_csr_update(
-                _capi.ptr(self.corpus_sorted), stride, self.dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
-                _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
-                _capi.ptr(vectors), vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
-                _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
-                _capi.ptr(nb_out), _capi.ptr(ws), ws_bytes, _stream(dev)))
+            entry, head, new, flags = L.nlsh_csr_update, (), (), ()
         elif self.storage == "sq8":
-            # kept rows move as bytes; the new rows arrive as codes (`_new_rows` has encoded float ones and counted the saturated rows);
-            # new rows' inv_norm over the decoded values
-            _capi.check(L.nlsh_csr_update_sq8(
-                _capi.ptr(self.corpus_sorted), _capi.ptr(self._qlo), _capi.ptr(self._qstep), stride, self.dim, _capi.ptr(self.gid),
-                _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys), _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
-                _capi.ptr(vectors), _capi.STORE_U8, vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
-                _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
-                _capi.ptr(nb_out), None, None, _capi.ptr(ws), ws_bytes, _stream(dev)))
+            entry, head, new, flags = L.nlsh_csr_update_sq8, (_capi.ptr(self._qlo), _capi.ptr(self._qstep)), (code,), (None, None)
         else:
-            # kept rows move as bytes; the new rows arrive in the storage's dtype (`_new_rows` has converted and checked float32 ones).  The
-            # call itself also converts -- C callers hand it rows of another storage -- and reports through `first_bad`; out of place, so
-            # a refusal leaves every array of the index the old one
-            code = _STORAGES[self.storage][1]
-            first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
-            _capi.check(L.nlsh_csr_update_typed(
-                _capi.ptr(self.corpus_sorted), code, stride, self.dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
-                _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
-                _capi.ptr(vectors), _STORE_CODE_OF_DTYPE[vectors.dtype] if M else code, vectors.stride(0) if M else self.dim, _capi.ptr(new_keys),
-                _capi.ptr(new_ids), M,
-                _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
-                _capi.ptr(nb_out), _capi.ptr(first_bad), _capi.ptr(ws), ws_bytes, _stream(dev)))
-            bad = int(first_bad.item())
-            if bad >= 0:
-                self._raise_unrepresentable(bad, self.storage, "added")
+            entry, head, new, flags = L.nlsh_csr_update_typed, (code,), (_STORE_CODE_OF_DTYPE[vectors.dtype] if M else code,), (None,)
+        _capi.check(entry(
+            _capi.ptr(self.corpus_sorted), *head, stride, self.dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
+            _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
+            _capi.ptr(vectors), *new, vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
+            _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
+            _capi.ptr(nb_out), *flags, _capi.ptr(ws), ws_bytes, _stream(dev)))
         n_buckets = int(nb_out.item())
         # the int32 side arrays in LOCAL order, from where every sorted row came from (`src_out`): torch plumbing, 4 bytes per row
         src = src_out.long()
@@ -637,27 +589,14 @@ class Indexer:
         if M == 0:
             return None, None, None
         vectors = add if add.stride(1) == 1 else add.contiguous()
-        if self.storage == "sq8":
-            # float32 rows are encoded FIRST by the index's quantiser (saturating: `last_clamped_rows`; a NaN or an infinity is refused
-            # before the hasher is touched); uint8 rows are codes.  What is hashed and merged below is the rows as the index holds them.
-            if vectors.dtype == torch.float32:
-                vectors = self._sq8_encode(vectors, "added")[:, :self.dim]
-            else:
+        if self.compressed:
+            # float32 rows are converted and checked FIRST, by the storage's own rule (sq8 saturates: `last_clamped_rows`): a refusal comes
+            # before the hasher is touched, and what is hashed and merged below is the rows as the index will hold them.  Rows of the
+            # storage's own dtype are held as they are (uint8 rows of an sq8 index are codes).
+            if self.storage == "sq8":
                 self.last_clamped_rows = 0
-        elif self.compressed and vectors.dtype == torch.float32:
-            # float32 rows into a compressed index are converted and checked FIRST (the typed gather with the identity permutation: the
-            # one conversion rule, one device flag): a refusal comes before the hasher is touched, and what is hashed and merged below
-            # is the rows as the index will hold them
-            dtype, code, _ = _STORAGES[self.storage]
-            held = torch.empty((M, self.row_stride), dtype=dtype, device=dev)
-            first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
-            _capi.check(_capi.lib().nlsh_gather_rows_typed(
-                _capi.ptr(vectors), _capi.STORE_F32, vectors.stride(0), self.dim, _capi.ptr(torch.arange(M, dtype=torch.int32, device=dev)), M,
-                _capi.ptr(held), code, self.row_stride, None, None, 0, _capi.ptr(first_bad), _stream(dev)))
-            bad = int(first_bad.item())
-            if bad >= 0:
-                self._raise_unrepresentable(bad, self.storage, "added")
-            vectors = held[:, :self.dim]
+            if vectors.dtype == torch.float32:
+                vectors = self._held_rows(vectors, "added")[:, :self.dim]
         if add_keys is not None:
             keys = add_keys
             if not isinstance(keys, torch.Tensor) or keys.shape != (M,) or keys.dtype != torch.int32 or keys.device != dev:
