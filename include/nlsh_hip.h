@@ -710,6 +710,40 @@ int nlsh_merge_topk_unique(const uint64_t *keys_in, int64_t row_stride, int G, i
                            float *out_dist, int32_t *out_idx, uint64_t *out_keys /* nullable */, int32_t *out_ncand, nlsh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exact re-ranking: the second stage of a two-stage query.  A scan over a compressed (float16 / uint8 / sq8) or a
+ * folded-L2 index over-fetches kc > k candidates per query; this call rescores those kc rows on the ORIGINAL float32 rows and keeps
+ * the k best.  No reference counterpart (the reference scans the caller's float32 rows and has nothing to refine).
+ *   Refine store: the index's rows as float32 in ID ORDER -- store [n_rows, store_stride], row id - id_base is the original row with
+ *         that id; store_stride a multiple of 4 floats, >= d, the whole pitch of every row readable (columns >= d are never used);
+ *         16-byte aligned.  Cosine: store_inv_norm [dev] [n_rows] holds the bits nlsh_gather_rows gives that row.  The store is device
+ *         memory (store_on_host = 0) or pinned host memory mapped for the device (store_on_host = 1: hipHostMalloc / hipHostRegister;
+ *         both ends of the store are held against the runtime's record of the mapping, a device pointer is refused); the kernel is
+ *         the same, a host store is read over the host link.
+ *   Input: queries [dev] [Q, q_stride] (any 4-byte alignment, strided row views allowed); cand [dev] [Q, cand_stride], the first kc
+ *         of each row one query's candidate ids (stage one's out_idx as it is).  1 <= k <= kc <= NLSH_MAX_K_TILED.
+ *   Ids:  a VALID id is one in [id_base, id_base + n_rows).  -1 is padding and may stand anywhere in a list.  Any other id is DROPPED,
+ *         never dereferenced, and reported: first_bad [dev] int32 [1] receives the smallest query number whose list held one, -1 for
+ *         none (the call initialises it).  Precondition, NOT checked: the ids within one list are distinct.
+ *   Result: per query the k smallest sort keys  mono(dist(q, row(id))) << 32 | id  over its valid ids, ascending -- the (distance bits,
+ *         id) order of every other top-k path -- in out_dist [Q, k], out_idx [Q, k], out_keys [Q, k] (nullable), the tail padded as
+ *         the scan pads it: id -1, dist +inf, key ~0.  out_count [Q] (nullable) = the number of real entries, min(k, valid ids).
+ *   dist has THE BITS THE TILED FLOAT32 SCAN GIVES THE SAME (query, row) PAIR:
+ *         one fmaf chain per pair over the dimension, ascending from 0;
+ *         NLSH_METRIC_L2_EPS  acc += ((q - c) + 1e-6f)^2, then the correctly rounded square root;
+ *         NLSH_METRIC_COSINE  acc += q' * c over q' = q / max(||q||, 1e-8) as the scan's PLAN phase normalises it, then
+ *                             1.0f - acc * store_inv_norm[row].
+ *         The re-rank is always the EXACT L2 form, whatever form stage one ran with: NLSH_METRIC_L2_EPS_FOLDED is refused.
+ *   Limits: 1 <= k <= kc <= NLSH_MAX_K_TILED and 1 <= d <= NLSH_MAX_DIM (NLSH_E_UNSUPPORTED beyond), Q < 2^31; Q = 0 is NLSH_OK
+ *         without a launch.  Every argument is checked on the host before anything is enqueued.  One launch; no workspace, no
+ *         atomics but the first_bad minimum. */
+int nlsh_rerank_topk(const float *queries, int64_t q_stride, int64_t Q, int d,
+                     const float *store, int64_t store_stride, int64_t n_rows, int32_t id_base, int store_on_host,
+                     const float *store_inv_norm /* cosine, device */,
+                     const int32_t *cand, int64_t cand_stride, int kc, int k, int metric /* NLSH_METRIC_L2_EPS | NLSH_METRIC_COSINE */,
+                     float *out_dist, int32_t *out_idx, uint64_t *out_keys /* nullable */, int32_t *out_count /* nullable */,
+                     int32_t *first_bad, nlsh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact brute-force k-NN: every row of `corpus` against every query, fp32-MFMA distances with the top-k fused behind them.
  * Replaces the reference's mm + topk precompute (precompute.py:22-67): ground truth of a query set, self-kNN of a training set.
  * Distances take precompute.py's forms, NOT the scan's pairwise_distance form (no square root, no epsilon):

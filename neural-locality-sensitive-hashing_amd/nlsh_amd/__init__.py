@@ -7,7 +7,7 @@ and `nlsh_amd.metrics` stay usable where the HIP library has not been built.
 """
 __version__ = "0.1.0"
 
-_LAZY = {"MultiTableIndexer": "multitable", "MultiRowFilter": "multitable"}
+_LAZY = {"MultiTableIndexer": "multitable", "MultiRowFilter": "multitable", "RefineStore": "refine"}
 
 
 def __getattr__(name):

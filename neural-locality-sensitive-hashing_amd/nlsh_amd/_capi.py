@@ -47,6 +47,7 @@ SYMBOLS = (
     "nlsh_merge_topk_unique",
     "nlsh_range_workspace", "nlsh_range_sort_workspace", "nlsh_range_count", "nlsh_range_fill",
     "nlsh_sq8_train_workspace", "nlsh_sq8_train", "nlsh_gather_rows_sq8", "nlsh_csr_update_sq8", "nlsh_scan_topk_cells_phase_sq8",
+    "nlsh_rerank_topk",
 )
 
 
@@ -185,6 +186,8 @@ def lib():
     L.nlsh_merge_topk.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, vp, vp]
     L.nlsh_merge_topk_unique.restype = i32     # nlsh_merge_topk with out_keys in front of out_ncand
     L.nlsh_merge_topk_unique.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp]
+    L.nlsh_rerank_topk.restype = i32           # queries (4) | store (5), inv_norm | cand, stride, kc, k, metric | outputs (4), first_bad, stream
+    L.nlsh_rerank_topk.argtypes = [vp, i64, i64, i32,  vp, i64, i64, ctypes.c_int32, i32, vp,  vp, i64, i32, i32, i32,  vp, vp, vp, vp, vp, vp]
     L.nlsh_step_create.restype = i32
     L.nlsh_step_create.argtypes = [ctypes.POINTER(StepDesc), sz, ctypes.POINTER(vp)]
     L.nlsh_step_create_graph.restype = i32

@@ -239,6 +239,9 @@ class ShardedIndexer:
 
     def __init__(self, hashing, local_corpus_gpu, distance_func, id_base: int, group=None, shard: str = "buckets", **kw):
         from .indexer import Indexer
+        if kw.get("refine") is not None:
+            raise NotImplementedError("ShardedIndexer is not built for refine=: the ranks exchange stage one's keys, and a refine store "
+                                      "addresses rows by id - id_base, which a bucket shard's ids are not (DESIGN.md 7)")
         if shard not in ("buckets", "rows"):
             raise ValueError("shard must be 'buckets' or 'rows'")
         if kw.get("storage") not in (None, "float32"):

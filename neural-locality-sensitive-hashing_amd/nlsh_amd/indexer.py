@@ -25,6 +25,7 @@ import torch
 
 from . import _capi
 from .data import metric_of
+from .refine import RefineStore, checked_refine, stage_one_k
 from .hashings import host_key_set, keys_to_sets
 
 HASH_BATCH = 4096  # nlsh/indexer.py:40 default batch_size
@@ -225,12 +226,22 @@ class Indexer:
     # the float32 index over its dequantised rows: both conversions to float32 are exact, the rows are widened as the tiled scan stages
     # them, and every array and every query result has the float32 index's bits.
     storage = "float32"
+    # None | "device" | "host": where the index keeps the caller's float32 rows for the exact re-rank; None = no second stage
+    refine, refine_factor, refine_store = None, 4, None
 
     def __init__(self, hashing, candidate_vectors_gpu, distance_func, compat=True, metric: Optional[str] = None,
                  seg_rows: int = 0, id_base: int = 0, algo: Optional[str] = None,
                  row_ids: Optional[torch.Tensor] = None, schedule_stats: Optional[Tuple[float, float]] = None,
                  corpus_keys: Optional[torch.Tensor] = None, l2_form: str = "exact", window_rows: Optional[int] = None,
-                 row_align: int = 4, storage: Optional[str] = None, quantiser=None):
+                 row_align: int = 4, storage: Optional[str] = None, quantiser=None, refine: Optional[str] = None, refine_factor: int = 4):
+        # refine: None | "device" | "host" = keep the caller's rows as float32 in id order (`RefineStore`) and rescore every
+        # top-k call's candidates on them: stage one runs at k1 = min(256, max(k, refine_factor * k)), one `nlsh_rerank_topk` launch cuts
+        # to k.  The store addresses rows by id - id_base: custom ids (`row_ids=`, `add(ids=)`) are refused, here and there.
+        self.refine, self.refine_factor = checked_refine(refine, refine_factor)
+        self.refine_store = None
+        if self.refine is not None and row_ids is not None:
+            raise ValueError("refine= needs the default row ids (id_base + row): the refine store addresses a row by id - id_base, "
+                             "row_ids= names rows freely")
         # storage: None / "float32" = the float32 copy (any other corpus dtype is converted with `.float()`, as ever); "float16" /
         # "uint8" / "sq8" = a compressed copy, read by the tiled schedule only (checked before anything touches a device)
         if storage is not None and storage not in _STORAGES:
@@ -297,6 +308,14 @@ class Indexer:
         self._build_index()
         # the id `add` gives its first row when the caller names none: only ever grows, so a removed row's id is never handed out again
         self.next_id = self.id_base + int(self.gid.shape[0])
+        if self.refine is not None:
+            if self.metric not in ("l2", "cosine"):
+                raise NotImplementedError("refine= needs metric 'l2' or 'cosine': the re-rank kernel computes the distance")
+            # the caller's rows BEFORE they are compressed (sq8 codes have no other original than what they decode to)
+            originals = candidate_vectors_gpu
+            if self.storage == "sq8" and originals.dtype == torch.uint8:
+                originals = self._dequantised(originals)
+            self.refine_store = RefineStore(originals, self.metric, id_base=self.id_base, where=self.refine, row_align=self.row_align)
 
     @property
     def compressed(self):
@@ -486,6 +505,9 @@ class Indexer:
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("update / add / remove need metric 'l2' or 'cosine': the generic-metric query reads the caller's "
                                       "corpus, which a mutated index no longer mirrors")
+        if self.refine_store is not None and add_ids is not None:
+            raise ValueError("add(ids=...) on an index with refine=: the refine store addresses a row by id - id_base, so added rows take "
+                             "the default ids (nothing was changed)")
         dev, N = self.corpus_sorted.device, int(self.gid.shape[0])
         vectors, new_ids, new_keys = self._new_rows(add, add_ids, add_keys, dev)
         M = 0 if vectors is None else int(vectors.shape[0])
@@ -566,6 +588,14 @@ class Indexer:
             self.next_id = max(self.next_id, int(new_ids.max().item()) + 1)
         self._drop_derived()
         self._candidate_vectors_gpu = None      # the index owns its rows now
+        if M and self.refine_store is not None:
+            # the caller's rows as they came, under the ids they were given (default ids: next_id .. = id_base + rows of the store);
+            # `remove` leaves the store alone -- stage one can no longer return a removed id
+            originals = add
+            if self.storage == "sq8" and add.dtype == torch.uint8:
+                originals = self._dequantised(vectors)
+            assert int(new_ids[0].item()) == self.id_base + self.refine_store.n_rows
+            self.refine_store.append(originals)
         self.generation += 1
         return (new_ids if M else torch.empty((0,), dtype=torch.int32, device=dev)), N - n_kept
 
@@ -951,13 +981,37 @@ class Indexer:
         self.last_algo, self.last_window = algo, window
         self._last_pack, self._last_tkey, self._last_max_tasks = pack, tkey, max_tasks
 
-    def scan_tensors(self, query_vectors, keys, nkeys, k=10, want_keys=False, check=True, events=None, algo=None, filter=None):
+    def _refine_k1(self, k, refine_k):
+        """Stage one's k of a call on this index: 0 = no second stage (no store, or `refine_k=0`); host arithmetic and refusals only."""
+        if self.refine_store is None:
+            if refine_k:
+                raise ValueError("refine_k= needs an index built with refine='device' or 'host'")
+            return 0
+        return stage_one_k(k, self.refine_factor, refine_k)
+
+    def _refuse_refine(self, what):
+        if self.refine is not None:
+            raise NotImplementedError(f"{what} is not built for an index with refine=: the re-rank is a top-k stage (DESIGN.md 7)")
+
+    def _rerank(self, query_vectors, stage_one, k, want_keys, check=True):
+        """Stage two behind a stage-one result (dist, idx [Q, k1], ncand, ...): ONE further launch on the same stream, stage one's idx its
+        candidate table, nothing read on the host in between -> (exact dist [Q, k], idx [Q, k], stage one's ncand, stage two's keys64 | None)."""
+        out = self.refine_store.rerank(self._as_queries(query_vectors), stage_one[1], k, want_keys=True, check=check)
+        path = self.last_query_path or "two_step"        # (a bare `scan_tensors` call is the two-step route's second step)
+        self.last_query_path = path if path.endswith("+refine") else path + "+refine"
+        return out[0], out[1], stage_one[2], out[3] if want_keys else None
+
+    def scan_tensors(self, query_vectors, keys, nkeys, k=10, want_keys=False, check=True, events=None, algo=None, filter=None, refine_k=None):
         """Scan stage on a device key table -> (dist [Q,k], idx [Q,k], ncand [Q], keys64 | None).
         filter (a `RowFilter` of this index, `row_filter()`; None = off): the result is, word for word, that of the index built from the
         allowed rows alone (same ids, same bucket keys, same key table) -- ids, distance bits and keys64, with -1 / +inf / ~0 behind a
         list shorter than k.  `ncand` stays the rows of the probed buckets, counted BEFORE the filter: the work the scan did, equal to
         the unfiltered call's.  A filtered call takes the tiled schedule whatever the batch shape, as a compressed index does."""
         filter = self._checked_filter(filter, algo)
+        k1 = self._refine_k1(k, refine_k)
+        if k1:      # stage one at k1 (this call, unrefined), then the re-rank (DESIGN.md 4.15)
+            one = self.scan_tensors(query_vectors, keys, nkeys, k=k1, check=check, events=events, algo=algo, filter=filter, refine_k=0)
+            return self._rerank(query_vectors, one, k, want_keys, check)
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("fused scan needs metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
         q = self._as_queries(query_vectors)
@@ -1085,7 +1139,7 @@ class Indexer:
         for c0 in range(0, keys.shape[1], _capi.MAX_PROBES):
             kc = keys[:, c0:c0 + _capi.MAX_PROBES].contiguous()
             nk = (nkeys - c0).clamp(0, kc.shape[1]).to(torch.int32)
-            _, _, nc, k64 = self.scan_tensors(q, kc, nk, k=k, want_keys=True, check=check, filter=filter)
+            _, _, nc, k64 = self.scan_tensors(q, kc, nk, k=k, want_keys=True, check=check, filter=filter, refine_k=0)
             parts.append(k64)
             counts.append(nc)
         packed = torch.cat([torch.stack(parts), torch.stack(counts).long()[:, :, None]], dim=2)
@@ -1153,6 +1207,7 @@ class Indexer:
         limit (None = off): ValueError once the counts are known and before any output is allocated, if T > limit.
         Two scan launches with one host read between them (`nlsh_range_count`, `nlsh_range_fill`): the call synchronises.  Always the
         tiled schedule, as filtered and compressed calls; key tables wider than 64 probes are refused."""
+        self._refuse_refine("range_scan_tensors")
         self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
         if self.metric not in ("l2", "cosine"):
@@ -1217,6 +1272,7 @@ class Indexer:
                       want_keys=False):
         """Device-resident radius query: the hash by the two-step route (`last_query_path == "two_step"`; probes / candidate_budget as in
         `query_tensors`), then `range_scan_tensors`.  hash_times <= 64."""
+        self._refuse_refine("range_tensors")
         self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
         if self.metric not in ("l2", "cosine"):
@@ -1243,11 +1299,13 @@ class Indexer:
         """Radius query in the shape `query()` returns: (List[List[int]], List[int]) -- per query the ids of every candidate within
         `radius`, in (distance, row id) order, and the candidate counts (before the radius and the filter); with return_distances=True
         also the lists of distances.  See `range_scan_tensors`."""
+        self._refuse_refine("range_query")
         out = self.range_tensors(query_vectors, radius, hash_times, seed, probes, candidate_budget, filter, limit)
         return self._range_lists(*out[:4], return_distances)
 
     def range_query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], radius, filter=None, return_distances=False):
         """`range_query` on caller-supplied key lists, like `query_with_keys`."""
+        self._refuse_refine("range_query_with_keys")
         self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
         key_lists = [list(dict.fromkeys(int(key) for key in ks)) for ks in key_lists]
@@ -1264,8 +1322,11 @@ class Indexer:
         return self._range_lists(*out[:4], return_distances)
 
     def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None, probes=None,
-                      candidate_budget=None, filter=None):
+                      candidate_budget=None, filter=None, refine_k=None):
         """Device-resident form of `query`: hashing + scan, nothing copied to the host.
+        refine_k (an index built with `refine=` only): None = stage one at k1 = min(256, max(k, refine_factor * k)), an integer in
+        [k, 256] = stage one at that k1, 0 = no second stage for this call.  With the stage on, the distances are the exact float32
+        ones of the ORIGINAL rows, `ncand` is stage one's, keys64 stage two's and `last_query_path` ends in "+refine".
         events = (begin, end) torch.cuda.Event pair (already recorded once) bracketing the scan kernel.
         probes ("sampled" | "ranked", None = the hasher's `probes` attribute): the multi-probe mode of this call.
         candidate_budget (ranked mode only; None = off): a query probes its ranked keys until their buckets hold that many candidates,
@@ -1274,9 +1335,14 @@ class Indexer:
         filtered tiled scan; `last_query_path == "two_step"`), never the fused or the ranked one-call route.  The candidate counts and
         `candidate_budget` count bucket rows BEFORE the filter: the probe kernel does not know it."""
         filter = self._checked_filter(filter)
+        k1 = self._refine_k1(k, refine_k)
+        if k1:
+            one = self.query_tensors(query_vectors, k=k1, hash_times=hash_times, seed=seed, check=check, events=events, probes=probes,
+                                     candidate_budget=candidate_budget, filter=filter, refine_k=0)
+            return self._rerank(query_vectors, one, k, want_keys, check)
         if filter is not None:
             keys, nkeys = self._filtered_keys(query_vectors, hash_times, seed, probes, candidate_budget)
-            return self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events, filter=filter)
+            return self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events, filter=filter, refine_k=0)
         if candidate_budget is not None:
             budget = self._candidate_budget(candidate_budget, probes)
             q = self._as_queries(query_vectors)
@@ -1285,7 +1351,7 @@ class Indexer:
                 return self._ranked_tensors(q, k, hash_times, budget, want_keys, check, events, algo, self._n_multi_rows(q.shape[0]))[:4]
             self.last_query_path = "two_step"
             keys, nkeys, _ = self._hash_budget(q, HASH_BATCH, hash_times, budget)
-            return self.scan_tensors(q, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events)
+            return self.scan_tensors(q, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events, refine_k=0)
         if probes is None:
             return self._batch_tensors(query_vectors, k, hash_times, seed, want_keys=want_keys, check=check, events=events)[:4]
         with self._probe_mode(probes):
@@ -1335,7 +1401,8 @@ class Indexer:
     # profiles/ranked_one_call.txt, tools/ranked_path_bench.py) -- the fused kernel takes longer than the two it replaces and the
     # launches it saves were not idle time.  True selects it (the tests and the A/B tool do); DESIGN.md 4.7 has the analysis.
     ranked_one_call = False
-    # which form served the last `query_tensors` / `query` call: "fused" (sampled, `nlsh_query_batch`) | "ranked_one_call" | "two_step"
+    # which form served the last `query_tensors` / `query` call: "fused" (sampled, `nlsh_query_batch`) | "ranked_one_call" | "two_step",
+    # with "+refine" behind it when the exact re-rank ran behind that form (an index built with refine=)
     last_query_path = None
 
     def _fuses_ranked(self, q, hash_times, algo, ranked=None):
@@ -1422,7 +1489,7 @@ class Indexer:
                 keys, nkeys = self._hashing.hash_device(q, n=hash_times, n_multi_rows=n_multi, seed=seed, row0=row0, out=out)
             else:
                 keys, nkeys = self.hash_device(q, hash_times=hash_times, seed=seed)
-            return self.scan_tensors(q, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events, algo=algo) + (keys, nkeys)
+            return self.scan_tensors(q, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events, algo=algo, refine_k=0) + (keys, nkeys)
         if d != self.dim:
             raise ValueError(f"query dim {d} != corpus dim {self.dim}")
         L, h, dev, P = _capi.lib(), self._hashing, q.device, hash_times
@@ -1537,9 +1604,9 @@ class Indexer:
         there, and nothing has to be copied afterwards."""
         if fused is None:
             if hi - lo == q.shape[0]:     # the whole batch (`_host_results`): nothing to slice
-                self.scan_tensors(q, keys, nkeys, k=k, check=False, algo=algo)
+                self.scan_tensors(q, keys, nkeys, k=k, check=False, algo=algo, refine_k=0)
             else:
-                self.scan_tensors(q[lo:hi], keys[lo:hi], nkeys[lo:hi], k=k, check=False, algo=algo)
+                self.scan_tensors(q[lo:hi], keys[lo:hi], nkeys[lo:hi], k=k, check=False, algo=algo, refine_k=0)
             return
         mode, seed, n_multi = fused
         ranked = mode == "ranked"
@@ -1799,8 +1866,22 @@ class Indexer:
     # of two threads and the nested pause of `_plain_lists` leave the collector as the FIRST of them found it (r06).
     pause_collector_for_call = True
 
+    def _query_refined(self, query_vectors, k, k1, hash_times, seed, probes, candidate_budget, filter):
+        """`query()` of an index with refine=: the two-step route's key table, stage one at k1, the re-rank, one copy to the host.  The
+        short-query rule (F7) is applied from stage one's candidate counts, as on an unrefined index."""
+        if hash_times < 1:
+            raise ValueError(f"`n` should be positive integer, but got {hash_times}")
+        keys, nkeys = self._filtered_keys(query_vectors, hash_times, seed, probes, candidate_budget)
+        _, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter, refine_k=k1)
+        self.last_query_path = "two_step+refine"
+        if filter is not None:
+            return self._filtered_lists(idx, ncand, keys64)
+        idx_h, nc_h = np.ascontiguousarray(idx.cpu().numpy()), ncand.cpu().numpy()
+        keys_h, nkeys_h = (keys.cpu().numpy(), nkeys.cpu().numpy()) if self.compat else (None, None)
+        return self._to_lists(self._short_key_sets(nc_h, keys_h, nkeys_h, k), idx_h, nc_h, k)
+
     def query(self, query_vectors, k=10, hash_times=10, seed=None, probes=None, candidate_budget=None,
-              filter=None) -> Tuple[List[List[int]], List[int]]:
+              filter=None, refine_k=None) -> Tuple[List[List[int]], List[int]]:
         """nlsh/indexer.py:56-96.  `seed` (not in the reference): the Philox seed of the multi-probe draws; None takes the next one
         from the hasher's call counter, like every other hashing call.  `probes` (not in the reference): "sampled" | "ranked", the
         multi-probe mode of this call; None = the hasher's `probes` attribute.  `candidate_budget` (not in the reference; ranked mode
@@ -1811,10 +1892,14 @@ class Indexer:
         NOT applied to a filtered one, whatever `compat` says.  The candidate counts (and `candidate_budget`) count the rows of the
         probed buckets BEFORE the filter.  Tiled schedule, two-step route (`last_query_path == "two_step"`)."""
         filter = self._checked_filter(filter)
+        k1 = self._refine_k1(k, refine_k)
+        if k1:
+            with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
+                return self._keep(self._query_refined(query_vectors, k, k1, hash_times, seed, probes, candidate_budget, filter))
         if filter is not None:
             with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
                 keys, nkeys = self._filtered_keys(query_vectors, hash_times, seed, probes, candidate_budget)
-                _, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter)
+                _, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter, refine_k=0)
                 return self._keep(self._filtered_lists(idx, ncand, keys64))
         if candidate_budget is not None:
             budget = self._candidate_budget(candidate_budget, probes)
@@ -1866,7 +1951,7 @@ class Indexer:
         else:
             keys, nkeys = self.hash_device(q, hash_times=hash_times, seed=seed)
         if keys.shape[1] > _capi.MAX_PROBES:
-            _, idx, ncand, _ = self.scan_tensors(q, keys, nkeys, k=k)
+            _, idx, ncand, _ = self.scan_tensors(q, keys, nkeys, k=k, refine_k=0)
             idx_h, nc_h = idx.cpu().numpy(), ncand.cpu().numpy()
             keys_h, nkeys_h = (keys.cpu().numpy(), nkeys.cpu().numpy()) if self.compat else (None, None)
         elif self._n_chunks() > 1 and q.shape[0] >= self._n_chunks() * self._CHUNK_MIN_ROWS:
@@ -1904,11 +1989,12 @@ class Indexer:
             q = q.float().contiguous()
         return q
 
-    def query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], k=10, filter=None):
+    def query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], k=10, filter=None, refine_k=None):
         """Scan stage on caller-supplied key lists (each in the iteration order the caller saw):
         parity on identical candidate sets, independent of hashing.  `filter`: as in `query` (allowed ids only, list lengths
         from the sort keys, no F7 rule, candidate counts before the filter)."""
         filter = self._checked_filter(filter)
+        self._refine_k1(k, refine_k)        # refused before anything is copied to the device
         # a query's keys are a set (nlsh/utils.pyx:27-31): a repeated key probes its bucket once; first-occurrence order kept
         key_lists = [list(dict.fromkeys(int(key) for key in ks)) for ks in key_lists]
         Q = len(key_lists)
@@ -1923,9 +2009,9 @@ class Indexer:
         keys = torch.as_tensor(tab).to(dev)
         nkeys = torch.as_tensor(cnt).to(dev)
         if filter is not None:
-            dist, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter)
+            dist, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter, refine_k=refine_k)
             return self._filtered_lists(idx, ncand, keys64) + (dist, idx)
-        dist, idx, ncand, _ = self.scan_tensors(query_vectors, keys, nkeys, k=k)
+        dist, idx, ncand, _ = self.scan_tensors(query_vectors, keys, nkeys, k=k, refine_k=refine_k)
         res, nc = self._to_lists(key_lists, idx.cpu().numpy(), ncand.cpu().numpy(), k)
         return res, nc, dist, idx
 

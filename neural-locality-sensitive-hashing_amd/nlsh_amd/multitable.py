@@ -27,6 +27,7 @@ import torch
 from . import _capi
 from .data import metric_of
 from .indexer import Indexer, RowFilter, _STORAGES, _stream
+from .refine import RefineStore, checked_refine, stage_one_k
 
 
 class MultiRowFilter:
@@ -55,9 +56,19 @@ class MultiTableIndexer:
     name the rows as in `Indexer` (a rebuilt index keeps its ids through them).  Metric 'l2' or 'cosine' only.
     `.tables` is the list of tables.  Results, candidate counts and limits: `query_tensors`."""
 
+    refine, refine_factor, refine_store = None, 4, None     # no second stage unless the constructor is given refine=
+
     def __init__(self, hashings, candidate_vectors_gpu, distance_func, metric: Optional[str] = None, storage: Optional[str] = None,
                  l2_form: str = "exact", row_align: int = 4, window_rows: Optional[int] = None, corpus_keys=None,
-                 row_ids: Optional[torch.Tensor] = None, id_base: int = 0, quantiser=None):
+                 row_ids: Optional[torch.Tensor] = None, id_base: int = 0, quantiser=None, refine: Optional[str] = None,
+                 refine_factor: int = 4):
+        # refine: None | "device" | "host" = ONE store of the caller's float32 rows behind the de-duplicating merge (DESIGN.md 4.15):
+        # every table runs at k1, the merge keeps k1 distinct candidates and one re-rank cuts to k.  The tables themselves hold no store.
+        self.refine, self.refine_factor = checked_refine(refine, refine_factor)
+        self.refine_store = None
+        if self.refine is not None and row_ids is not None:
+            raise ValueError("refine= needs the default row ids (id_base + row): the refine store addresses a row by id - id_base, "
+                             "row_ids= names rows freely")
         if quantiser is not None and storage != "sq8":
             raise ValueError(f"quantiser= belongs to storage='sq8', not storage={storage!r}")
         hashings = list(hashings)
@@ -88,6 +99,11 @@ class MultiTableIndexer:
                                        l2_form=l2_form, row_align=row_align, window_rows=window_rows, row_ids=row_ids, id_base=id_base,
                                        corpus_keys=None if corpus_keys is None else corpus_keys[t], **kw))
         self.storage = self.tables[0].storage
+        if self.refine is not None:
+            originals = candidate_vectors_gpu
+            if self.storage == "sq8" and originals.dtype == torch.uint8:
+                originals = self.tables[0]._dequantised(originals)
+            self.refine_store = RefineStore(originals, self.metric, id_base=id_base, where=self.refine, row_align=row_align)
         self.generation = 0         # +1 per effective add / remove / update: a MultiRowFilter of an older one is stale
 
     # ------------------------------------------------------------------ shape
@@ -128,15 +144,26 @@ class MultiTableIndexer:
         return int(k)
 
     def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, probes=None, candidate_budget=None, filter=None,
-                      want_keys=False):
+                      want_keys=False, refine_k=None):
         """Device-resident query -> (dist [Q, k] float32, idx [Q, k] int32, ncand [Q] int32[, keys64 [Q, k] int64]).
         Every table answers `Indexer.query_tensors(..., want_keys=True)` with these arguments, one after the other on the current
         stream -- `hash_times`, `probes`, `candidate_budget` and `seed` are therefore PER TABLE -- and one `nlsh_merge_topk_unique` call
         merges the T lists: the k best DISTINCT (distance bits, id) keys, -1 / +inf / ~0 behind a query with fewer than k distinct
         candidates.  `ncand` is the sum of the tables' counts: scored (query, row) pairs, a row found by two tables counted twice.
-        filter: a `MultiRowFilter` of this index (`row_filter()`); table t is handed its own bitset.  k <= 256."""
+        filter: a `MultiRowFilter` of this index (`row_filter()`); table t is handed its own bitset.  k <= 256.
+        refine_k (an index built with `refine=` only; None = min(256, max(k, refine_factor * k)), 0 = off for this call): every table runs
+        at k1, the merge keeps the k1 best distinct candidates and ONE `nlsh_rerank_topk` launch returns the k best of them by their exact
+        float32 distance to the original rows; `ncand` stays the merge's sum, keys64 are the re-rank's."""
         k = self._checked_k(k)
         filters = self._checked_filter(filter)
+        if self.refine_store is None and refine_k:
+            raise ValueError("refine_k= needs an index built with refine='device' or 'host'")
+        k1 = stage_one_k(k, self.refine_factor, refine_k) if self.refine_store is not None else 0
+        if k1:
+            _, idx1, nc = self.query_tensors(query_vectors, k=k1, hash_times=hash_times, seed=seed, probes=probes,
+                                             candidate_budget=candidate_budget, filter=filter, refine_k=0)
+            dist, idx, _, keys64 = self.refine_store.rerank(self.tables[0]._as_queries(query_vectors), idx1, k, want_keys=True)
+            return (dist, idx, nc, keys64) if want_keys else (dist, idx, nc)
         q = self.tables[0]._as_queries(query_vectors)     # made contiguous float32 once, not once per table
         keys, counts = [], []
         for table, f in zip(self.tables, filters):
@@ -183,6 +210,9 @@ class MultiTableIndexer:
         """`Indexer.update` on every table: `remove` and `add` in one pass per table -> (ids of the added rows, rows removed).  After
         the call every table holds the same id set.  A `MultiRowFilter` built before an effective call is stale."""
         first = self.tables[0]
+        if self.refine_store is not None and add_ids is not None:
+            raise ValueError("add(ids=...) on an index with refine=: the refine store addresses a row by id - id_base, so added rows take "
+                             "the default ids (nothing was changed)")
         if add is not None:
             for t, table in enumerate(self.tables):     # what a LATER table would refuse is refused before the first one changes
                 needs_train = getattr(table._hashing, "_needs_train_forward", None)
@@ -207,6 +237,12 @@ class MultiTableIndexer:
             result = got if result is None else result
         if any(table.generation != g for table, g in zip(self.tables, before)):
             self.generation += 1
+        if self.refine_store is not None and result is not None and int(result[0].shape[0]):
+            originals = add
+            if self.storage == "sq8" and add.dtype == torch.uint8:
+                originals = first._dequantised(add)
+            assert int(result[0][0].item()) == self.refine_store.id_base + self.refine_store.n_rows
+            self.refine_store.append(originals)      # once: the tables share the store
         return result
 
     # ------------------------------------------------------------------ filters

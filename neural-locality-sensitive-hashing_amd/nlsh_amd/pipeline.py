@@ -57,6 +57,9 @@ class QueryPipeline:
         (`nlsh_step_create_graph`): batches overlap because the slots' streams do, and a submit costs the host one graph launch + two
         node updates instead of the staged slots' five launches + eight to ten event calls.  False = the three / four stage streams of
         r03-r05.  None = graph slots whenever the schedule is a bucket-major one (`QueryPipeline.default_graph`)."""
+        if getattr(indexer, "refine", None) is not None:
+            raise NotImplementedError("pipelined batches are not built for an index with refine=: a slot's launches end at the scan's merge "
+                                      "and have no re-rank stage (DESIGN.md 7)")
         if getattr(indexer, "storage", "float32") != "float32":
             raise NotImplementedError(f"pipelined batches (staged and graph slots) take float32 indexes only, not storage={indexer.storage!r}: "
                                       "the step descriptor has no storage field")
