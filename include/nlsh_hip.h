@@ -111,6 +111,22 @@ int nlsh_encode_hash(const float *x, int64_t n, int64_t x_stride, int n_layers, 
                      uint64_t seed, int64_t row0, float *z_out, float *probs_out, uint32_t *code_out,
                      int32_t *keys_out, int32_t *nkeys_out, nlsh_stream_t stream);
 
+/* The kernel forms of nlsh_encode_hash (same arithmetic, different geometry): rows per workgroup 16 | 32 | 32 with three column tiles
+ * per wave | 128 | 64 on two LDS images | 32, then 16 for the rows behind the last full round of workgroups. */
+enum {
+    NLSH_ENC_FORM_H16 = 0, NLSH_ENC_FORM_SINGLE = 1, NLSH_ENC_FORM_SINGLE_WIDE = 2, NLSH_ENC_FORM_BUILD128 = 3, NLSH_ENC_FORM_PINGPONG = 4,
+    NLSH_ENC_FORM_HET = 5
+};
+
+/* Read-only: the form an nlsh_encode_hash call of n rows, this layer stack and n_probes would take, from the planning code the launch
+ * itself runs; nothing is launched and no device is needed.  Outputs ([host], each nullable): the form id, the rows of a workgroup
+ * (NLSH_ENC_FORM_HET: 32, its larger workgroups), the dynamic LDS bytes of a workgroup (rows x row stride x 4, twice that for
+ * NLSH_ENC_FORM_PINGPONG) and the compute-unit count the NLSH_ENC_FORM_HET rule used (the current device's; 256 when none is visible).
+ * Refuses what nlsh_encode_hash refuses for the shape: the limits above (NLSH_E_INVALID / NLSH_E_UNSUPPORTED) and a row image
+ * larger than the LDS of a compute unit (NLSH_E_UNSUPPORTED). */
+int nlsh_encode_form(int64_t n, int n_layers, const int *dims, int n_probes, int *form_out, int *rows_per_workgroup_out,
+                     size_t *lds_bytes_out, int *cus_out);
+
 /* The streamed form: the same function for encoders with hidden layers up to NLSH_MAX_STREAM_WIDTH wide (narrow ones too).
  * The LDS-resident form above keeps a row's whole activation on chip, which bounds a hidden layer at NLSH_MAX_WIDTH; here the
  * activations of a block of rows live in `workspace` between layers: one fp32-MFMA GEMM launch per Linear layer (one k-ascending

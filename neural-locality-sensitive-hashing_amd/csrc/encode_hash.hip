@@ -5,8 +5,10 @@
 // .cpu().numpy() -> nlsh/utils.pyx:6-32 (binarr_to_int, set()).  Nothing leaves the device.
 //
 // gfx950 mapping
-//   * three forms, same arithmetic: index builds 128 rows per workgroup, query batches 32, batches of <= 4096 rows 16 (H16, all
-//     layers as 16x16x4 tiles); described here for the 32-row-tile forms:
+//   * six forms, same arithmetic, chosen by encode_plan_fill (DESIGN.md 4.1 has the table; nlsh_encode_form reads the choice back):
+//     batches of <= 4096 rows 16 per workgroup (H16, all layers as 16x16x4 tiles), query batches 32 on one image (SINGLE; HET with a
+//     16-row tail in the same grid; SINGLE_WIDE with three column tiles per wave for hidden layers wider than 256), index builds 128
+//     (BUILD128) or, with hidden layers wider than 256, 64 on two images (PINGPONG); described here for the 32-row-tile forms:
 //   * one workgroup (NW = 8 wavefronts, 512 threads) owns M = 32*RT rows; their activations never
 //     leave LDS (two ping-pong [M][S] fp32 images, 133 KB at width 256, so ONE workgroup per CU: the
 //     two wavefronts per SIMD are what overlaps one wave's LDS/L2 waits, write-back and epilogue VALU
@@ -963,6 +965,27 @@ extern "C" int nlsh_encode_hash(const float *x, int64_t n, int64_t x_stride, int
                               keys_out, nkeys_out);
     if (rc != NLSH_OK) return rc;
     return encode_plan_launch(p, x, x_stride, seed, (hipStream_t)stream);
+}
+
+static_assert(NLSH_ENC_FORM_H16 == ENC_FORM_H16 && NLSH_ENC_FORM_SINGLE == ENC_FORM_SINGLE && NLSH_ENC_FORM_SINGLE_WIDE == ENC_FORM_SINGLE_WIDE &&
+              NLSH_ENC_FORM_BUILD128 == ENC_FORM_BUILD128 && NLSH_ENC_FORM_PINGPONG == ENC_FORM_PINGPONG && NLSH_ENC_FORM_HET == ENC_FORM_HET,
+              "the header names the form ids of encode_common.h");
+
+// The plan nlsh_encode_hash would launch for this shape, read back: encode_plan_fill itself (its pointer arguments are only checked
+// for null there, never read), nothing is launched.
+extern "C" int nlsh_encode_form(int64_t n, int n_layers, const int *dims, int n_probes, int *form_out, int *rows_per_workgroup_out,
+                                size_t *lds_bytes_out, int *cus_out) {
+    static const float no_weights = 0.0f;
+    int32_t no_keys = 0;
+    EncPlan p;
+    int rc = encode_plan_fill(p, n, n_layers, dims, &no_weights, NLSH_ACT_SIGMOID, NLSH_KEY_FULL, n_probes, n, 0, nullptr, nullptr, nullptr,
+                              &no_keys, &no_keys);
+    if (rc != NLSH_OK) return rc;
+    if (form_out) *form_out = p.form;
+    if (rows_per_workgroup_out) *rows_per_workgroup_out = p.form == ENC_FORM_HET ? 32 : form_rows(p.form);   // HET: the rows its image is sized for
+    if (lds_bytes_out) *lds_bytes_out = p.lds;
+    if (cus_out) *cus_out = device_cus();
+    return NLSH_OK;
 }
 
 // ================================================================================================================================

@@ -26,12 +26,15 @@ MAX_ENCODE_PROBES = 128  # nlsh_encode_hash generates up to this many keys per r
 EXACT_L2, EXACT_COSINE = 0, 1   # metrics of nlsh_exact_topk (precompute.py's forms: squared L2, 1 - cos; not the scan's METRIC_*)
 PROBES = ("sampled", "ranked")  # multi-probe modes of the hashing: Philox Bernoulli draws (the reference's form, the default) | nlsh_probe_ranked
 PROBE_RANKED_ROWS_PER_WORKGROUP = 4  # nlsh_probe_ranked: one wavefront per row, this many rows per workgroup (tests size their batches by it)
+# NLSH_ENC_FORM_*: the kernel form nlsh_encode_hash takes for a shape (nlsh_encode_form reads the library's own choice back)
+ENC_FORM_H16, ENC_FORM_SINGLE, ENC_FORM_SINGLE_WIDE, ENC_FORM_BUILD128, ENC_FORM_PINGPONG, ENC_FORM_HET = 0, 1, 2, 3, 4, 5
+ENC_FORM_NAMES = ("H16", "SINGLE", "SINGLE_WIDE", "BUILD128", "PINGPONG", "HET")
 MAX_STREAM_WIDTH = 4096  # widest hidden layer of the streamed encoder form (nlsh_encode_hash_stream); MAX_WIDTH: the LDS-resident forms
 
 # every symbol include/nlsh_hip.h declares (tests/test_host_cpu.py::test_capi_library_exports_every_declared_symbol checks the header against this)
 SYMBOLS = (
     "nlsh_abi_version", "nlsh_last_error",
-    "nlsh_encoder_packed_floats", "nlsh_encoder_pack", "nlsh_encode_hash", "nlsh_pack_codes",
+    "nlsh_encoder_packed_floats", "nlsh_encoder_pack", "nlsh_encode_hash", "nlsh_encode_form", "nlsh_pack_codes",
     "nlsh_encoder_stream_packed_floats", "nlsh_encoder_stream_pack", "nlsh_encode_stream_workspace", "nlsh_encode_hash_stream",
     "nlsh_build_csr_workspace", "nlsh_build_csr", "nlsh_bucket_order_workspace", "nlsh_bucket_order", "nlsh_build_cells_workspace", "nlsh_build_cells", "nlsh_gather_rows",
     "nlsh_scan_workspace", "nlsh_scan_workspace_layout", "nlsh_scan_topk", "nlsh_scan_topk_phase", "nlsh_scan_topk_cells_phase",
@@ -106,6 +109,8 @@ def lib():
     L.nlsh_encoder_pack.argtypes = [i32, vp, vp, vp, vp, vp]
     L.nlsh_encode_hash.restype = i32
     L.nlsh_encode_hash.argtypes = [vp, i64, i64, i32, vp, vp, i32, i32, i32, i64, u64, i64, vp, vp, vp, vp, vp, vp]
+    L.nlsh_encode_form.restype = i32           # n, n_layers, dims, n_probes | form, rows per workgroup, LDS bytes, CUs (host pointers)
+    L.nlsh_encode_form.argtypes = [i64, i32, vp, i32, vp, vp, vp, vp]
     L.nlsh_pack_codes.restype = i32
     L.nlsh_pack_codes.argtypes = [vp, i64, i32, i32, i32, vp, vp]
     L.nlsh_encoder_stream_packed_floats.restype = i64
@@ -222,6 +227,15 @@ def lib():
 def check(rc):
     if rc != OK:
         raise NlshHipError(rc, lib().nlsh_last_error().decode("utf-8", "replace"))
+
+
+def encode_form(n, dims, n_probes=1):
+    """(form id, rows per workgroup, LDS bytes per workgroup, CU count of the HET rule) of the `nlsh_encode_hash` call of `n` rows
+    through the layer stack `dims` = [d, hidden..., H]: the library's own plan, nothing is launched.  A refused shape raises."""
+    form, rows, cus, lds = i32(-1), i32(0), i32(0), sz(0)
+    check(lib().nlsh_encode_form(int(n), len(dims) - 1, int_array(dims), int(n_probes), ctypes.byref(form), ctypes.byref(rows),
+                                 ctypes.byref(lds), ctypes.byref(cus)))
+    return form.value, rows.value, lds.value, cus.value
 
 
 def probe_mode(probes, default="sampled"):
