@@ -582,6 +582,53 @@ int nlsh_scan_topk_cells_phase_sq8(const uint8_t *corpus_sorted, const float *lo
                                    const uint32_t *row_filter);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-query tag filters: row tags matched against query masks inside the tiled scan.
+ *
+ * Every SORTED row carries a 64-bit tag word: row_tags [dev, 8-byte aligned] uint64 [N], entry p = the tag of sorted row p (the caller
+ * keeps it in step with gid: tags_sorted = tags[perm]; a signed 64-bit container is reinterpreted, bit 63 is a bit like any other).
+ * Every query of the call carries a 64-bit mask: query_masks [dev, 8-byte aligned] uint64 [Q].  The call has ONE match mode, tag_match:
+ *   NLSH_TAG_ANY  the row passes iff (tag & mask) != 0
+ *   NLSH_TAG_ALL  the row passes iff (tag & mask) == mask
+ *   NLSH_TAG_EQ   the row passes iff tag == mask
+ * Definition: query q's result is what the same call gives on the index built from the rows that pass q's mask alone, with the same
+ * ids, bucket keys and key table -- ids, distance bits and the 64-bit sort keys, with -1 / +inf / ~0 behind a list shorter than k.
+ * out_ncand counts the rows of the probed buckets BEFORE the tags, as it does before a row filter.  A denied row is dropped in front of
+ * the top-k selection; it changes no distance bit of another row, whatever it holds (NaN, infinities).  NLSH_TAG_ALL with mask 0 passes
+ * every row (the untagged call's outputs in every word), NLSH_TAG_ANY with mask 0 passes none (all-padding lists).  With row_filter
+ * given as well a row must pass both.  The tags are the rows', not a generation's: nothing is built per call and nothing goes stale.
+ *
+ * nlsh_scan_topk_cells_phase_tagged: nlsh_scan_topk_cells_phase_filtered plus the trailing row_tags, query_masks, tag_match.
+ * nlsh_scan_topk_cells_phase_sq8_tagged: nlsh_scan_topk_cells_phase_sq8 plus the same three arguments.
+ * row_tags == NULL (then query_masks must be NULL too; tag_match is not looked at) is the base call, argument for argument.  Tiled
+ * schedule only, every storage, every metric, k <= NLSH_MAX_K_TILED.  Refused before anything is enqueued, the argument named in
+ * nlsh_last_error(): a schedule other than NLSH_SCAN_BUCKET_TILED (NLSH_E_UNSUPPORTED); one of the two pointers without the other, a
+ * pointer that is not 8-byte aligned, tag_match outside the three codes (NLSH_E_INVALID).  The calls cannot check the arrays' sizes.
+ * The step, graph-slot, one-call batch and radius entry points take no tags.  Beside what the filtered call reads, the scan reads
+ * 8 bytes per (task, row) -- next to the row id -- and 8 bytes per (task, query).
+ * ------------------------------------------------------------------------------------------- */
+#define NLSH_TAG_ANY 0
+#define NLSH_TAG_ALL 1
+#define NLSH_TAG_EQ 2
+int nlsh_scan_topk_cells_phase_tagged(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
+                                      const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                                      const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                                      const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
+                                      const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows,
+                                      float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand,
+                                      int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
+                                      void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                                      const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks, int tag_match);
+int nlsh_scan_topk_cells_phase_sq8_tagged(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d,
+                                          const int32_t *gid, const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order,
+                                          int32_t n_buckets, const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                                          const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
+                                          const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows,
+                                          float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand,
+                                          int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
+                                          void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                                          const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks, int tag_match);
+
+/* ---------------------------------------------------------------------------------------------
  * One pipelined query batch per call.  Replaces, for a caller that streams batches, the whole body of Indexer.query
  * (nlsh/indexer.py:56-96: hashing.hash on the batch :59 via Indexer.hash :40-54, then the per-query loop :62-95) by ONE
  * enqueue: nlsh_encode_hash + the PLAN, SCAN and MERGE phases of nlsh_scan_topk_cells_phase (five launches since r06: the bucket

@@ -102,6 +102,7 @@ struct ScanLaunch {
     dim3 grid, block;
     void *argv[2];   // the kernel's BArgs and, read by the filtered kernels alone, the filter pointer as their second parameter
     QuantArgs quant; // ... or, read by the affine kernels alone, the quantiser and the filter
+    TagArgs tag;     // ... or, read by the tagged kernels alone, tags, masks, mode, filter and quantiser
 };
 static int scan_launch_of(const BucketScanCall &c, int metric, const BArgs *a, ScanLaunch *l) {
     l->argv[0] = (void *)a;
@@ -110,10 +111,15 @@ static int scan_launch_of(const BucketScanCall &c, int metric, const BArgs *a, S
         l->quant = QuantArgs{(const float4 *)c.quant_lo, (const float4 *)c.quant_step, c.row_filter};
         l->argv[1] = (void *)&l->quant;
     }
+    if (c.row_tags) {
+        l->tag = TagArgs{c.row_tags, c.query_masks, c.tag_match, c.row_filter, c.affine ? (const float4 *)c.quant_lo : nullptr,
+                         c.affine ? (const float4 *)c.quant_step : nullptr};
+        l->argv[1] = (void *)&l->tag;
+    }
     const bool wide = c.k > NLSH_MAX_K;   // wide k: the same task body, its epilogue selecting up to 64 * TPS keys per list
     if (!c.tiled()) {
-        NLSH_REQUIRE(!c.row_filter && c.storage == NLSH_STORE_F32 && !c.affine, NLSH_E_UNSUPPORTED,
-                     "scan_topk(bucket-major): row_filter and a float16 / uint8 corpus are read by the tiled schedule only");
+        NLSH_REQUIRE(!c.row_filter && c.storage == NLSH_STORE_F32 && !c.affine && !c.row_tags, NLSH_E_UNSUPPORTED,
+                     "scan_topk(bucket-major): row_filter, row_tags and a float16 / uint8 corpus are read by the tiled schedule only");
         l->grid = dim3((unsigned)((c.max_tasks + 3) / 4));  // one wavefront per task
         l->block = dim3(256);
     } else {
@@ -122,7 +128,8 @@ static int scan_launch_of(const BucketScanCall &c, int metric, const BArgs *a, S
     }
     // (the float32 tiled kernels are named before the wave-level ones: a code object keeps its kernels in the order the host code first
     // names them, and scan_bucket.hip's is compared byte for byte across changes of this file)
-    if (c.tiled() && c.affine) l->fn = affine_scan_kernel_of(metric, wide);                                      // scan_bucket_affine.hip
+    if (c.tiled() && c.row_tags) l->fn = tagged_scan_kernel_of(c.affine ? NLSH_STORE_SQ8 : c.storage, metric, wide);   // scan_bucket_tagged.hip
+    else if (c.tiled() && c.affine) l->fn = affine_scan_kernel_of(metric, wide);                                      // scan_bucket_affine.hip
     else if (c.tiled() && c.row_filter) l->fn = filtered_scan_kernel_of(c.storage, metric, wide);                    // scan_bucket_filtered.hip
     else if (c.tiled() && c.storage != NLSH_STORE_F32) l->fn = typed_scan_kernel_of(c.storage, metric, wide);   // scan_bucket_typed.hip
     else if (c.tiled() && wide) l->fn = NLSH_TILED_KERNEL(bscanw_kernel, metric);
@@ -181,6 +188,7 @@ int bucket_scan_node(const BucketScanCall &c, ScanNode *out) {
     // a node carries ONE kernel parameter (ScanNode::argv): the filtered kernels take two
     NLSH_REQUIRE(c.row_filter == nullptr, NLSH_E_UNSUPPORTED, "scan node: a call with a row_filter cannot be replayed from a graph node");
     NLSH_REQUIRE(!c.affine, NLSH_E_UNSUPPORTED, "scan node: a call over an sq8 corpus cannot be replayed from a graph node");
+    NLSH_REQUIRE(c.row_tags == nullptr, NLSH_E_UNSUPPORTED, "scan node: a call with row_tags cannot be replayed from a graph node");
     BucketScanPrep p;
     int rc = bucket_scan_args(c, &p);
     if (rc != NLSH_OK) return rc;

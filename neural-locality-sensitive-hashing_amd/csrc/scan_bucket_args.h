@@ -96,6 +96,17 @@ struct QuantArgs {
     const uint32_t *row_filter;    // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: every row allowed
 };
 
+// Second parameter of the tagged kernels (bscang_kernel, scan_bucket_tagged.hip; nlsh_scan_topk_cells_phase_tagged / _sq8_tagged), as
+// RangeArgs is the radius kernels': BArgs keeps its layout.  What TAGS of tiled_task_body reads beside BArgs.
+struct TagArgs {
+    const uint64_t *tags;          // [N] tag word of every SORTED row, read with the row position the lane already has
+    const uint64_t *qmask;         // [Q] mask of every query of the call
+    int match;                     // NLSH_TAG_ANY | NLSH_TAG_ALL | NLSH_TAG_EQ (wave-uniform)
+    const uint32_t *row_filter;    // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: every row allowed
+    const float4 *lo4;             // NLSH_STORE_SQ8 instantiations: the quantiser, as in QuantArgs; nullptr otherwise
+    const float4 *step4;
+};
+
 // A call's prepared launch (scan_bucket.hip): the workspace held against the schedule's layout (NLSH_E_WORKSPACE), then what the scan kernels
 // take (bucket_scan_run; the radius calls for their own kernel), what the lookup takes (step.hip, probe_ranked.hip: the launch that does it),
 // the metric the schedule really computes and whether the tiled schedule needs its padded / pre-normalised query copy

@@ -3,7 +3,7 @@
 // the hand-scheduled k-blocks, the task bodies built from them (l2_task*), one task start to finish (tiled_task_body) and the kernels
 // bscan3_kernel (k <= 64) and bscanw_kernel (k up to NLSH_MAX_K_TILED) over a float32 corpus, bscant_kernel over a float16 / uint8 one,
 // bscanf_kernel behind a row filter (scan_bucket_filtered.hip instantiates it), bscanr_kernel for radius queries (scan_bucket_range.hip),
-// bscana_kernel over an sq8 corpus (scan_bucket_affine.hip).
+// bscana_kernel over an sq8 corpus (scan_bucket_affine.hip), bscang_kernel behind per-query tag filters (scan_bucket_tagged.hip).
 #pragma once
 
 // Diagnostic build only (make EXTRA=-DNLSH_SCAN_TRACE, tools/scan_trace.py): wave 0 of every bscan3 workgroup
@@ -497,17 +497,27 @@ __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const typena
 // list's first slot of the query's segment and every hit lane stores its key at row_offsets[q] + slot (mbcnt ranks, as in
 // select_k_smallest's compaction).  tauq and partial are not touched.  range->row_filter (nullable) is the filter, a run-time operand
 // here: a null pointer gives every lane an all-ones word.  Off (the default), neither the parameter nor the code exists.
-template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = NLSH_STORE_F32, bool FILT = false, bool RANGE = false>
+// TAGS (compile time; nlsh_scan_topk_cells_phase_tagged / _sq8_tagged, bscang_kernel): per-query tag filters.  Every sorted row carries a
+// 64-bit tag word (tag->tags, read with the row position the lane already has: 8 bytes per lane and tile, coalesced), every query a 64-bit
+// mask (tag->qmask[q], wave-uniform: a scalar load per query of the wave, of the slot's own query -- qid[jq] is the id of slot
+// NLSH_SLOT(wave, jq), clamped as everywhere) and the call one match mode.  Tags, masks and the optional bitset bit (tag->row_filter) are
+// folded into ONE register of 16 pass bits (bit tl * QW + jq) in front of the task bodies, so that neither the tag words nor the filter
+// words are live during the arithmetic; bit (tl, jq) enters `mine` in the epilogue.  A denied row changes nothing in staging, in the
+// k-blocks or in a distance.  With STORE == NLSH_STORE_SQ8 the quantiser comes from TagArgs too.  Off (the default), none of it exists.
+template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = NLSH_STORE_F32, bool FILT = false, bool RANGE = false,
+          bool TAGS = false>
 __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, long long t, const int4 desc, const int2 qr_all, int tid, int lane,
                                                 int wave, [[maybe_unused]] unsigned long long ts_entry,
                                                 [[maybe_unused]] const uint32_t *row_filter = nullptr,
                                                 [[maybe_unused]] const RangeArgs *range = nullptr,
-                                                [[maybe_unused]] const QuantArgs *quant = nullptr) {
+                                                [[maybe_unused]] const QuantArgs *quant = nullptr,
+                                                [[maybe_unused]] const TagArgs *tag = nullptr) {
     static_assert(!(RANGE && (FILT || WIDEK)), "the range epilogue reads its filter from RangeArgs and selects nothing");
+    static_assert(!(TAGS && (FILT || RANGE)), "the tagged kernels read their filter from TagArgs and have no range epilogue");
     // AFFINE (STORE == NLSH_STORE_SQ8; nlsh_scan_topk_cells_phase_sq8, bscana_kernel): the staging code decodes with quant->lo4 / step4,
     // and quant->row_filter (nullable) is the filter, a run-time operand as in the range kernels.  Off, none of it exists in the code.
     constexpr bool AFFINE = STORE == NLSH_STORE_SQ8;
-    static_assert(!(AFFINE && (FILT || RANGE)), "the affine kernels read their filter from QuantArgs and have no range epilogue");
+    static_assert(!(AFFINE && (FILT || RANGE)), "the affine kernels read their filter from QuantArgs (the tagged form: TagArgs) and have no range epilogue");
     static_assert(QW == 4 && TPS == 4 && NW == 4, "the hand-scheduled task bodies (l2_task_nt) are written for 4 waves x 4 queries x 4 row tiles");
 #ifdef NLSH_SCAN_TRACE_CLOCK
     const unsigned long long ts0 = SCAN_NOW();
@@ -562,12 +572,37 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
         const int prow = row0 + (valid[tl] ? tl * 64 + lane : 0);
         mygid[tl] = valid[tl] ? a.gid[prow] : -1;
         myinv[tl] = (METRIC == NLSH_METRIC_COSINE && valid[tl]) ? a.inv_norm[prow] : 0.0f;
-        if (FILT) myfw[tl] = row_filter[prow >> 5];
+        if (TAGS) myfw[tl] = tag->row_filter ? tag->row_filter[prow >> 5] : 0xFFFFFFFFu;
+        else if (FILT) myfw[tl] = row_filter[prow >> 5];
         else if (RANGE) myfw[tl] = range->row_filter ? range->row_filter[prow >> 5] : 0xFFFFFFFFu;
         else if (AFFINE) myfw[tl] = quant->row_filter ? quant->row_filter[prow >> 5] : 0xFFFFFFFFu;
     }
     [[maybe_unused]] const float4 *qlo = nullptr, *qstep = nullptr;
-    if constexpr (AFFINE) { qlo = quant->lo4; qstep = quant->step4; }
+    if constexpr (AFFINE && TAGS) { qlo = tag->lo4; qstep = tag->step4; }
+    else if constexpr (AFFINE) { qlo = quant->lo4; qstep = quant->step4; }
+    // TAGS: the 16 pass bits of the lane's (tile, query) pairs.  The masks of the wave's LIVE slots only (jq < nqw: what the epilogue
+    // reads the bounds of); lanes past the task's last row hold the words of row0 and are never `valid`.  The empty asm pins the fold in
+    // front of the task bodies: behind them, the eight tag registers and the filter words would live through the arithmetic.
+    [[maybe_unused]] uint32_t pass = 0u;
+    if constexpr (TAGS) {
+        uint64_t mytag[TPS], qm[QW];
+#pragma unroll
+        for (int tl = 0; tl < TPS; ++tl) mytag[tl] = tag->tags[row0 + (valid[tl] ? tl * 64 + lane : 0)];
+#pragma unroll
+        for (int jq = 0; jq < QW; ++jq) qm[jq] = jq < nqw ? tag->qmask[qid[jq]] : 0ull;
+        const int match = tag->match;
+#pragma unroll
+        for (int tl = 0; tl < TPS; ++tl) {
+            const bool fbit = (myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u;   // valid lanes: the bit of prow
+#pragma unroll
+            for (int jq = 0; jq < QW; ++jq) {
+                const uint64_t both = mytag[tl] & qm[jq];
+                const bool ok = match == NLSH_TAG_ANY ? both != 0ull : (match == NLSH_TAG_ALL ? both == qm[jq] : mytag[tl] == qm[jq]);
+                pass |= (ok && fbit && jq < nqw) ? 1u << (tl * QW + jq) : 0u;
+            }
+        }
+        asm volatile("" : "+v"(pass));
+    }
     [[maybe_unused]] unsigned long long trl[3] = {0, 0, 0};
     [[maybe_unused]] const unsigned long long ts_in = SCAN_NOW();
     // a task whose rows x chunks fit one stage takes the single-stage body (l2_task_single): selected as "0 tiles" of the same switch
@@ -629,7 +664,8 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
 #pragma unroll
             for (int tl = 0; tl < TPS; ++tl) {
                 bool mine = valid[tl] && (unsigned)(tl * 64 + lane) - r_lo < r_n;
-                if (FILT || RANGE || AFFINE) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
+                if (TAGS) mine = mine && ((pass >> (tl * QW + jq)) & 1u);   // tag, mask and filter bit of (tile, query), folded at the top
+                else if (FILT || RANGE || AFFINE) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
                 uint64_t kk;
                 [[maybe_unused]] float dist_r;   // RANGE: the distance the key is built from, held against the radius
                 if (lean) {
@@ -886,6 +922,33 @@ __global__ __launch_bounds__(64 * NW, 1) void bscana_kernel(BArgs a, QuantArgs q
     const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
     if (t >= ntasks) return;
     tiled_task_body<METRIC, QW, NW, TPS, WIDEK, NLSH_STORE_SQ8>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, nullptr, nullptr, &q);
+}
+
+// The tiled scan behind per-query tag filters (TAGS of tiled_task_body; nlsh_scan_topk_cells_phase_tagged / _sq8_tagged), every storage --
+// NLSH_STORE_SQ8 among them: the quantiser rides in TagArgs --, k <= 64 (WIDEK false) and k in 65..NLSH_MAX_K_TILED (true).  One kernel per
+// (metric, storage, k class) serves the three match modes and both filter states: g.match and g.row_filter are wave-uniform run-time
+// operands.  TagArgs is a SECOND kernel parameter: BArgs and every kernel above keep their layout and their code (profiles/row_tags.txt).
+// Instantiated in scan_bucket_tagged.hip, a translation unit of its own.  The task pick is bscan3_kernel's, line for line (see the
+// comments there), written out again for the reason given at bscanw_kernel.
+template <int METRIC, int QW, int NW, int TPS, int STORE, bool WIDEK>
+__global__ __launch_bounds__(64 * NW, 1) void bscang_kernel(BArgs a, TagArgs g) {
+    constexpr int RS = NLSH_TILED_KB + 1;
+    __shared__ float4 tile[64 * TPS * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
+    long long ntasks = a.status[0];
+    if (ntasks > a.max_tasks) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
+        ntasks = a.max_tasks;
+    }
+    constexpr int XC = 16;
+    const long long j = blockIdx.x >> 3;
+    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
+    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
+    const int4 desc = a.task[tc];
+    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
+    if (t >= ntasks) return;
+    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE, false, false, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, nullptr, nullptr, nullptr, &g);
 }
 
 }  // namespace nlsh

@@ -441,6 +441,11 @@ struct BucketScanCall {
                                   // SCAN phase launches an affine kernel, which takes the quantiser (and the filter) as a second parameter
     const float *quant_lo;        // affine: [row_stride] per-dimension offsets, padded to the pitch with 0 (device, 16-byte aligned)
     const float *quant_step;      // affine: [row_stride] per-dimension steps, padded with 1
+    const uint64_t *row_tags;     // nlsh_scan_topk_cells_phase_tagged / _sq8_tagged: [N] tag word of every sorted row, or nullptr: no tags.  The
+                                  // tiled schedule's alone; the SCAN phase then launches a tagged kernel, whose second parameter (TagArgs) holds
+                                  // the tags, the masks, the mode, the filter and -- affine -- the quantiser
+    const uint64_t *query_masks;  // [Q] mask of every query; given iff row_tags is
+    int tag_match;                // NLSH_TAG_ANY | NLSH_TAG_ALL | NLSH_TAG_EQ; looked at only with row_tags
     bool tiled() const { return algo == NLSH_SCAN_BUCKET_TILED; }
 };
 // internal phase bit (not part of the C ABI's phase mask): the PLAN phase WITHOUT the bucket lookup, which the batch's encode_hash
@@ -475,5 +480,8 @@ const void *typed_scan_kernel_of(int storage, int metric, bool wide);
 const void *filtered_scan_kernel_of(int storage, int metric, bool wide);
 // the tiled scan kernel over an sq8 corpus (scan_bucket_affine.hip): its parameters are (BArgs, QuantArgs), the filter inside the second
 const void *affine_scan_kernel_of(int metric, bool wide);
+// the tiled scan kernel behind per-query tag filters (scan_bucket_tagged.hip): any storage, NLSH_STORE_SQ8 (scan_bucket_args.h) for an
+// affine call; its parameters are (BArgs, TagArgs), the filter and the quantiser inside the second
+const void *tagged_scan_kernel_of(int storage, int metric, bool wide);
 
 }  // namespace nlsh

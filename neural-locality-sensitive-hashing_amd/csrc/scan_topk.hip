@@ -381,11 +381,21 @@ int scan_call_check(const char *who, const BucketScanCall &c, unsigned needs) {
     const char *tiled_only = "the tiled schedule only (NLSH_SCAN_BUCKET_TILED)";
     NLSH_REQUIRE(topk || c.tiled(), NLSH_E_UNSUPPORTED, "%s: a radius query is scanned by %s, not by algo=%d", who, tiled_only, c.algo);
     NLSH_REQUIRE(!c.row_filter || c.tiled(), NLSH_E_UNSUPPORTED, "%s: row_filter is read by %s, not by algo=%d", who, tiled_only, c.algo);
+    NLSH_REQUIRE(!(c.row_tags || c.query_masks) || c.tiled(), NLSH_E_UNSUPPORTED, "%s: row_tags and query_masks are read by %s, not by algo=%d", who, tiled_only, c.algo);
     NLSH_REQUIRE(!c.affine || c.tiled(), NLSH_E_UNSUPPORTED, "%s: an sq8 corpus is read by %s, not by algo=%d", who, tiled_only, c.algo);
     NLSH_REQUIRE(c.storage == NLSH_STORE_F32 || c.tiled(), NLSH_E_UNSUPPORTED, "%s: a %s corpus (storage=%d) is read by %s, not by algo=%d", who,
                  c.storage == NLSH_STORE_F16 ? "float16" : "uint8", c.storage, tiled_only, c.algo);
     NLSH_REQUIRE(!c.affine || c.storage == NLSH_STORE_U8, NLSH_E_INVALID, "%s: an sq8 corpus is held in the uint8 layout, not storage=%d", who, c.storage);
     NLSH_REQUIRE(((uintptr_t)c.row_filter & 3) == 0, NLSH_E_INVALID, "%s: row_filter must be 4-byte aligned", who);
+    // per-query tag filters (the schedule is held above): both arrays or neither, read with 8-byte loads, by the top-k kernels of a direct call alone
+    NLSH_REQUIRE(c.row_tags || !c.query_masks, NLSH_E_INVALID, "%s: query_masks without row_tags", who);
+    NLSH_REQUIRE(!c.row_tags || c.query_masks, NLSH_E_INVALID, "%s: row_tags without query_masks", who);
+    NLSH_REQUIRE(((uintptr_t)c.row_tags & 7) == 0, NLSH_E_INVALID, "%s: row_tags must be 8-byte aligned", who);
+    NLSH_REQUIRE(((uintptr_t)c.query_masks & 7) == 0, NLSH_E_INVALID, "%s: query_masks must be 8-byte aligned", who);
+    NLSH_REQUIRE(!c.row_tags || (c.tag_match >= NLSH_TAG_ANY && c.tag_match <= NLSH_TAG_EQ), NLSH_E_INVALID,
+                 "%s: tag_match=%d is none of NLSH_TAG_ANY / ALL / EQ", who, c.tag_match);
+    NLSH_REQUIRE(!c.row_tags || (topk && !(needs & SCAN_ALLOWS_PLAN_REST) && !(c.phases & NLSH_PHASE_PLAN_REST)), NLSH_E_UNSUPPORTED,
+                 "%s: row_tags are read by the direct top-k calls only, not by a radius call, a step or a graph slot", who);
     // A compressed copy's pitch is held HERE for the top-k calls, ahead of the limits and of the empty batch, as the typed entry always
     // did; float32 rows and the radius calls have theirs held behind both, below: each entry keeps the code it had.
     const bool pitch_first = topk && c.storage != NLSH_STORE_F32;
@@ -520,6 +530,38 @@ extern "C" int nlsh_scan_topk_cells_phase_sq8(const uint8_t *corpus_sorted, cons
     c.phases = phases; c.storage = NLSH_STORE_U8; c.row_filter = row_filter;
     c.affine = true; c.quant_lo = lo; c.quant_step = step;
     return topk_call("scan_topk_sq8", c);
+}
+
+// The filtered call behind per-query tag filters: without row_tags it IS the filtered call, and says so in its refusals.
+extern "C" int nlsh_scan_topk_cells_phase_tagged(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
+                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
+                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
+                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
+                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                              const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks, int tag_match) {
+    NLSH_TOPK_CALL(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
+    c.phases = phases; c.storage = storage; c.row_filter = row_filter;
+    c.row_tags = row_tags; c.query_masks = query_masks; c.tag_match = tag_match;
+    return topk_call((row_tags || query_masks) ? "scan_topk_tagged" : (row_filter ? "scan_topk_filtered" : "scan_topk_typed"), c);
+}
+
+extern "C" int nlsh_scan_topk_cells_phase_sq8_tagged(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d,
+                              const int32_t *gid, const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
+                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
+                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
+                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
+                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                              const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks, int tag_match) {
+    NLSH_TOPK_CALL(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
+    c.phases = phases; c.storage = NLSH_STORE_U8; c.row_filter = row_filter;
+    c.affine = true; c.quant_lo = lo; c.quant_step = step;
+    c.row_tags = row_tags; c.query_masks = query_masks; c.tag_match = tag_match;
+    return topk_call((row_tags || query_masks) ? "scan_topk_sq8_tagged" : "scan_topk_sq8", c);
 }
 
 extern "C" int nlsh_merge_topk(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,

@@ -17,6 +17,7 @@ KEY_REF_INT16, KEY_FULL = 0, 1
 METRIC_L2_EPS, METRIC_COSINE, METRIC_L2_EPS_FOLDED = 0, 1, 2
 SCAN_QUERY_MAJOR, SCAN_BUCKET_MAJOR, SCAN_BUCKET_TILED = 0, 1, 2
 STORE_F32, STORE_F16, STORE_U8 = 0, 1, 2   # NLSH_STORE_*: element type of a bucket-sorted corpus copy (the *_typed entry points)
+TAG_ANY, TAG_ALL, TAG_EQ = 0, 1, 2         # NLSH_TAG_*: match mode of a tagged scan call (row tags against query masks)
 MAX_LAYERS, MAX_HASH_BITS, MAX_PROBES, MAX_K, MAX_DIM, MAX_WIDTH = 8, 32, 64, 64, 1024, 632
 MAX_K_TILED = 256  # k of the tiled schedule and of nlsh_merge_topk (NLSH_MAX_K_TILED); MAX_K is what every schedule takes
 MAX_TABLES = 16    # lists per query of nlsh_merge_topk_unique = hash tables of a MultiTableIndexer (NLSH_MAX_TABLES)
@@ -51,6 +52,7 @@ SYMBOLS = (
     "nlsh_range_workspace", "nlsh_range_sort_workspace", "nlsh_range_count", "nlsh_range_fill",
     "nlsh_sq8_train_workspace", "nlsh_sq8_train", "nlsh_gather_rows_sq8", "nlsh_csr_update_sq8", "nlsh_scan_topk_cells_phase_sq8",
     "nlsh_rerank_topk",
+    "nlsh_scan_topk_cells_phase_tagged", "nlsh_scan_topk_cells_phase_sq8_tagged",
 )
 
 
@@ -183,6 +185,10 @@ def lib():
     L.nlsh_scan_topk_cells_phase_sq8.restype = i32     # the filtered call with (lo, step) in place of the storage code
     L.nlsh_scan_topk_cells_phase_sq8.argtypes = (L.nlsh_scan_topk_cells_phase_filtered.argtypes[:1] + [vp, vp]
                                                  + L.nlsh_scan_topk_cells_phase_filtered.argtypes[2:])
+    for base in ("nlsh_scan_topk_cells_phase_filtered", "nlsh_scan_topk_cells_phase_sq8"):     # ... plus row_tags, query_masks, tag_match
+        tagged = getattr(L, base.replace("_filtered", "") + "_tagged")
+        tagged.restype = i32
+        tagged.argtypes = list(getattr(L, base).argtypes) + [vp, vp, i32]
     L.nlsh_row_filter_words.restype = sz
     L.nlsh_row_filter_words.argtypes = [i64]
     L.nlsh_row_filter_build.restype = i32      # gid, n_rows | ids, n_ids | dense, n_dense, id_base | invert | row_filter, n_allowed, stream

@@ -242,6 +242,9 @@ class ShardedIndexer:
         if kw.get("refine") is not None:
             raise NotImplementedError("ShardedIndexer is not built for refine=: the ranks exchange stage one's keys, and a refine store "
                                       "addresses rows by id - id_base, which a bucket shard's ids are not (DESIGN.md 7)")
+        if kw.get("tags") is not None:
+            raise NotImplementedError("ShardedIndexer takes no tags= / tag_mask: the row exchange moves rows, ids and keys, not row tags "
+                                      "(DESIGN.md 7)")
         if shard not in ("buckets", "rows"):
             raise ValueError("shard must be 'buckets' or 'rows'")
         if kw.get("storage") not in (None, "float32"):
@@ -284,15 +287,21 @@ class ShardedIndexer:
             return []
         return order[offs[i]:offs[i + 1]].tolist()
 
-    def query_tensors(self, query_vectors, k=10, hash_times=10, seed=0, check=True, events=None):
+    def query_tensors(self, query_vectors, k=10, hash_times=10, seed=0, check=True, events=None, tag_mask=None):
         """`seed` must be the same on every rank (default 0; pass a per-step value to vary probes)."""
+        self._refuse_tags(tag_mask)
         _, _, ncand, keys64 = self.local.query_tensors(query_vectors, k=k, hash_times=hash_times, seed=seed,
                                                        want_keys=True, check=check, events=events)
         if not dist.is_initialized() or dist.get_world_size(self.group) == 1:
             return merge_topk_device(torch.cat([keys64, ncand.long()[:, None]], dim=1)[None], k)
         return gather_and_merge(keys64, ncand, k, self.group)
 
-    def query(self, query_vectors, k=10, hash_times=10, seed=None, own_slice=False):
+    @staticmethod
+    def _refuse_tags(tag_mask):
+        if tag_mask is not None:
+            raise NotImplementedError("a sharded query takes no tag_mask: per-query tag filters are built for a single Indexer (DESIGN.md 7)")
+
+    def query(self, query_vectors, k=10, hash_times=10, seed=None, own_slice=False, tag_mask=None):
         """`Indexer.query` (nlsh/indexer.py:56-96) over the sharded corpus: the reference's `(List[List[int]],
         List[int])`, identical to the single-GPU answer.  hash -> local scan -> all-gather + merge -> one
         device->host copy.  The multi-probe seed comes from the hasher's call counter (identical on all ranks as long
@@ -303,6 +312,7 @@ class ShardedIndexer:
         (the merged device tensors are complete everywhere), but the host-side work of the reference's return type
         (device->host copy + 10^5 Python ints per 10^4 queries) is divided over the ranks like the scan is."""
         import numpy as np
+        self._refuse_tags(tag_mask)
         local = self.local
         if seed is None:
             seed = local._hashing.next_seed()

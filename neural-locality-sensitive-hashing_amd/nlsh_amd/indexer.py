@@ -210,6 +210,36 @@ class RowFilter:
         return f"RowFilter(n_allowed={self.n_allowed}, generation={self.generation})"
 
 
+TAG_MATCH = {"any": _capi.TAG_ANY, "all": _capi.TAG_ALL, "eq": _capi.TAG_EQ}   # tag_match= -> NLSH_TAG_* (include/nlsh_hip.h)
+
+
+class TagFilter:
+    """What a tagged call carries where an untagged one carries its `RowFilter` (internal; built by `Indexer._checked_filter` from
+    `tag_mask=` / `tag_match=` / `filter=`): `mask`, one Python int for every query or an int64 [Q] device tensor, `match`, the
+    NLSH_TAG_* code, and `row_filter`, the checked RowFilter or None (a row must pass both).  DESIGN.md 4.16."""
+
+    __slots__ = ("mask", "match", "row_filter")
+
+    def __init__(self, mask, match, row_filter):
+        self.mask, self.match, self.row_filter = mask, int(match), row_filter
+
+    def masks(self, Q, dev):
+        """int64 [Q] on `dev`: the tensor as given, or the one int repeated."""
+        if isinstance(self.mask, torch.Tensor):
+            return self.mask
+        return torch.full((max(Q, 1),), self.mask, dtype=torch.int64, device=dev)
+
+
+def checked_tags(tags, n_rows, dev, what="tags"):
+    """A tag array of the constructor / `add` / `set_tags`: int64 [n_rows] on the index's device (the 64 bits are read as unsigned)."""
+    if not isinstance(tags, torch.Tensor) or tags.dtype != torch.int64 or tuple(tags.shape) != (n_rows,):
+        got = f"{tags.dtype} {tuple(tags.shape)}" if isinstance(tags, torch.Tensor) else type(tags).__name__
+        raise ValueError(f"{what} must be an int64 tensor of shape ({n_rows},) (64 tag bits per row, read as unsigned), got {got}")
+    if tags.device != dev:
+        raise ValueError(f"{what} are on {tags.device}, the index on {dev}")
+    return tags.contiguous()
+
+
 def pack_row_filter(allowed) -> np.ndarray:
     """Host statement of the filter layout: bool [N] in sorted-row order -> uint32 [2 * ceil(N / 64)] words (what
     `nlsh_row_filter_build` writes on the device; the tests hold one against the other)."""
@@ -228,12 +258,20 @@ class Indexer:
     storage = "float32"
     # None | "device" | "host": where the index keeps the caller's float32 rows for the exact re-rank; None = no second stage
     refine, refine_factor, refine_store = None, 4, None
+    # None | int64 [N]: the rows' 64-bit tag words in SORTED order, beside `gid` (an index built with `tags=`)
+    tags_sorted = None
 
     def __init__(self, hashing, candidate_vectors_gpu, distance_func, compat=True, metric: Optional[str] = None,
                  seg_rows: int = 0, id_base: int = 0, algo: Optional[str] = None,
                  row_ids: Optional[torch.Tensor] = None, schedule_stats: Optional[Tuple[float, float]] = None,
                  corpus_keys: Optional[torch.Tensor] = None, l2_form: str = "exact", window_rows: Optional[int] = None,
-                 row_align: int = 4, storage: Optional[str] = None, quantiser=None, refine: Optional[str] = None, refine_factor: int = 4):
+                 row_align: int = 4, storage: Optional[str] = None, quantiser=None, refine: Optional[str] = None, refine_factor: int = 4,
+                 tags: Optional[torch.Tensor] = None):
+        # tags: None | int64 [N] in the caller's row order = one 64-bit tag word per row for per-query tag filters (`tag_mask=` of the
+        # query calls).  The index keeps them beside `gid` in sorted order (`tags_sorted`, 8 bytes per row) and carries
+        # them through add / remove / update; an index built without tags has none and refuses `tag_mask=` and `add(tags=)`.
+        self._given_tags = None if tags is None else checked_tags(tags, int(candidate_vectors_gpu.shape[0]), candidate_vectors_gpu.device)
+        self.tags_sorted = None
         # refine: None | "device" | "host" = keep the caller's rows as float32 in id order (`RefineStore`) and rescore every
         # top-k call's candidates on them: stage one runs at k1 = min(256, max(k, refine_factor * k)), one `nlsh_rerank_topk` launch cuts
         # to k.  The store addresses rows by id - id_base: custom ids (`row_ids=`, `add(ids=)`) are refused, here and there.
@@ -463,6 +501,9 @@ class Indexer:
             if self.row_ids.shape[0] != N or self.row_ids.dtype != torch.int32:
                 raise ValueError("row_ids must be int32 [N]")
             self.gid = self.row_ids[self.perm.long()].contiguous()
+        if self._given_tags is not None:      # the int64 side array in sorted order: torch plumbing, as the int32 ones
+            self.tags_sorted = self._given_tags[self.perm.long()].contiguous()
+            self._given_tags = None
         self._refresh_bucket_tables()
 
     def _refresh_bucket_tables(self):
@@ -485,23 +526,30 @@ class Indexer:
     # After any sequence of these calls every array of the index equals, word for word, what the constructor builds from the index's
     # rows in local order -- the constructor's corpus, then every added batch, minus the removed rows -- with `row_ids=` their ids and
     # `corpus_keys=` their keys.  One pass over the sorted corpus (`nlsh_csr_update`), no sort of the old keys.
-    def add(self, vectors, ids=None, keys=None) -> torch.Tensor:
+    def add(self, vectors, ids=None, keys=None, tags=None) -> torch.Tensor:
         """Add float32 rows [M, d] (device; strided row views allowed; a compressed index also takes rows of its own dtype and refuses
         float32 values its storage cannot hold with a ValueError, nothing changed) -> their int32 ids (device).  `ids` (int32 [M], new and distinct)
         default to `next_id ..`; an index built with `row_ids=` has no default.  `keys` (int32 [M]) default to the hasher's keys,
-        as `corpus_keys=` does in the constructor."""
-        return self.update(add=vectors, add_ids=ids, add_keys=keys)[0]
+        as `corpus_keys=` does in the constructor.  `tags` (int64 [M]; an index built with `tags=` only) default to 0."""
+        return self.update(add=vectors, add_ids=ids, add_keys=keys, add_tags=tags)[0]
 
     def remove(self, ids) -> int:
         """Remove the rows with these ids (int tensor or sequence) -> how many rows went.  Unknown ids are ignored, duplicates count once."""
         return self.update(remove=ids)[1]
 
-    def update(self, add=None, add_ids=None, add_keys=None, remove=None) -> Tuple[torch.Tensor, int]:
+    def update(self, add=None, add_ids=None, add_keys=None, remove=None, add_tags=None) -> Tuple[torch.Tensor, int]:
         """`remove` and `add` in ONE pass over the corpus -> (ids of the added rows, number of rows removed).  Removal applies to the
         rows the index held before the call.  A build-path call: it runs on the current stream after the device has drained, and
         synchronises.  Out of place: the new sorted corpus is written beside the old one, which is released afterwards (peak memory:
         twice the sorted corpus).  Everything built on the old arrays -- plans, workspaces, cells, a `QueryPipeline` -- is stale
-        afterwards (`generation`)."""
+        afterwards (`generation`) -- the row tags are not: they belong to the rows and move with them (`add_tags`: int64 [M], default 0)."""
+        if add_tags is not None:
+            if self.tags_sorted is None:
+                raise ValueError("tags= on an index built without tags: pass tags= to the constructor (nothing was changed)")
+            if add is None:
+                raise ValueError("add_tags without rows to add")
+            add_tags = checked_tags(add_tags, int(add.shape[0]) if isinstance(add, torch.Tensor) and add.dim() == 2 else -1,
+                                    self.corpus_sorted.device)
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("update / add / remove need metric 'l2' or 'cosine': the generic-metric query reads the caller's "
                                       "corpus, which a mutated index no longer mirrors")
@@ -577,6 +625,16 @@ class Indexer:
         else:
             perm, old_keys = ~src, self.corpus_keys
             old_ids = None if self.row_ids is None else self.row_ids
+        if self.tags_sorted is not None:
+            # the tags follow the rows through `src_out`, as the keys and ids do through `perm`: a kept row's from its old sorted position,
+            # a new row's from `add_tags` (default 0)
+            new_tags = add_tags if add_tags is not None else torch.zeros((M,), dtype=torch.int64, device=dev)
+            if M == 0:
+                self.tags_sorted = self.tags_sorted[src]
+            elif N == 0:
+                self.tags_sorted = new_tags[~src]
+            else:
+                self.tags_sorted = torch.where(src >= 0, self.tags_sorted[src.clamp(min=0)], new_tags[(~src).clamp(min=0)])
         self.perm = perm.to(torch.int32)
         self.corpus_keys = torch.cat([old_keys, new_keys]) if M else old_keys.contiguous()
         if self.row_ids is not None:
@@ -673,6 +731,38 @@ class Indexer:
         for name in ("_range_plans", "_ranked_key_tables", "_key_tables", "_held", "_bucket_dir"):
             self.__dict__.pop(name, None)
 
+    # ------------------------------------------------------------------ row tags
+    def set_tags(self, ids, tags) -> int:
+        """Change the tags of held rows in place: `ids` (integer tensor or sequence), `tags` (int64, one per id) -> how many rows were
+        found.  Unknown ids are ignored, as in `remove`; of a repeated id one of its tags wins.  No row moves and `generation` stays:
+        RowFilters, plans and workspaces remain valid, and the next call sees the new tags (stream order)."""
+        if self.tags_sorted is None:
+            raise ValueError("set_tags on an index built without tags: pass tags= to the constructor")
+        dev = self.tags_sorted.device
+        ids = torch.as_tensor(ids, device=dev).reshape(-1)
+        if ids.numel() and (ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool):
+            raise ValueError("ids must hold integer ids")
+        tags = checked_tags(tags if isinstance(tags, torch.Tensor) else torch.as_tensor(tags, dtype=torch.int64, device=dev).reshape(-1),
+                            int(ids.numel()), dev)
+        if ids.numel() == 0 or self.gid.numel() == 0:
+            return 0
+        sorted_gid, order = torch.sort(self.gid.long())
+        ids = ids.long()
+        pos = torch.searchsorted(sorted_gid, ids).clamp_(max=sorted_gid.numel() - 1)
+        found = sorted_gid[pos] == ids
+        rows = order[pos[found]]
+        self.tags_sorted[rows] = tags[found]
+        return int(torch.unique(rows).numel())
+
+    def tags_local(self) -> torch.Tensor:
+        """The tags in LOCAL row order (int64 [N]; the constructor's rows, then every added batch, minus the removed rows): what
+        `Indexer(..., tags=)` takes to rebuild this index."""
+        if self.tags_sorted is None:
+            raise ValueError("an index built without tags has none")
+        out = torch.empty_like(self.tags_sorted)
+        out[self.perm.long()] = self.tags_sorted
+        return out
+
     # ------------------------------------------------------------------ row filters
     def row_filter(self, allow=None, deny=None, mask=None) -> RowFilter:
         """A per-call row filter of this index (`filter=` of `scan_tensors` / `query_tensors` / `query_with_keys` / `query`): EXACTLY ONE
@@ -725,8 +815,37 @@ class Indexer:
                                             words.data_ptr() if N else None, n_allowed.data_ptr(), _stream(dev)))
         return RowFilter(self, words, int(n_allowed.item()), self.generation)
 
-    def _checked_filter(self, filter, algo=None):
-        """`filter=` of a call, checked before anything is launched -> the RowFilter or None."""
+    def _checked_filter(self, filter, algo=None, tag_mask=None, tag_match="any", query_vectors=None):
+        """`filter=` / `tag_mask=` / `tag_match=` of a call, checked before anything is launched -> None, the RowFilter, or -- a tagged
+        call -- the TagFilter that carries masks, mode and RowFilter along the routes a RowFilter takes."""
+        if isinstance(filter, TagFilter):       # a call of this class handing its checked TagFilter on
+            return filter
+        if tag_match not in TAG_MATCH:
+            raise ValueError(f"tag_match must be one of {tuple(TAG_MATCH)}, got {tag_match!r}")
+        if tag_mask is not None:
+            if self.tags_sorted is None:
+                raise ValueError("tag_mask= on an index built without tags: pass tags= to the constructor")
+            if isinstance(tag_mask, torch.Tensor):
+                n_queries = None if query_vectors is None else int(query_vectors.shape[0])
+                if tag_mask.dtype != torch.int64 or tag_mask.dim() != 1 or (n_queries is not None and tag_mask.shape[0] != n_queries):
+                    raise ValueError(f"tag_mask must be one Python int or an int64 tensor with one mask per query"
+                                     f"{'' if n_queries is None else f' ({n_queries},)'}, got {tag_mask.dtype} {tuple(tag_mask.shape)}")
+                if tag_mask.device != self.tags_sorted.device:
+                    raise ValueError(f"tag_mask is on {tag_mask.device}, the index on {self.tags_sorted.device}")
+                tag_mask = tag_mask.contiguous()
+            elif isinstance(tag_mask, bool) or not isinstance(tag_mask, numbers.Integral):
+                raise ValueError(f"tag_mask must be one Python int or an int64 tensor with one mask per query, got {type(tag_mask).__name__}")
+            else:
+                tag_mask = int(tag_mask)
+                if not -(1 << 63) <= tag_mask < (1 << 64):
+                    raise ValueError(f"tag_mask={tag_mask} does not fit 64 bits")
+                tag_mask = tag_mask - (1 << 64) if tag_mask >= (1 << 63) else tag_mask     # the same 64 bits in the signed container
+            if self.metric not in ("l2", "cosine"):
+                raise NotImplementedError("tag_mask= needs metric 'l2' or 'cosine': the tags are read by the tiled scan kernel")
+            if self.algo in ("query", "bucket") or algo in (_capi.SCAN_QUERY_MAJOR, _capi.SCAN_BUCKET_MAJOR):
+                raise ValueError("a tagged call (tag_mask=) is scanned by the tiled schedule only: algo='query' / 'bucket' cannot read row "
+                                 "tags (algo=None or 'tiled')")
+            return TagFilter(tag_mask, TAG_MATCH[tag_match], self._checked_filter(filter, algo))
         if filter is None:
             return None
         if not isinstance(filter, RowFilter):
@@ -993,6 +1112,11 @@ class Indexer:
         if self.refine is not None:
             raise NotImplementedError(f"{what} is not built for an index with refine=: the re-rank is a top-k stage (DESIGN.md 7)")
 
+    @staticmethod
+    def _refuse_tags(what, tag_mask):
+        if tag_mask is not None:
+            raise NotImplementedError(f"{what} takes no tag_mask: per-query tag filters are built for the top-k calls (DESIGN.md 7)")
+
     def _rerank(self, query_vectors, stage_one, k, want_keys, check=True):
         """Stage two behind a stage-one result (dist, idx [Q, k1], ncand, ...): ONE further launch on the same stream, stage one's idx its
         candidate table, nothing read on the host in between -> (exact dist [Q, k], idx [Q, k], stage one's ncand, stage two's keys64 | None)."""
@@ -1001,13 +1125,18 @@ class Indexer:
         self.last_query_path = path if path.endswith("+refine") else path + "+refine"
         return out[0], out[1], stage_one[2], out[3] if want_keys else None
 
-    def scan_tensors(self, query_vectors, keys, nkeys, k=10, want_keys=False, check=True, events=None, algo=None, filter=None, refine_k=None):
+    def scan_tensors(self, query_vectors, keys, nkeys, k=10, want_keys=False, check=True, events=None, algo=None, filter=None, refine_k=None,
+                     tag_mask=None, tag_match="any"):
         """Scan stage on a device key table -> (dist [Q,k], idx [Q,k], ncand [Q], keys64 | None).
+        tag_mask (an index built with `tags=` only; None = off): one Python int (every query's mask) or an int64 [Q] device tensor, matched
+        against the rows' 64-bit tags by `tag_match` -- "any": (tag & mask) != 0, "all": (tag & mask) == mask, "eq": tag == mask.  Query
+        q's result is, word for word, that of the index built from the rows that pass ITS mask alone, as with `filter=`; with `filter=`
+        as well a row must pass both.  `ncand` counts bucket rows before the tags.  Tiled schedule.
         filter (a `RowFilter` of this index, `row_filter()`; None = off): the result is, word for word, that of the index built from the
         allowed rows alone (same ids, same bucket keys, same key table) -- ids, distance bits and keys64, with -1 / +inf / ~0 behind a
         list shorter than k.  `ncand` stays the rows of the probed buckets, counted BEFORE the filter: the work the scan did, equal to
         the unfiltered call's.  A filtered call takes the tiled schedule whatever the batch shape, as a compressed index does."""
-        filter = self._checked_filter(filter, algo)
+        filter = self._checked_filter(filter, algo, tag_mask, tag_match, query_vectors)
         k1 = self._refine_k1(k, refine_k)
         if k1:      # stage one at k1 (this call, unrefined), then the re-rank (DESIGN.md 4.15)
             one = self.scan_tensors(query_vectors, keys, nkeys, k=k1, check=check, events=events, algo=algo, filter=filter, refine_k=0)
@@ -1124,10 +1253,16 @@ class Indexer:
         # an sq8 index has the call of its own: the quantiser's two arrays stand where the storage code does
         call, store = ((_capi.lib().nlsh_scan_topk_cells_phase_sq8, (self._qlo.data_ptr(), self._qstep.data_ptr())) if self.storage == "sq8"
                        else (_capi.lib().nlsh_scan_topk_cells_phase_filtered, (_STORAGES[self.storage][1],)))
+        tail = ()
+        if isinstance(filter, TagFilter):       # the tagged twin of either entry: tags, masks and mode behind the filter words
+            call = _capi.lib().nlsh_scan_topk_cells_phase_sq8_tagged if self.storage == "sq8" else _capi.lib().nlsh_scan_topk_cells_phase_tagged
+            masks = filter.masks(Q, q.device)      # alive until the call returns: the launch is enqueued by then (stream order)
+            tail = (self.tags_sorted.data_ptr() if self.tags_sorted.numel() else masks.data_ptr(), masks.data_ptr(), filter.match)
+            filter = filter.row_filter
         _capi.check(call(
             before[0], *store, *before[1:], q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
             events[0].cuda_event if events else None, events[1].cuda_event if events else None,
-            _stream(q.device) if stream is None else stream, phases, None if filter is None else filter.words.data_ptr()))
+            _stream(q.device) if stream is None else stream, phases, None if filter is None else filter.words.data_ptr(), *tail))
 
     def _scan_sliced(self, q, keys, nkeys, k, want_keys, check, filter=None):
         """hash_times > 64 (eval.py:148 sweeps n_samples up to 100): the key table is scanned in column slices of
@@ -1197,7 +1332,7 @@ class Indexer:
                 a(self.inv_norm), q.data_ptr(), q.stride(0), q.shape[0], keys.data_ptr(), nkeys.data_ptr(), keys.shape[1],
                 self._metric_code(), _capi.SCAN_BUCKET_TILED, a(filter.words) if filter is not None else None, rad.data_ptr())
 
-    def range_scan_tensors(self, query_vectors, keys, nkeys, radius, filter=None, limit=None, want_keys=False):
+    def range_scan_tensors(self, query_vectors, keys, nkeys, radius, filter=None, limit=None, want_keys=False, tag_mask=None):
         """Radius query on a device key table -> (offsets int64 [Q + 1], idx int32 [T], dist float32 [T], ncand int32 [Q], keys64 | None),
         all on the device: query q's result is idx / dist [offsets[q]:offsets[q + 1]], EVERY row of its keys' buckets with
         dist <= radius[q] (IEEE float32: a NaN distance never is, +inf only at radius +inf), each once, in the (distance, row id) order
@@ -1207,6 +1342,7 @@ class Indexer:
         limit (None = off): ValueError once the counts are known and before any output is allocated, if T > limit.
         Two scan launches with one host read between them (`nlsh_range_count`, `nlsh_range_fill`): the call synchronises.  Always the
         tiled schedule, as filtered and compressed calls; key tables wider than 64 probes are refused."""
+        self._refuse_tags("range_scan_tensors", tag_mask)
         self._refuse_refine("range_scan_tensors")
         self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
@@ -1269,9 +1405,10 @@ class Indexer:
         return offsets, idx, dist, ncand, keys64
 
     def range_tensors(self, query_vectors, radius, hash_times=10, seed=None, probes=None, candidate_budget=None, filter=None, limit=None,
-                      want_keys=False):
+                      want_keys=False, tag_mask=None):
         """Device-resident radius query: the hash by the two-step route (`last_query_path == "two_step"`; probes / candidate_budget as in
         `query_tensors`), then `range_scan_tensors`.  hash_times <= 64."""
+        self._refuse_tags("range_tensors", tag_mask)
         self._refuse_refine("range_tensors")
         self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
@@ -1295,16 +1432,19 @@ class Indexer:
         return rows, nc, [dh[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
 
     def range_query(self, query_vectors, radius, hash_times=10, seed=None, probes=None, candidate_budget=None, filter=None, limit=None,
-                    return_distances=False):
+                    return_distances=False, tag_mask=None):
         """Radius query in the shape `query()` returns: (List[List[int]], List[int]) -- per query the ids of every candidate within
         `radius`, in (distance, row id) order, and the candidate counts (before the radius and the filter); with return_distances=True
         also the lists of distances.  See `range_scan_tensors`."""
+        self._refuse_tags("range_query", tag_mask)
         self._refuse_refine("range_query")
         out = self.range_tensors(query_vectors, radius, hash_times, seed, probes, candidate_budget, filter, limit)
         return self._range_lists(*out[:4], return_distances)
 
-    def range_query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], radius, filter=None, return_distances=False):
+    def range_query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], radius, filter=None, return_distances=False,
+                              tag_mask=None):
         """`range_query` on caller-supplied key lists, like `query_with_keys`."""
+        self._refuse_tags("range_query_with_keys", tag_mask)
         self._refuse_refine("range_query_with_keys")
         self._refuse_range_on_sq8()
         filter = self._checked_filter(filter)
@@ -1322,8 +1462,10 @@ class Indexer:
         return self._range_lists(*out[:4], return_distances)
 
     def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None, probes=None,
-                      candidate_budget=None, filter=None, refine_k=None):
+                      candidate_budget=None, filter=None, refine_k=None, tag_mask=None, tag_match="any"):
         """Device-resident form of `query`: hashing + scan, nothing copied to the host.
+        tag_mask / tag_match (an index built with `tags=` only; None = off): per-query tag filters, see `scan_tensors`.  A tagged call
+        takes the route a filtered one takes: two-step, tiled schedule, counts and `candidate_budget` before the tags.
         refine_k (an index built with `refine=` only): None = stage one at k1 = min(256, max(k, refine_factor * k)), an integer in
         [k, 256] = stage one at that k1, 0 = no second stage for this call.  With the stage on, the distances are the exact float32
         ones of the ORIGINAL rows, `ncand` is stage one's, keys64 stage two's and `last_query_path` ends in "+refine".
@@ -1334,7 +1476,7 @@ class Indexer:
         filter (a `RowFilter` of this index; None = off): see `scan_tensors`.  A filtered call takes the two-step route (hash, then the
         filtered tiled scan; `last_query_path == "two_step"`), never the fused or the ranked one-call route.  The candidate counts and
         `candidate_budget` count bucket rows BEFORE the filter: the probe kernel does not know it."""
-        filter = self._checked_filter(filter)
+        filter = self._checked_filter(filter, None, tag_mask, tag_match, query_vectors)
         k1 = self._refine_k1(k, refine_k)
         if k1:
             one = self.query_tensors(query_vectors, k=k1, hash_times=hash_times, seed=seed, check=check, events=events, probes=probes,
@@ -1881,7 +2023,7 @@ class Indexer:
         return self._to_lists(self._short_key_sets(nc_h, keys_h, nkeys_h, k), idx_h, nc_h, k)
 
     def query(self, query_vectors, k=10, hash_times=10, seed=None, probes=None, candidate_budget=None,
-              filter=None, refine_k=None) -> Tuple[List[List[int]], List[int]]:
+              filter=None, refine_k=None, tag_mask=None, tag_match="any") -> Tuple[List[List[int]], List[int]]:
         """nlsh/indexer.py:56-96.  `seed` (not in the reference): the Philox seed of the multi-probe draws; None takes the next one
         from the hasher's call counter, like every other hashing call.  `probes` (not in the reference): "sampled" | "ranked", the
         multi-probe mode of this call; None = the hasher's `probes` attribute.  `candidate_budget` (not in the reference; ranked mode
@@ -1890,8 +2032,10 @@ class Indexer:
         (distance, id) order, min(k, allowed candidates) of them -- what the index over the allowed rows alone returns with
         compat=False.  The reference's "fewer than k candidates -> rows of the last key" rule (F7) describes an unfiltered query and is
         NOT applied to a filtered one, whatever `compat` says.  The candidate counts (and `candidate_budget`) count the rows of the
-        probed buckets BEFORE the filter.  Tiled schedule, two-step route (`last_query_path == "two_step"`)."""
-        filter = self._checked_filter(filter)
+        probed buckets BEFORE the filter.  Tiled schedule, two-step route (`last_query_path == "two_step"`).
+        `tag_mask` / `tag_match` (not in the reference; an index built with `tags=` only): per-query tag filters, see `scan_tensors`; the
+        lists and counts follow the rules of a filtered call."""
+        filter = self._checked_filter(filter, None, tag_mask, tag_match, query_vectors)
         k1 = self._refine_k1(k, refine_k)
         if k1:
             with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
@@ -1989,11 +2133,12 @@ class Indexer:
             q = q.float().contiguous()
         return q
 
-    def query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], k=10, filter=None, refine_k=None):
+    def query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], k=10, filter=None, refine_k=None, tag_mask=None,
+                        tag_match="any"):
         """Scan stage on caller-supplied key lists (each in the iteration order the caller saw):
         parity on identical candidate sets, independent of hashing.  `filter`: as in `query` (allowed ids only, list lengths
-        from the sort keys, no F7 rule, candidate counts before the filter)."""
-        filter = self._checked_filter(filter)
+        from the sort keys, no F7 rule, candidate counts before the filter).  `tag_mask` / `tag_match`: as in `query`."""
+        filter = self._checked_filter(filter, None, tag_mask, tag_match, query_vectors)
         self._refine_k1(k, refine_k)        # refused before anything is copied to the device
         # a query's keys are a set (nlsh/utils.pyx:27-31): a repeated key probes its bucket once; first-occurrence order kept
         key_lists = [list(dict.fromkeys(int(key) for key in ks)) for ks in key_lists]

@@ -61,7 +61,9 @@ class MultiTableIndexer:
     def __init__(self, hashings, candidate_vectors_gpu, distance_func, metric: Optional[str] = None, storage: Optional[str] = None,
                  l2_form: str = "exact", row_align: int = 4, window_rows: Optional[int] = None, corpus_keys=None,
                  row_ids: Optional[torch.Tensor] = None, id_base: int = 0, quantiser=None, refine: Optional[str] = None,
-                 refine_factor: int = 4):
+                 refine_factor: int = 4, tags: Optional[torch.Tensor] = None):
+        # tags: None | int64 [N] = `Indexer`'s `tags=`, handed to every table (each keeps them in its own sorted order: 8 bytes per row
+        # and table); the queries then take `tag_mask=` / `tag_match=`
         # refine: None | "device" | "host" = ONE store of the caller's float32 rows behind the de-duplicating merge:
         # every table runs at k1, the merge keeps k1 distinct candidates and one re-rank cuts to k.  The tables themselves hold no store.
         self.refine, self.refine_factor = checked_refine(refine, refine_factor)
@@ -97,7 +99,7 @@ class MultiTableIndexer:
             kw = {} if storage != "sq8" else {"quantiser": quantiser if t == 0 else self.tables[0].quantiser}
             self.tables.append(Indexer(h, candidate_vectors_gpu, distance_func, compat=False, metric=self.metric, algo="tiled", storage=storage,
                                        l2_form=l2_form, row_align=row_align, window_rows=window_rows, row_ids=row_ids, id_base=id_base,
-                                       corpus_keys=None if corpus_keys is None else corpus_keys[t], **kw))
+                                       corpus_keys=None if corpus_keys is None else corpus_keys[t], tags=tags, **kw))
         self.storage = self.tables[0].storage
         if self.refine is not None:
             originals = candidate_vectors_gpu
@@ -144,13 +146,14 @@ class MultiTableIndexer:
         return int(k)
 
     def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, probes=None, candidate_budget=None, filter=None,
-                      want_keys=False, refine_k=None):
+                      want_keys=False, refine_k=None, tag_mask=None, tag_match="any"):
         """Device-resident query -> (dist [Q, k] float32, idx [Q, k] int32, ncand [Q] int32[, keys64 [Q, k] int64]).
         Every table answers `Indexer.query_tensors(..., want_keys=True)` with these arguments, one after the other on the current
         stream -- `hash_times`, `probes`, `candidate_budget` and `seed` are therefore PER TABLE -- and one `nlsh_merge_topk_unique` call
         merges the T lists: the k best DISTINCT (distance bits, id) keys, -1 / +inf / ~0 behind a query with fewer than k distinct
         candidates.  `ncand` is the sum of the tables' counts: scored (query, row) pairs, a row found by two tables counted twice.
         filter: a `MultiRowFilter` of this index (`row_filter()`); table t is handed its own bitset.  k <= 256.
+        tag_mask / tag_match (an index built with `tags=` only): `Indexer.query_tensors`' per-query tag filters, handed to every table.
         refine_k (an index built with `refine=` only; None = min(256, max(k, refine_factor * k)), 0 = off for this call): every table runs
         at k1, the merge keeps the k1 best distinct candidates and ONE `nlsh_rerank_topk` launch returns the k best of them by their exact
         float32 distance to the original rows; `ncand` stays the merge's sum, keys64 are the re-rank's."""
@@ -161,14 +164,15 @@ class MultiTableIndexer:
         k1 = stage_one_k(k, self.refine_factor, refine_k) if self.refine_store is not None else 0
         if k1:
             _, idx1, nc = self.query_tensors(query_vectors, k=k1, hash_times=hash_times, seed=seed, probes=probes,
-                                             candidate_budget=candidate_budget, filter=filter, refine_k=0)
+                                             candidate_budget=candidate_budget, filter=filter, refine_k=0, tag_mask=tag_mask,
+                                             tag_match=tag_match)
             dist, idx, _, keys64 = self.refine_store.rerank(self.tables[0]._as_queries(query_vectors), idx1, k, want_keys=True)
             return (dist, idx, nc, keys64) if want_keys else (dist, idx, nc)
         q = self.tables[0]._as_queries(query_vectors)     # made contiguous float32 once, not once per table
         keys, counts = [], []
         for table, f in zip(self.tables, filters):
             _, _, nc, k64 = table.query_tensors(q, k=k, hash_times=hash_times, seed=seed, want_keys=True, probes=probes,
-                                                candidate_budget=candidate_budget, filter=f)
+                                                candidate_budget=candidate_budget, filter=f, tag_mask=tag_mask, tag_match=tag_match)
             keys.append(k64)
             counts.append(nc)
         return self._merge(torch.stack(keys), torch.stack(counts), k, want_keys)
@@ -187,26 +191,27 @@ class MultiTableIndexer:
         return (out_dist, out_idx, out_nc, out_keys) if want_keys else (out_dist, out_idx, out_nc)
 
     def query(self, query_vectors, k=10, hash_times=10, seed=None, probes=None, candidate_budget=None,
-              filter=None) -> Tuple[List[List[int]], List[int]]:
+              filter=None, tag_mask=None, tag_match="any") -> Tuple[List[List[int]], List[int]]:
         """`Indexer.query` with `compat=False`: (id lists in (distance, id) order, candidate counts).  A list holds min(k, distinct
         candidates) ids -- its length comes from the sort keys, -1 being a legal row id -- so a query with fewer than k distinct
         candidates gets a short list and one with none an empty list: the reference's "fewer than k candidates -> rows of the last key"
         rule (F7) describes one hash table and is not applied here, as on filtered calls.  The counts are `query_tensors`' sums."""
         _, idx, ncand, keys64 = self.query_tensors(query_vectors, k=k, hash_times=hash_times, seed=seed, probes=probes,
-                                                   candidate_budget=candidate_budget, filter=filter, want_keys=True)
+                                                   candidate_budget=candidate_budget, filter=filter, want_keys=True, tag_mask=tag_mask,
+                                                   tag_match=tag_match)
         return self.tables[0]._filtered_lists(idx, ncand, keys64)
 
     # ------------------------------------------------------------------ mutation
-    def add(self, vectors, ids=None) -> torch.Tensor:
+    def add(self, vectors, ids=None, tags=None) -> torch.Tensor:
         """Add rows [M, d] to EVERY table -> their int32 ids (device).  The ids are fixed once -- `ids`, or `next_id ..` -- and handed
         to each table explicitly, so a row has one id everywhere; each table hashes the rows with its own hasher."""
-        return self.update(add=vectors, add_ids=ids)[0]
+        return self.update(add=vectors, add_ids=ids, add_tags=tags)[0]
 
     def remove(self, ids) -> int:
         """Remove the rows with these ids from every table -> how many rows went."""
         return self.update(remove=ids)[1]
 
-    def update(self, add=None, add_ids=None, remove=None) -> Tuple[torch.Tensor, int]:
+    def update(self, add=None, add_ids=None, remove=None, add_tags=None) -> Tuple[torch.Tensor, int]:
         """`Indexer.update` on every table: `remove` and `add` in one pass per table -> (ids of the added rows, rows removed).  After
         the call every table holds the same id set.  A `MultiRowFilter` built before an effective call is stale."""
         first = self.tables[0]
@@ -228,7 +233,7 @@ class MultiTableIndexer:
         result = None
         for t, table in enumerate(self.tables):
             try:
-                got = table.update(add=add, add_ids=add_ids, remove=remove)
+                got = table.update(add=add, add_ids=add_ids, remove=remove, add_tags=add_tags)
             except Exception as exc:
                 if t:       # the arguments are the same for every table, so a refusal comes from the first one, nothing changed
                     raise RuntimeError(f"table {t} refused an update that tables 0..{t - 1} applied; the tables no longer hold the "
@@ -244,6 +249,10 @@ class MultiTableIndexer:
             assert int(result[0][0].item()) == self.refine_store.id_base + self.refine_store.n_rows
             self.refine_store.append(originals)      # once: the tables share the store
         return result
+
+    def set_tags(self, ids, tags) -> int:
+        """`Indexer.set_tags` on every table -> how many rows were found (the tables hold the same ids)."""
+        return [table.set_tags(ids, tags) for table in self.tables][0]
 
     # ------------------------------------------------------------------ filters
     def row_filter(self, allow=None, deny=None, mask=None) -> MultiRowFilter:

@@ -49,7 +49,7 @@ class QueryPipeline:
     default_graph = True     # slots replay a captured hipGraph of the batch on a stream of their own (False: the staged streams of r03-r05)
 
     def __init__(self, indexer, sample_queries, k=10, hash_times=10, depth=3, want_keys=False,
-                 exchange: Optional[Callable] = None, split_front: Optional[bool] = None, graph: Optional[bool] = None):
+                 exchange: Optional[Callable] = None, split_front: Optional[bool] = None, graph: Optional[bool] = None, tag_mask=None):
         """`sample_queries`: a batch of the shape every later batch has (sizes the task table with one ordinary,
         checked call).  `exchange(keys64, ncand) -> (dist, idx, ncand)`: the sharded index's all-gather + merge,
         run on the tail stream (needs the 64-bit keys, so it implies want_keys).
@@ -57,6 +57,9 @@ class QueryPipeline:
         (`nlsh_step_create_graph`): batches overlap because the slots' streams do, and a submit costs the host one graph launch + two
         node updates instead of the staged slots' five launches + eight to ten event calls.  False = the three / four stage streams of
         r03-r05.  None = graph slots whenever the schedule is a bucket-major one (`QueryPipeline.default_graph`)."""
+        if tag_mask is not None:
+            raise NotImplementedError("pipelined batches take no tag_mask: the step descriptor carries neither row tags nor query masks, "
+                                      "and the graph nodes refuse them (DESIGN.md 7)")
         if getattr(indexer, "refine", None) is not None:
             raise NotImplementedError("pipelined batches are not built for an index with refine=: a slot's launches end at the scan's merge "
                                       "and have no re-rank stage (DESIGN.md 7)")
@@ -198,13 +201,16 @@ class QueryPipeline:
             return (slot.lane,) if slot is not None else tuple(sl.lane for sl in self.slots)
         return (self.front, self.mid, self.tail) + ((self.plan,) if self.plan is not None else ())
 
-    def submit(self, queries, seed=None, events=None):
+    def submit(self, queries, seed=None, events=None, tag_mask=None):
         """Enqueue one batch; returns (dist, idx, ncand, keys64 | None) -- device tensors owned by the batch's slot
         (or fresh ones from `exchange`), valid once the tail stream has passed the batch (`synchronize()`), and
         overwritten `depth` submits later.  `events`: (begin, end) pair recorded around the scan kernel.
         The hasher's weights are the ones present at THIS call.  A batch that needs more tasks than the sample batch's table holds
         (1.25x + 1024 of what the sample needed) is reported by `overflowed()`, not by this call: check it before trusting a result
         of a batch much heavier than the sample."""
+        if tag_mask is not None:
+            raise NotImplementedError("pipelined batches take no tag_mask: the step descriptor carries neither row tags nor query masks "
+                                      "(DESIGN.md 7)")
         if queries.shape != (self.Q, self.d) or queries.dtype != torch.float32 or queries.stride(1) != 1:
             raise ValueError("batch shape/dtype differs from the pipeline's sample batch")
         ix, L = self.indexer, self._lib

@@ -26,15 +26,18 @@ struct Args {   // the valid set of the Python test: d = 100 in rows of 112, the
     size_t workspace_bytes = 0; int64_t max_tasks = 16; int phases = NLSH_PHASE_PLAN | NLSH_PHASE_SCAN | NLSH_PHASE_MERGE;
     void *row_filter = FAKE, *radius = FAKE, *out_count = FAKE, *row_offsets = FAKE; int64_t total = 5;
     void *cursor = FAKE, *sort_workspace = FAKE; size_t sort_workspace_bytes = 0;
+    void *lo = FAKE, *step = FAKE, *row_tags = FAKE, *query_masks = FAKE; int tag_match = NLSH_TAG_ANY;   // the tagged entries' alone
 };
 
-enum Entry { SCAN_TOPK, PHASE, CELLS, TYPED, FILTERED, RANGE_COUNT, RANGE_FILL, N_ENTRIES };
+enum Entry { SCAN_TOPK, PHASE, CELLS, TYPED, FILTERED, RANGE_COUNT, RANGE_FILL, TAGGED, SQ8_TAGGED, N_ENTRIES };
 const char *const ENTRY_NAME[N_ENTRIES] = {"nlsh_scan_topk", "nlsh_scan_topk_phase", "nlsh_scan_topk_cells_phase", "nlsh_scan_topk_cells_phase_typed",
-                                           "nlsh_scan_topk_cells_phase_filtered", "nlsh_range_count", "nlsh_range_fill"};
+                                           "nlsh_scan_topk_cells_phase_filtered", "nlsh_range_count", "nlsh_range_fill",
+                                           "nlsh_scan_topk_cells_phase_tagged", "nlsh_scan_topk_cells_phase_sq8_tagged"};
 constexpr unsigned bit(Entry e) { return 1u << e; }
-constexpr unsigned TOPK = bit(SCAN_TOPK) | bit(PHASE) | bit(CELLS) | bit(TYPED) | bit(FILTERED), RANGE = bit(RANGE_COUNT) | bit(RANGE_FILL);
-constexpr unsigned HAS_PHASES = TOPK & ~bit(SCAN_TOPK), HAS_CELLS = bit(CELLS) | bit(TYPED) | bit(FILTERED) | RANGE;
-constexpr unsigned STORED = bit(TYPED) | bit(FILTERED) | RANGE, HAS_FILTER = bit(FILTERED) | RANGE, ALL = TOPK | RANGE;
+constexpr unsigned TAGS = bit(TAGGED) | bit(SQ8_TAGGED);   // the filtered and the sq8 call plus row_tags, query_masks, tag_match
+constexpr unsigned TOPK = bit(SCAN_TOPK) | bit(PHASE) | bit(CELLS) | bit(TYPED) | bit(FILTERED) | TAGS, RANGE = bit(RANGE_COUNT) | bit(RANGE_FILL);
+constexpr unsigned HAS_PHASES = TOPK & ~bit(SCAN_TOPK), HAS_CELLS = bit(CELLS) | bit(TYPED) | bit(FILTERED) | RANGE | TAGS;
+constexpr unsigned STORED = bit(TYPED) | bit(FILTERED) | RANGE | bit(TAGGED), HAS_FILTER = bit(FILTERED) | RANGE | TAGS, ALL = TOPK | RANGE;
 
 #define F32P(p) ((const float *)(p))
 #define I32P(p) ((const int32_t *)(p))
@@ -54,6 +57,12 @@ int call(Entry e, const Args &a) {
     case TYPED: return nlsh_scan_topk_cells_phase_typed(a.corpus_sorted, a.storage, INDEX(a), CELLS_OF(a), TOPK_TAIL(a), a.phases);
     case FILTERED:
         return nlsh_scan_topk_cells_phase_filtered(a.corpus_sorted, a.storage, INDEX(a), CELLS_OF(a), TOPK_TAIL(a), a.phases, (const uint32_t *)a.row_filter);
+    case TAGGED:
+        return nlsh_scan_topk_cells_phase_tagged(a.corpus_sorted, a.storage, INDEX(a), CELLS_OF(a), TOPK_TAIL(a), a.phases, (const uint32_t *)a.row_filter,
+                                                 (const uint64_t *)a.row_tags, (const uint64_t *)a.query_masks, a.tag_match);
+    case SQ8_TAGGED:
+        return nlsh_scan_topk_cells_phase_sq8_tagged((const uint8_t *)a.corpus_sorted, F32P(a.lo), F32P(a.step), INDEX(a), CELLS_OF(a), TOPK_TAIL(a), a.phases,
+                                                     (const uint32_t *)a.row_filter, (const uint64_t *)a.row_tags, (const uint64_t *)a.query_masks, a.tag_match);
     case RANGE_COUNT:
         return nlsh_range_count(RANGE_HEAD(a), (int32_t *)a.out_count, (int32_t *)a.out_ncand, (int32_t *)a.status, a.workspace, a.workspace_bytes, a.max_tasks,
                                 nullptr, nullptr, nullptr);
@@ -86,7 +95,8 @@ void expect(Entry e, const char *what, const Args &a, int code, const char *frag
 
 int main() {
     const int INV = NLSH_E_INVALID, UNS = NLSH_E_UNSUPPORTED;
-    auto no_filter = [](Args &a) { a.row_filter = nullptr; };
+    // (the untagged faults below reach the tagged entries with their tags in place: the tags' own refusals come behind the schedule's)
+    auto no_filter = [](Args &a) { a.row_filter = nullptr; a.row_tags = a.query_masks = nullptr; };
     std::vector<Fault> faults = {
         {"Q negative", [](Args &a) { a.Q = -1; }, "Q=-1", ALL, INV},
         {"Q = 2^31", [](Args &a) { a.Q = 1ll << 31; }, "Q=2147483648", ALL, INV},
@@ -95,8 +105,8 @@ int main() {
         {"P = 0", [](Args &a) { a.P = 0; }, "P=0", ALL, UNS},
         {"P > MAX_PROBES", [](Args &a) { a.P = NLSH_MAX_PROBES + 1; }, "P=65", ALL, UNS},
         {"k = 0", [](Args &a) { a.k = 0; }, "k=0", TOPK, UNS},
-        {"k = 65, query-major", [=](Args &a) { a.k = 65; a.algo = NLSH_SCAN_QUERY_MAJOR; no_filter(a); }, "k=65", TOPK, UNS},
-        {"k = 65, bucket-major", [=](Args &a) { a.k = 65; a.algo = NLSH_SCAN_BUCKET_MAJOR; no_filter(a); }, "k=65", TOPK, UNS},
+        {"k = 65, query-major", [=](Args &a) { a.k = 65; a.algo = NLSH_SCAN_QUERY_MAJOR; no_filter(a); }, "k=65", TOPK & ~bit(SQ8_TAGGED), UNS},   // (an sq8 call names its storage first)
+        {"k = 65, bucket-major", [=](Args &a) { a.k = 65; a.algo = NLSH_SCAN_BUCKET_MAJOR; no_filter(a); }, "k=65", TOPK & ~bit(SQ8_TAGGED), UNS},   // (an sq8 call names its storage first)
         {"k = 257, tiled", [](Args &a) { a.k = 257; }, "k=257", TOPK, UNS},
         {"metric", [](Args &a) { a.metric = 9; }, "metric=9", ALL, INV},
         {"algo", [](Args &a) { a.algo = 9; }, "algo=9", ALL, INV},
@@ -119,7 +129,7 @@ int main() {
         {"null out_ncand", [](Args &a) { a.out_ncand = nullptr; }, "null", TOPK, INV},
         {"cosine without inv_norm", [](Args &a) { a.metric = NLSH_METRIC_COSINE; }, "inv_norm", ALL, INV},
         {"row_stride < d", [](Args &a) { a.row_stride = 96; }, "row_stride=96", ALL, INV},
-        {"pitch, float32", [](Args &a) { a.row_stride = 102; }, "multiple of 4", ALL, INV},
+        {"pitch, float32", [](Args &a) { a.row_stride = 102; }, "multiple of 4", ALL & ~bit(SQ8_TAGGED), INV},
         {"pitch, float16", [](Args &a) { a.storage = NLSH_STORE_F16; a.row_stride = 100; }, "multiple of 8", STORED, INV},
         {"pitch, uint8", [](Args &a) { a.storage = NLSH_STORE_U8; a.row_stride = 104; }, "multiple of 16", STORED, INV},
         {"corpus misaligned", [](Args &a) { a.corpus_sorted = off(4); }, "16-byte aligned", ALL, INV},
@@ -133,12 +143,21 @@ int main() {
         {"storage", [](Args &a) { a.storage = 7; }, "storage=7", STORED, INV},
         {"float16, query-major", [=](Args &a) { a.storage = NLSH_STORE_F16; a.algo = NLSH_SCAN_QUERY_MAJOR; no_filter(a); }, "NLSH_SCAN_BUCKET_TILED", bit(TYPED) | bit(FILTERED), UNS},
         {"uint8, bucket-major", [=](Args &a) { a.storage = NLSH_STORE_U8; a.algo = NLSH_SCAN_BUCKET_MAJOR; no_filter(a); }, "NLSH_SCAN_BUCKET_TILED", bit(TYPED) | bit(FILTERED), UNS},
-        {"filter, query-major", [](Args &a) { a.algo = NLSH_SCAN_QUERY_MAJOR; }, "row_filter", bit(FILTERED), UNS},
-        {"filter, bucket-major", [](Args &a) { a.algo = NLSH_SCAN_BUCKET_MAJOR; }, "row_filter", bit(FILTERED), UNS},
+        {"filter, query-major", [](Args &a) { a.algo = NLSH_SCAN_QUERY_MAJOR; }, "row_filter", bit(FILTERED) | TAGS, UNS},
+        {"filter, bucket-major", [](Args &a) { a.algo = NLSH_SCAN_BUCKET_MAJOR; }, "row_filter", bit(FILTERED) | TAGS, UNS},
+        // per-query tag filters
+        {"tags, query-major", [](Args &a) { a.algo = NLSH_SCAN_QUERY_MAJOR; a.row_filter = nullptr; }, "row_tags", TAGS, UNS},
+        {"tags, bucket-major", [](Args &a) { a.algo = NLSH_SCAN_BUCKET_MAJOR; a.row_filter = nullptr; }, "row_tags", TAGS, UNS},
+        {"query_masks without row_tags", [](Args &a) { a.row_tags = nullptr; }, "query_masks without row_tags", TAGS, INV},
+        {"row_tags without query_masks", [](Args &a) { a.query_masks = nullptr; }, "row_tags without query_masks", TAGS, INV},
+        {"row_tags misaligned", [](Args &a) { a.row_tags = off(4); }, "row_tags must be 8-byte aligned", TAGS, INV},
+        {"query_masks misaligned", [](Args &a) { a.query_masks = off(4); }, "query_masks must be 8-byte aligned", TAGS, INV},
+        {"tag_match = 3", [](Args &a) { a.tag_match = 3; }, "tag_match=3", TAGS, INV},
+        {"tag_match = -1", [](Args &a) { a.tag_match = -1; }, "tag_match=-1", TAGS, INV},
         {"range, query-major", [=](Args &a) { a.algo = NLSH_SCAN_QUERY_MAJOR; no_filter(a); }, "NLSH_SCAN_BUCKET_TILED", RANGE, UNS},
         {"range, bucket-major", [=](Args &a) { a.algo = NLSH_SCAN_BUCKET_MAJOR; no_filter(a); }, "NLSH_SCAN_BUCKET_TILED", RANGE, UNS},
         // entries that disagree: a compressed top-k call holds its pitch (now < d) before the limits
-        {"d > MAX_DIM, float16 (top-k)", [](Args &a) { a.d = NLSH_MAX_DIM + 1; a.storage = NLSH_STORE_F16; }, "row_stride=112", bit(TYPED) | bit(FILTERED), INV},
+        {"d > MAX_DIM, float16 (top-k)", [](Args &a) { a.d = NLSH_MAX_DIM + 1; a.storage = NLSH_STORE_F16; }, "row_stride=112", bit(TYPED) | bit(FILTERED) | bit(TAGGED), INV},
         {"d > MAX_DIM, float16 (range)", [](Args &a) { a.d = NLSH_MAX_DIM + 1; a.storage = NLSH_STORE_F16; }, "d=1025", RANGE, UNS},
     };
     int calls = 0;
@@ -147,8 +166,8 @@ int main() {
         expect((Entry)e, "valid", Args(), NLSH_E_WORKSPACE, "workspace");
         for (int algo : {NLSH_SCAN_QUERY_MAJOR, NLSH_SCAN_BUCKET_MAJOR}) {
             Args a;
-            a.algo = algo; a.row_filter = nullptr;
-            if (bit((Entry)e) & TOPK) expect((Entry)e, "valid, other schedule", a, NLSH_E_WORKSPACE, "workspace");
+            a.algo = algo; a.row_filter = nullptr; a.row_tags = a.query_masks = nullptr;
+            if (bit((Entry)e) & TOPK & ~bit(SQ8_TAGGED)) expect((Entry)e, "valid, other schedule", a, NLSH_E_WORKSPACE, "workspace");
         }
         for (const Fault &f : faults) {
             if (!(f.entries & bit((Entry)e))) continue;
@@ -161,6 +180,7 @@ int main() {
         empty.Q = 0;
         empty.corpus_sorted = empty.gid = empty.uniq_keys = empty.offsets = empty.queries = empty.qkeys = empty.nkeys = empty.out_dist = empty.out_idx =
             empty.out_ncand = empty.status = empty.workspace = empty.row_filter = empty.cursor = empty.sort_workspace = nullptr;
+        empty.lo = empty.step = empty.row_tags = empty.query_masks = nullptr;
         expect((Entry)e, "empty batch", empty, NLSH_OK, nullptr);
     }
     printf("%d refused calls over %d entry points, %d failures\n", calls, (int)N_ENTRIES, failures);
