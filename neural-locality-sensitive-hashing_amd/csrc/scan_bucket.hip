@@ -100,22 +100,14 @@ static const void *bscan2_of(int d4) {
 struct ScanLaunch {
     const void *fn;
     dim3 grid, block;
-    void *argv[2];   // the kernel's BArgs and, read by the filtered kernels alone, the filter pointer as their second parameter
-    QuantArgs quant; // ... or, read by the affine kernels alone, the quantiser and the filter
-    TagArgs tag;     // ... or, read by the tagged kernels alone, tags, masks, mode, filter and quantiser
+    void *argv[2];   // the kernel's BArgs and, read by the filtered, affine and tagged kernels alone, `side` as their second parameter
+    SideArgs side;   // the call's filter, quantiser, tags, masks and mode: what it does not carry is null
 };
 static int scan_launch_of(const BucketScanCall &c, int metric, const BArgs *a, ScanLaunch *l) {
+    l->side = SideArgs{c.row_tags, c.query_masks, c.tag_match, c.row_filter, c.affine ? (const float4 *)c.quant_lo : nullptr,
+                       c.affine ? (const float4 *)c.quant_step : nullptr};
     l->argv[0] = (void *)a;
-    l->argv[1] = (void *)&c.row_filter;
-    if (c.affine) {
-        l->quant = QuantArgs{(const float4 *)c.quant_lo, (const float4 *)c.quant_step, c.row_filter};
-        l->argv[1] = (void *)&l->quant;
-    }
-    if (c.row_tags) {
-        l->tag = TagArgs{c.row_tags, c.query_masks, c.tag_match, c.row_filter, c.affine ? (const float4 *)c.quant_lo : nullptr,
-                         c.affine ? (const float4 *)c.quant_step : nullptr};
-        l->argv[1] = (void *)&l->tag;
-    }
+    l->argv[1] = (void *)&l->side;
     const bool wide = c.k > NLSH_MAX_K;   // wide k: the same task body, its epilogue selecting up to 64 * TPS keys per list
     if (!c.tiled()) {
         NLSH_REQUIRE(!c.row_filter && c.storage == NLSH_STORE_F32 && !c.affine && !c.row_tags, NLSH_E_UNSUPPORTED,

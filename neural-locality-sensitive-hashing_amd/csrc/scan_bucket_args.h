@@ -89,22 +89,18 @@ struct RangeArgs {
 // uint8 layout, decoded per dimension as the tile is written (Stored<NLSH_STORE_SQ8>).  Internal: the C ABI's storage codes end at
 // NLSH_STORE_U8, an sq8 call is a uint8 call that carries a quantiser (BucketScanCall::affine).
 #define NLSH_STORE_SQ8 3
-// Second parameter of the affine kernels, as RangeArgs is the radius kernels': BArgs keeps its layout.
-struct QuantArgs {
-    const float4 *lo4;             // [row_stride / 4] the quantiser's offsets, padded to the pitch with 0
-    const float4 *step4;           // [row_stride / 4] its steps, padded with 1: a padded column (code 0) decodes to +0
-    const uint32_t *row_filter;    // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: every row allowed
-};
-
-// Second parameter of the tagged kernels (bscang_kernel, scan_bucket_tagged.hip; nlsh_scan_topk_cells_phase_tagged / _sq8_tagged), as
-// RangeArgs is the radius kernels': BArgs keeps its layout.  What TAGS of tiled_task_body reads beside BArgs.
-struct TagArgs {
-    const uint64_t *tags;          // [N] tag word of every SORTED row, read with the row position the lane already has
-    const uint64_t *qmask;         // [Q] mask of every query of the call
-    int match;                     // NLSH_TAG_ANY | NLSH_TAG_ALL | NLSH_TAG_EQ (wave-uniform)
-    const uint32_t *row_filter;    // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: every row allowed
-    const float4 *lo4;             // NLSH_STORE_SQ8 instantiations: the quantiser, as in QuantArgs; nullptr otherwise
-    const float4 *step4;
+// The side arguments of a tiled scan: everything a call can carry beside BArgs, which keeps its layout.  ONE struct, the second parameter
+// of the filtered, affine and tagged kernels (bscanf_kernel, bscana_kernel, bscang_kernel) and what tiled_task_body reads its filter and
+// its quantiser from in every form; a kernel reads the fields its compile-time flags (FILT, STORE, TAGS) name and no others.  Filled once
+// per call from the BucketScanCall (scan_launch_of).  The field order decides how the compiler merges the argument loads: with this one
+// every kernel keeps its resource figures and its arithmetic loops (profiles/scan_side_args.txt).
+struct SideArgs {
+    const uint64_t *tags;          // TAGS: [N] tag word of every SORTED row, read with the row position the lane already has
+    const uint64_t *qmask;         // TAGS: [Q] mask of every query of the call
+    int match;                     // TAGS: NLSH_TAG_ANY | NLSH_TAG_ALL | NLSH_TAG_EQ (wave-uniform)
+    const uint32_t *row_filter;    // bitset over the sorted rows (nlsh_row_filter_build); FILT: never null, otherwise nullptr = every row allowed
+    const float4 *lo4;             // NLSH_STORE_SQ8: [row_stride / 4] the quantiser's offsets, padded to the pitch with 0
+    const float4 *step4;           // NLSH_STORE_SQ8: [row_stride / 4] its steps, padded with 1: a padded column (code 0) decodes to +0
 };
 
 // A call's prepared launch (scan_bucket.hip): the workspace held against the schedule's layout (NLSH_E_WORKSPACE), then what the scan kernels

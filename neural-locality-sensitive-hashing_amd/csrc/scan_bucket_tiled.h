@@ -486,8 +486,8 @@ __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const typena
 // the wave's query ids).  `tile` = the workgroup's LDS stage.
 // WIDEK (compile time): k in 65..NLSH_MAX_K_TILED -- the epilogue's selection pads its k-key list with a lane-strided loop; everything in
 // front of the epilogue is the same code, so every distance keeps its bits.
-// FILT (compile time; nlsh_scan_topk_cells_phase_filtered): `row_filter` is a bitset over the sorted rows (bit p & 31 of word p >> 5: row p
-// may be returned).  The lane's word of every tile is requested beside its row id at the top of the task and its bit enters `mine` in
+// FILT (compile time; nlsh_scan_topk_cells_phase_filtered): `side->row_filter` is a bitset over the sorted rows (bit p & 31 of word p >> 5:
+// row p may be returned).  The lane's word of every tile is requested beside its row id at the top of the task and its bit enters `mine` in
 // the epilogue: a denied row is dropped in front of the selection and changes nothing in staging, in the k-blocks or in a distance.
 // Off (the default), neither the parameter nor the words exist in the code.
 // RANGE (compile time; nlsh_range_count / nlsh_range_fill, bscanr_kernel): the RANGE EPILOGUE in place of the selection.  Everything up to
@@ -495,29 +495,30 @@ __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const typena
 // dist <= range->radius[q] (IEEE float32: a NaN distance never is, +inf only at radius +inf), the hits are counted with ballots over the
 // TPS tiles and lane 0 adds the count to range->counter[q] -- the whole answer in count mode; in fill mode the add's result is the
 // list's first slot of the query's segment and every hit lane stores its key at row_offsets[q] + slot (mbcnt ranks, as in
-// select_k_smallest's compaction).  tauq and partial are not touched.  range->row_filter (nullable) is the filter, a run-time operand
+// select_k_smallest's compaction).  tauq and partial are not touched.  side->row_filter (nullable) is the filter, a run-time operand
 // here: a null pointer gives every lane an all-ones word.  Off (the default), neither the parameter nor the code exists.
 // TAGS (compile time; nlsh_scan_topk_cells_phase_tagged / _sq8_tagged, bscang_kernel): per-query tag filters.  Every sorted row carries a
-// 64-bit tag word (tag->tags, read with the row position the lane already has: 8 bytes per lane and tile, coalesced), every query a 64-bit
-// mask (tag->qmask[q], wave-uniform: a scalar load per query of the wave, of the slot's own query -- qid[jq] is the id of slot
-// NLSH_SLOT(wave, jq), clamped as everywhere) and the call one match mode.  Tags, masks and the optional bitset bit (tag->row_filter) are
+// 64-bit tag word (side->tags, read with the row position the lane already has: 8 bytes per lane and tile, coalesced), every query a 64-bit
+// mask (side->qmask[q], wave-uniform: a scalar load per query of the wave, of the slot's own query -- qid[jq] is the id of slot
+// NLSH_SLOT(wave, jq), clamped as everywhere) and the call one match mode.  Tags, masks and the optional bitset bit (side->row_filter) are
 // folded into ONE register of 16 pass bits (bit tl * QW + jq) in front of the task bodies, so that neither the tag words nor the filter
 // words are live during the arithmetic; bit (tl, jq) enters `mine` in the epilogue.  A denied row changes nothing in staging, in the
-// k-blocks or in a distance.  With STORE == NLSH_STORE_SQ8 the quantiser comes from TagArgs too.  Off (the default), none of it exists.
+// k-blocks or in a distance.  With STORE == NLSH_STORE_SQ8 the quantiser is side->lo4 / step4, as in the affine kernels.  Off (the
+// default), none of it exists.
 template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = NLSH_STORE_F32, bool FILT = false, bool RANGE = false,
           bool TAGS = false>
 __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, long long t, const int4 desc, const int2 qr_all, int tid, int lane,
                                                 int wave, [[maybe_unused]] unsigned long long ts_entry,
-                                                [[maybe_unused]] const uint32_t *row_filter = nullptr,
-                                                [[maybe_unused]] const RangeArgs *range = nullptr,
-                                                [[maybe_unused]] const QuantArgs *quant = nullptr,
-                                                [[maybe_unused]] const TagArgs *tag = nullptr) {
-    static_assert(!(RANGE && (FILT || WIDEK)), "the range epilogue reads its filter from RangeArgs and selects nothing");
-    static_assert(!(TAGS && (FILT || RANGE)), "the tagged kernels read their filter from TagArgs and have no range epilogue");
-    // AFFINE (STORE == NLSH_STORE_SQ8; nlsh_scan_topk_cells_phase_sq8, bscana_kernel): the staging code decodes with quant->lo4 / step4,
-    // and quant->row_filter (nullable) is the filter, a run-time operand as in the range kernels.  Off, none of it exists in the code.
+                                                [[maybe_unused]] const SideArgs *side = nullptr,
+                                                [[maybe_unused]] const RangeArgs *range = nullptr) {
+    static_assert(!(RANGE && (FILT || WIDEK)), "the range epilogue takes its filter as a nullable run-time operand and selects nothing");
+    static_assert(!(TAGS && (FILT || RANGE)), "the tagged kernels take their filter as a nullable run-time operand and have no range epilogue");
+    // AFFINE (STORE == NLSH_STORE_SQ8; nlsh_scan_topk_cells_phase_sq8, bscana_kernel): the staging code decodes with side->lo4 / step4,
+    // and the filter is a nullable run-time operand as in the range kernels.  Off, none of it exists in the code.
     constexpr bool AFFINE = STORE == NLSH_STORE_SQ8;
-    static_assert(!(AFFINE && (FILT || RANGE)), "the affine kernels read their filter from QuantArgs (the tagged form: TagArgs) and have no range epilogue");
+    static_assert(!(AFFINE && (FILT || RANGE)), "the affine kernels take their filter as a nullable run-time operand and have no range epilogue");
+    // SIDE: the forms that read `side` at all; in the others neither the parameter nor the filter words exist in the code
+    constexpr bool SIDE = FILT || RANGE || AFFINE || TAGS;
     static_assert(QW == 4 && TPS == 4 && NW == 4, "the hand-scheduled task bodies (l2_task_nt) are written for 4 waves x 4 queries x 4 row tiles");
 #ifdef NLSH_SCAN_TRACE_CLOCK
     const unsigned long long ts0 = SCAN_NOW();
@@ -572,14 +573,12 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
         const int prow = row0 + (valid[tl] ? tl * 64 + lane : 0);
         mygid[tl] = valid[tl] ? a.gid[prow] : -1;
         myinv[tl] = (METRIC == NLSH_METRIC_COSINE && valid[tl]) ? a.inv_norm[prow] : 0.0f;
-        if (TAGS) myfw[tl] = tag->row_filter ? tag->row_filter[prow >> 5] : 0xFFFFFFFFu;
-        else if (FILT) myfw[tl] = row_filter[prow >> 5];
-        else if (RANGE) myfw[tl] = range->row_filter ? range->row_filter[prow >> 5] : 0xFFFFFFFFu;
-        else if (AFFINE) myfw[tl] = quant->row_filter ? quant->row_filter[prow >> 5] : 0xFFFFFFFFu;
+        // the filter word, read HERE for every form: FILT reads it without a test, the other forms take a null pointer as all ones
+        if constexpr (SIDE) myfw[tl] = (FILT || side->row_filter) ? side->row_filter[prow >> 5] : 0xFFFFFFFFu;
     }
+    // the quantiser, read HERE for every form
     [[maybe_unused]] const float4 *qlo = nullptr, *qstep = nullptr;
-    if constexpr (AFFINE && TAGS) { qlo = tag->lo4; qstep = tag->step4; }
-    else if constexpr (AFFINE) { qlo = quant->lo4; qstep = quant->step4; }
+    if constexpr (AFFINE) { qlo = side->lo4; qstep = side->step4; }
     // TAGS: the 16 pass bits of the lane's (tile, query) pairs.  The masks of the wave's LIVE slots only (jq < nqw: what the epilogue
     // reads the bounds of); lanes past the task's last row hold the words of row0 and are never `valid`.  The empty asm pins the fold in
     // front of the task bodies: behind them, the eight tag registers and the filter words would live through the arithmetic.
@@ -587,10 +586,10 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
     if constexpr (TAGS) {
         uint64_t mytag[TPS], qm[QW];
 #pragma unroll
-        for (int tl = 0; tl < TPS; ++tl) mytag[tl] = tag->tags[row0 + (valid[tl] ? tl * 64 + lane : 0)];
+        for (int tl = 0; tl < TPS; ++tl) mytag[tl] = side->tags[row0 + (valid[tl] ? tl * 64 + lane : 0)];
 #pragma unroll
-        for (int jq = 0; jq < QW; ++jq) qm[jq] = jq < nqw ? tag->qmask[qid[jq]] : 0ull;
-        const int match = tag->match;
+        for (int jq = 0; jq < QW; ++jq) qm[jq] = jq < nqw ? side->qmask[qid[jq]] : 0ull;
+        const int match = side->match;
 #pragma unroll
         for (int tl = 0; tl < TPS; ++tl) {
             const bool fbit = (myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u;   // valid lanes: the bit of prow
@@ -665,7 +664,7 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
             for (int tl = 0; tl < TPS; ++tl) {
                 bool mine = valid[tl] && (unsigned)(tl * 64 + lane) - r_lo < r_n;
                 if (TAGS) mine = mine && ((pass >> (tl * QW + jq)) & 1u);   // tag, mask and filter bit of (tile, query), folded at the top
-                else if (FILT || RANGE || AFFINE) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
+                else if (SIDE) mine = mine && ((myfw[tl] >> ((row0 + tl * 64 + lane) & 31)) & 1u);   // valid lanes: the bit of prow
                 uint64_t kk;
                 [[maybe_unused]] float dist_r;   // RANGE: the distance the key is built from, held against the radius
                 if (lean) {
@@ -753,6 +752,47 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
 }
 
 
+// The task pick of every tiled kernel: after it `t` (task id), `desc` (its descriptor) and `qr_all` (its slot records) are in scope, and a
+// workgroup past the task count has returned.  Needs `a` (BArgs), `lane`, QW and NW.  A MACRO, not a function: as a __forceinline__ function
+// that returns the three through references the compiler merges the two slot-record dwords into one load and re-orders the hot loops of
+// bscan3_kernel and bscanw_kernel (profiles/scan_side_args.txt); expanded in each __global__ it is the text every kernel carried, and the
+// kernels are the code they were.
+//   - status: a task count above the table is clamped and flagged incomplete -- the caller must retry (a refusal of the PLAN phase, 2 or
+//     3, stays).
+//   - Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Task ids are dealt to the XCDs in CHUNKS of 16
+//     consecutive ids: the query groups of one row segment (consecutive ids) mostly land on one XCD and re-read its rows from that L2
+//     instead of HBM, while every XCD still walks the size-ordered task list front to back (a contiguous 1/8 range per XCD would hand all
+//     the heavy tasks to XCD 0).  Placement only changes speed, never results.
+//   - The descriptor is requested BEFORE the task count is known (index clamped into the table): one dependent round trip less in front
+//     of every task.
+//   - All 16 {query id, row range} records of the task come in ONE load, one record per lane (& 15) -- address known from the task id
+//     alone, requested with the descriptor.  A wave picks its own slots out of it with v_readlane (r04: four 8-byte loads per wave), and
+//     the hull of the rows the task's queries own at all is taken over all sixteen (r05).  Slots >= nq hold garbage, never used.
+//   - (r06: cross-task prefetch into the XCD's L2 -- a finished workgroup touching the rows of the task 1792-3072 ids ahead on its XCD
+//     with loads nobody waits for -- was built and is NOT here: every run of it ended in a GPU exception.  Cause not established: only
+//     queue dumps were kept, and the form that did not fault differed in distance, task class and the wait.  With the wait in front of
+//     s_endpgm the workgroup's slot is held for exactly the HBM miss the prefetch was meant to hide.  DESIGN.md appendix A.)
+#define NLSH_TILED_PICK(a)                                                                   \
+    long long ntasks = (a).status[0];                                                        \
+    if (ntasks > (a).max_tasks) {                                                            \
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&(a).status[1], 1);               \
+        ntasks = (a).max_tasks;                                                              \
+    }                                                                                        \
+    constexpr int XC = 16;                                                                   \
+    const long long j = blockIdx.x >> 3;                                                     \
+    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);                   \
+    const long long tc = t < (a).max_tasks ? t : (a).max_tasks - 1;                          \
+    const int4 desc = (a).task[tc];                                                          \
+    const int2 qr_all = (a).task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];                \
+    if (t >= ntasks) return
+
+// The seven kernels below are shells: the LDS stage, the pick, one call of tiled_task_body.  The stage is declared in each __global__:
+// handed to a shared function, or declared in one, its address stops being a compile-time constant of the staging code and the float32
+// kernels' instructions change.  Each is a kernel of its own name with task bodies of its own instantiation, in a translation unit of
+// its own where it says so, so that the kernels in front of it keep their code and their register / occupancy budget; BArgs keeps its
+// layout, and what a form needs beside it rides in a second parameter (SideArgs, RangeArgs: scan_bucket_args.h).
+
+// The tiled scan over a float32 corpus, k <= 64: what every default call runs.
 template <int METRIC, int QW, int NW, int TPS>
 __global__ __launch_bounds__(64 * NW, 1) void bscan3_kernel(BArgs a) {
     constexpr int KB = NLSH_TILED_KB;        // 16-byte chunks per k-block
@@ -761,68 +801,26 @@ __global__ __launch_bounds__(64 * NW, 1) void bscan3_kernel(BArgs a) {
     __shared__ float4 tile[ROWS * RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
-    long long ntasks = a.status[0];
-    if (ntasks > a.max_tasks) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);  // incomplete: caller must retry (a refusal of the PLAN phase -- 2, 3 -- stays)
-        ntasks = a.max_tasks;
-    }
-    // Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Task ids are dealt to the XCDs
-    // in CHUNKS of 16 consecutive ids: the query groups of one row segment (consecutive ids) mostly land on one
-    // XCD and re-read its rows from that L2 instead of HBM, while every XCD still walks the size-ordered task
-    // list front to back (a contiguous 1/8 range per XCD would hand all the heavy tasks to XCD 0).
-    // Placement only changes speed, never results.
-    constexpr int XC = 16;
-    const long long j = blockIdx.x >> 3;
-    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
-    // the descriptor is requested BEFORE the task count is known (index clamped into the table): one dependent round trip
-    // less in front of every task
-    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
-    const int4 desc = a.task[tc];
-    // all 16 {query id, row range} records of the task in ONE load, one record per lane (& 15) -- address known from the task id alone,
-    // requested with the descriptor.  A wave picks its own slots out of it with v_readlane (r04: four 8-byte loads per wave), and the
-    // hull of the rows the task's queries own at all is taken over all sixteen (r05).  Slots >= nq hold garbage, never used.
-    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
-    // (r06: cross-task prefetch into the XCD's L2 -- a finished workgroup touching the rows of the task 1792-3072 ids ahead on its XCD with
-    // loads nobody waits for -- was built and is NOT here: every run of it ended in a GPU exception.  Cause not established: only queue
-    // dumps were kept, and the form that did not fault differed in distance, task class and the wait.  With the wait in front of s_endpgm
-    // the workgroup's slot is held for exactly the HBM miss the prefetch was meant to hide.  DESIGN.md appendix A.)
-    if (t >= ntasks) return;
+    NLSH_TILED_PICK(a);
     if (NLSH_ABLATE == 9) return;   // diagnostic: every workgroup leaves after its descriptor loads (what dispatching the grid costs)
     if (NLSH_ABLATE == 8 && desc.y <= 4) return;   // diagnostic: tasks with few queries vanish (what the low-density tasks cost)
     if (NLSH_ABLATE == 7 && desc.w <= 64) return;   // diagnostic: tasks of <= 64 rows vanish (what a kernel without the tail of tiny tasks would take)
     tiled_task_body<METRIC, QW, NW, TPS>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry);
 }
 
-// The tiled scan for k in 65..NLSH_MAX_K_TILED: bscan3_kernel with the wide epilogue.  A kernel of its own name, so that the three
-// bscan3_kernel instantiations -- what every k <= 64 call runs -- keep their code and their register / occupancy budget.  The task pick
-// is bscan3_kernel's, line for line (see the comments there), and written out again: with the LDS stage handed to a shared function, or
-// declared in one, its address stops being a compile-time constant of the staging code and the narrow kernels' instructions change.
+// k in 65..NLSH_MAX_K_TILED: bscan3_kernel with the wide epilogue.
 template <int METRIC, int QW, int NW, int TPS>
 __global__ __launch_bounds__(64 * NW, 1) void bscanw_kernel(BArgs a) {
     constexpr int RS = NLSH_TILED_KB + 1;
     __shared__ float4 tile[64 * TPS * RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
-    long long ntasks = a.status[0];
-    if (ntasks > a.max_tasks) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
-        ntasks = a.max_tasks;
-    }
-    constexpr int XC = 16;
-    const long long j = blockIdx.x >> 3;
-    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
-    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
-    const int4 desc = a.task[tc];
-    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
-    if (t >= ntasks) return;
+    NLSH_TILED_PICK(a);
     tiled_task_body<METRIC, QW, NW, TPS, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry);
 }
 
-// The tiled scan over a float16 / uint8 corpus (STORE: NLSH_STORE_F16 | NLSH_STORE_U8; nlsh_scan_topk_cells_phase_typed), k <= 64 (WIDEK
-// false) and k in 65..NLSH_MAX_K_TILED (true).  Kernels of their own name with task bodies of their own instantiation (STORE), so that
-// bscan3_kernel and bscanw_kernel -- what every float32 index runs -- keep their code: profiles/corpus_storage.txt compares them with
-// the build before the typed forms existed.  The task pick is bscan3_kernel's, line for line (see the comments there), written out
-// again for the reason given at bscanw_kernel.
+// A float16 / uint8 corpus (STORE: NLSH_STORE_F16 | NLSH_STORE_U8; nlsh_scan_topk_cells_phase_typed), k <= 64 (WIDEK false) and k in
+// 65..NLSH_MAX_K_TILED (true).  Instantiated in scan_bucket_typed.hip (profiles/corpus_storage.txt).
 template <int METRIC, int QW, int NW, int TPS, int STORE, bool WIDEK>
 __global__ __launch_bounds__(64 * NW, 1) void bscant_kernel(BArgs a) {
     static_assert(STORE == NLSH_STORE_F16 || STORE == NLSH_STORE_U8, "the float32 corpus has bscan3_kernel / bscanw_kernel");
@@ -830,125 +828,61 @@ __global__ __launch_bounds__(64 * NW, 1) void bscant_kernel(BArgs a) {
     __shared__ float4 tile[64 * TPS * RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
-    long long ntasks = a.status[0];
-    if (ntasks > a.max_tasks) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
-        ntasks = a.max_tasks;
-    }
-    constexpr int XC = 16;
-    const long long j = blockIdx.x >> 3;
-    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
-    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
-    const int4 desc = a.task[tc];
-    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
-    if (t >= ntasks) return;
+    NLSH_TILED_PICK(a);
     tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry);
 }
 
-// The tiled scan behind a row filter (FILT of tiled_task_body; nlsh_scan_topk_cells_phase_filtered), every storage, k <= 64 (WIDEK false)
-// and k in 65..NLSH_MAX_K_TILED (true).  The filter is a SECOND kernel parameter: BArgs, and with it every kernel above, keeps its
-// layout and its code (profiles/row_filter.txt compares them with the build before the filter existed).  Instantiated in
-// scan_bucket_filtered.hip, a translation unit of its own.  The task pick is bscan3_kernel's, line for line (see the comments there),
-// written out again for the reason given at bscanw_kernel.
+// Behind a row filter (FILT of tiled_task_body; nlsh_scan_topk_cells_phase_filtered), every storage, both k classes: s.row_filter is never
+// null.  Instantiated in scan_bucket_filtered.hip (profiles/row_filter.txt).
 template <int METRIC, int QW, int NW, int TPS, int STORE, bool WIDEK>
-__global__ __launch_bounds__(64 * NW, 1) void bscanf_kernel(BArgs a, const uint32_t *row_filter) {
+__global__ __launch_bounds__(64 * NW, 1) void bscanf_kernel(BArgs a, SideArgs s) {
     constexpr int RS = NLSH_TILED_KB + 1;
     __shared__ float4 tile[64 * TPS * RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
-    long long ntasks = a.status[0];
-    if (ntasks > a.max_tasks) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
-        ntasks = a.max_tasks;
-    }
-    constexpr int XC = 16;
-    const long long j = blockIdx.x >> 3;
-    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
-    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
-    const int4 desc = a.task[tc];
-    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
-    if (t >= ntasks) return;
-    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, row_filter);
+    NLSH_TILED_PICK(a);
+    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, &s);
 }
 
-// The radius query's scan (RANGE of tiled_task_body; nlsh_range_count / nlsh_range_fill), every storage: the tiled kernels with the range
-// epilogue.  One kernel per (metric, storage) serves both modes and both filter states -- r.mode and r.row_filter are wave-uniform
-// run-time operands of the epilogue.  RangeArgs is a SECOND kernel parameter, as the filter is bscanf_kernel's: BArgs and every kernel
-// above keep their layout and their code (profiles/range_query.txt).  Instantiated in scan_bucket_range.hip, a translation unit of its
-// own.  The task pick is bscan3_kernel's, line for line (see the comments there), written out again for the reason given at bscanw_kernel.
+// The radius query's scan (RANGE of tiled_task_body; nlsh_range_count / nlsh_range_fill), every storage: the range epilogue.  One kernel
+// per (metric, storage) serves both modes and both filter states -- r.mode and r.row_filter are wave-uniform run-time operands.  The
+// kernel's parameters stay (BArgs, RangeArgs); the filter reaches the task body in a SideArgs built here, like every other form's.
+// Instantiated in scan_bucket_range.hip (profiles/range_query.txt).
 template <int METRIC, int QW, int NW, int TPS, int STORE>
 __global__ __launch_bounds__(64 * NW, 1) void bscanr_kernel(BArgs a, RangeArgs r) {
     constexpr int RS = NLSH_TILED_KB + 1;
     __shared__ float4 tile[64 * TPS * RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
-    long long ntasks = a.status[0];
-    if (ntasks > a.max_tasks) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
-        ntasks = a.max_tasks;
-    }
-    constexpr int XC = 16;
-    const long long j = blockIdx.x >> 3;
-    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
-    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
-    const int4 desc = a.task[tc];
-    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
-    if (t >= ntasks) return;
-    tiled_task_body<METRIC, QW, NW, TPS, false, STORE, false, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, nullptr, &r);
+    NLSH_TILED_PICK(a);
+    const SideArgs s = {nullptr, nullptr, 0, r.row_filter, nullptr, nullptr};
+    tiled_task_body<METRIC, QW, NW, TPS, false, STORE, false, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, &s, &r);
 }
 
-// The tiled scan over an sq8 corpus (AFFINE of tiled_task_body; nlsh_scan_topk_cells_phase_sq8): uint8 codes decoded per dimension as the
-// tile is written, k <= 64 (WIDEK false) and k in 65..NLSH_MAX_K_TILED (true).  One kernel per (metric, k class) serves both filter states
-// -- q.row_filter is a wave-uniform run-time operand, as in the range kernels.  QuantArgs is a SECOND kernel parameter: BArgs and every
-// kernel above keep their layout and their code (profiles/sq8_storage.txt).  Instantiated in scan_bucket_affine.hip, a translation unit
-// of its own.  The task pick is bscan3_kernel's, line for line (see the comments there), written out again for the reason given at
-// bscanw_kernel.
+// An sq8 corpus (STORE == NLSH_STORE_SQ8; nlsh_scan_topk_cells_phase_sq8): uint8 codes decoded per dimension with s.lo4 / s.step4 as the
+// tile is written, both k classes.  One kernel per (metric, k class) serves both filter states -- s.row_filter is a wave-uniform run-time
+// operand, as in the range kernels.  Instantiated in scan_bucket_affine.hip (profiles/sq8_storage.txt).
 template <int METRIC, int QW, int NW, int TPS, bool WIDEK>
-__global__ __launch_bounds__(64 * NW, 1) void bscana_kernel(BArgs a, QuantArgs q) {
+__global__ __launch_bounds__(64 * NW, 1) void bscana_kernel(BArgs a, SideArgs s) {
     constexpr int RS = NLSH_TILED_KB + 1;
     __shared__ float4 tile[64 * TPS * RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
-    long long ntasks = a.status[0];
-    if (ntasks > a.max_tasks) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
-        ntasks = a.max_tasks;
-    }
-    constexpr int XC = 16;
-    const long long j = blockIdx.x >> 3;
-    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
-    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
-    const int4 desc = a.task[tc];
-    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
-    if (t >= ntasks) return;
-    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, NLSH_STORE_SQ8>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, nullptr, nullptr, &q);
+    NLSH_TILED_PICK(a);
+    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, NLSH_STORE_SQ8>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, &s);
 }
 
-// The tiled scan behind per-query tag filters (TAGS of tiled_task_body; nlsh_scan_topk_cells_phase_tagged / _sq8_tagged), every storage --
-// NLSH_STORE_SQ8 among them: the quantiser rides in TagArgs --, k <= 64 (WIDEK false) and k in 65..NLSH_MAX_K_TILED (true).  One kernel per
-// (metric, storage, k class) serves the three match modes and both filter states: g.match and g.row_filter are wave-uniform run-time
-// operands.  TagArgs is a SECOND kernel parameter: BArgs and every kernel above keep their layout and their code (profiles/row_tags.txt).
-// Instantiated in scan_bucket_tagged.hip, a translation unit of its own.  The task pick is bscan3_kernel's, line for line (see the
-// comments there), written out again for the reason given at bscanw_kernel.
+// Behind per-query tag filters (TAGS of tiled_task_body; nlsh_scan_topk_cells_phase_tagged / _sq8_tagged), every storage -- NLSH_STORE_SQ8
+// among them --, both k classes.  One kernel per (metric, storage, k class) serves the three match modes and both filter states: s.match
+// and s.row_filter are wave-uniform run-time operands.  Instantiated in scan_bucket_tagged.hip (profiles/row_tags.txt).
 template <int METRIC, int QW, int NW, int TPS, int STORE, bool WIDEK>
-__global__ __launch_bounds__(64 * NW, 1) void bscang_kernel(BArgs a, TagArgs g) {
+__global__ __launch_bounds__(64 * NW, 1) void bscang_kernel(BArgs a, SideArgs s) {
     constexpr int RS = NLSH_TILED_KB + 1;
     __shared__ float4 tile[64 * TPS * RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
-    long long ntasks = a.status[0];
-    if (ntasks > a.max_tasks) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.status[1], 1);
-        ntasks = a.max_tasks;
-    }
-    constexpr int XC = 16;
-    const long long j = blockIdx.x >> 3;
-    const long long t = ((j / XC) * 8 + (blockIdx.x & 7)) * XC + (j % XC);
-    const long long tc = t < a.max_tasks ? t : a.max_tasks - 1;
-    const int4 desc = a.task[tc];
-    const int2 qr_all = a.task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];
-    if (t >= ntasks) return;
-    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE, false, false, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, nullptr, nullptr, nullptr, &g);
+    NLSH_TILED_PICK(a);
+    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, STORE, false, false, true>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, &s);
 }
 
 }  // namespace nlsh

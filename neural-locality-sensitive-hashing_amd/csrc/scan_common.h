@@ -436,13 +436,13 @@ struct BucketScanCall {
     int storage;                  // NLSH_STORE_*: what `corpus` really points to (row_stride in elements); anything but F32 is the tiled
                                   // schedule's alone (0 = F32 for every entry without a storage argument)
     const uint32_t *row_filter;   // bitset over the sorted rows (nlsh_row_filter_build) or nullptr: the tiled schedule's alone; the SCAN phase
-                                  // then launches a filtered kernel, which takes the pointer as a second parameter (BArgs does not hold it)
+                                  // then launches a filtered kernel, which reads it from its second parameter (SideArgs; BArgs does not hold it)
     bool affine;                  // nlsh_scan_topk_cells_phase_sq8: `corpus` holds sq8 codes in the uint8 layout (storage = NLSH_STORE_U8) and the
-                                  // SCAN phase launches an affine kernel, which takes the quantiser (and the filter) as a second parameter
+                                  // SCAN phase launches an affine kernel, which reads the quantiser (and the filter) from its second parameter
     const float *quant_lo;        // affine: [row_stride] per-dimension offsets, padded to the pitch with 0 (device, 16-byte aligned)
     const float *quant_step;      // affine: [row_stride] per-dimension steps, padded with 1
     const uint64_t *row_tags;     // nlsh_scan_topk_cells_phase_tagged / _sq8_tagged: [N] tag word of every sorted row, or nullptr: no tags.  The
-                                  // tiled schedule's alone; the SCAN phase then launches a tagged kernel, whose second parameter (TagArgs) holds
+                                  // tiled schedule's alone; the SCAN phase then launches a tagged kernel, whose second parameter (SideArgs) holds
                                   // the tags, the masks, the mode, the filter and -- affine -- the quantiser
     const uint64_t *query_masks;  // [Q] mask of every query; given iff row_tags is
     int tag_match;                // NLSH_TAG_ANY | NLSH_TAG_ALL | NLSH_TAG_EQ; looked at only with row_tags
@@ -476,12 +476,12 @@ int bucket_scan_run(const BucketScanCall &c);         // scan_bucket.hip
 inline int scan_call_run(const BucketScanCall &c) { return c.algo == NLSH_SCAN_QUERY_MAJOR ? query_major_run(c) : bucket_scan_run(c); }
 // the tiled scan kernel over a float16 / uint8 corpus (scan_bucket_typed.hip): storage NLSH_STORE_F16 | NLSH_STORE_U8, wide = k > NLSH_MAX_K
 const void *typed_scan_kernel_of(int storage, int metric, bool wide);
-// the tiled scan kernel behind a row filter (scan_bucket_filtered.hip): any storage; its parameters are (BArgs, const uint32_t *row_filter)
+// the tiled scan kernel behind a row filter (scan_bucket_filtered.hip): any storage; its parameters are (BArgs, SideArgs: scan_bucket_args.h), like the next two
 const void *filtered_scan_kernel_of(int storage, int metric, bool wide);
-// the tiled scan kernel over an sq8 corpus (scan_bucket_affine.hip): its parameters are (BArgs, QuantArgs), the filter inside the second
+// the tiled scan kernel over an sq8 corpus (scan_bucket_affine.hip), the quantiser and the filter inside the second parameter
 const void *affine_scan_kernel_of(int metric, bool wide);
 // the tiled scan kernel behind per-query tag filters (scan_bucket_tagged.hip): any storage, NLSH_STORE_SQ8 (scan_bucket_args.h) for an
-// affine call; its parameters are (BArgs, TagArgs), the filter and the quantiser inside the second
+// affine call; tags, masks, mode, the filter and the quantiser inside the second parameter
 const void *tagged_scan_kernel_of(int storage, int metric, bool wide);
 
 }  // namespace nlsh

@@ -440,7 +440,7 @@ extern "C" size_t nlsh_scan_workspace(int64_t Q, int P, int k, int64_t max_tasks
     return w.total > b ? w.total : b;
 }
 
-// The five top-k entry points: fill, check, run.  The descriptor with what they all have, under the header's parameter names:
+// The top-k entry points: fill, check, run.  The descriptor with what they all have, under the header's parameter names:
 #define NLSH_TOPK_CALL(c)                                                                                                          \
     BucketScanCall c = {};                                                                                                         \
     NLSH_SCAN_CALL_COMMON(c);                                                                                                      \
@@ -474,95 +474,74 @@ extern "C" int nlsh_scan_topk_phase(const float *corpus_sorted, int64_t row_stri
     return topk_call("scan_topk_phase", c);
 }
 
-extern "C" int nlsh_scan_topk_cells_phase(const float *corpus_sorted, int64_t row_stride, int d, const int32_t *gid,
-                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
-                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
-                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
-                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
-                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
-                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases) {
-    NLSH_TOPK_CALL(c);
-    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
-    c.phases = phases;
-    return topk_call("scan_topk_cells_phase", c);
-}
-
-extern "C" int nlsh_scan_topk_cells_phase_typed(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
-                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
-                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
-                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
-                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
-                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
-                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases) {
-    NLSH_TOPK_CALL(c);
-    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
-    c.phases = phases; c.storage = storage;
-    return topk_call("scan_topk_typed", c);
-}
-
-extern "C" int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
-                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
-                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
-                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
-                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
-                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
-                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
-                              const uint32_t *row_filter) {
+// The six entries with cells fill their descriptor in two places, one per family: the narrower entries of a family are its widest one
+// without the trailing arguments, under a name of their own in the refusals (`who`).
+#define NLSH_CELLS_PARAMS                                                                                                          \
+    int64_t row_stride, int d, const int32_t *gid, const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order,   \
+    int32_t n_buckets, const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells, const float *inv_norm,                 \
+    const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric,        \
+    int algo, int seg_rows, float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand, int32_t *status,             \
+    void *workspace, size_t workspace_bytes, int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream,       \
+    int phases
+#define NLSH_CELLS_ARGS                                                                                                            \
+    row_stride, d, gid, uniq_keys, offsets, bucket_order, n_buckets, cell_of, cell_offsets, n_cells, inv_norm, queries, q_stride, Q, \
+    qkeys, nkeys, P, k, metric, algo, seg_rows, out_dist, out_idx, out_keys, out_ncand, status, workspace, workspace_bytes,         \
+    max_tasks, ev_scan_begin, ev_scan_end, stream, phases
+// the cells / typed / filtered / tagged family
+static int cells_topk_call(const char *who, const void *corpus_sorted, int storage, NLSH_CELLS_PARAMS, const uint32_t *row_filter,
+                           const uint64_t *row_tags, const uint64_t *query_masks, int tag_match) {
     NLSH_TOPK_CALL(c);
     c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
     c.phases = phases; c.storage = storage; c.row_filter = row_filter;
+    c.row_tags = row_tags; c.query_masks = query_masks; c.tag_match = tag_match;
+    return topk_call(who, c);
+}
+// the sq8 / sq8_tagged family: uint8 layout, the quantiser beside it
+static int sq8_topk_call(const char *who, const uint8_t *corpus_sorted, const float *lo, const float *step, NLSH_CELLS_PARAMS,
+                         const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks, int tag_match) {
+    NLSH_TOPK_CALL(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
+    c.phases = phases; c.storage = NLSH_STORE_U8; c.row_filter = row_filter;
+    c.affine = true; c.quant_lo = lo; c.quant_step = step;
+    c.row_tags = row_tags; c.query_masks = query_masks; c.tag_match = tag_match;
+    return topk_call(who, c);
+}
+
+extern "C" int nlsh_scan_topk_cells_phase(const float *corpus_sorted, NLSH_CELLS_PARAMS) {
+    return cells_topk_call("scan_topk_cells_phase", corpus_sorted, NLSH_STORE_F32, NLSH_CELLS_ARGS, nullptr, nullptr, nullptr, 0);
+}
+
+extern "C" int nlsh_scan_topk_cells_phase_typed(const void *corpus_sorted, int storage, NLSH_CELLS_PARAMS) {
+    return cells_topk_call("scan_topk_typed", corpus_sorted, storage, NLSH_CELLS_ARGS, nullptr, nullptr, nullptr, 0);
+}
+
+extern "C" int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, int storage, NLSH_CELLS_PARAMS, const uint32_t *row_filter) {
     // without a filter this IS the typed call (include/nlsh_hip.h), and says so in its refusals
-    return topk_call(row_filter ? "scan_topk_filtered" : "scan_topk_typed", c);
+    return cells_topk_call(row_filter ? "scan_topk_filtered" : "scan_topk_typed", corpus_sorted, storage, NLSH_CELLS_ARGS, row_filter, nullptr, nullptr, 0);
 }
 
 // The filtered call over an sq8 corpus: uint8 layout, the quantiser behind the filter.  Not a fourth storage code of the typed calls
 // (they answer NLSH_E_INVALID to anything past NLSH_STORE_U8): an entry of its own.
-extern "C" int nlsh_scan_topk_cells_phase_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d,
-                              const int32_t *gid, const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
-                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
-                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
-                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
-                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
-                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
-                              const uint32_t *row_filter) {
-    NLSH_TOPK_CALL(c);
-    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
-    c.phases = phases; c.storage = NLSH_STORE_U8; c.row_filter = row_filter;
-    c.affine = true; c.quant_lo = lo; c.quant_step = step;
-    return topk_call("scan_topk_sq8", c);
+extern "C" int nlsh_scan_topk_cells_phase_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, NLSH_CELLS_PARAMS,
+                                              const uint32_t *row_filter) {
+    return sq8_topk_call("scan_topk_sq8", corpus_sorted, lo, step, NLSH_CELLS_ARGS, row_filter, nullptr, nullptr, 0);
 }
 
 // The filtered call behind per-query tag filters: without row_tags it IS the filtered call, and says so in its refusals.
-extern "C" int nlsh_scan_topk_cells_phase_tagged(const void *corpus_sorted, int storage, int64_t row_stride, int d, const int32_t *gid,
-                              const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
-                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
-                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
-                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
-                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
-                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
-                              const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks, int tag_match) {
-    NLSH_TOPK_CALL(c);
-    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
-    c.phases = phases; c.storage = storage; c.row_filter = row_filter;
-    c.row_tags = row_tags; c.query_masks = query_masks; c.tag_match = tag_match;
-    return topk_call((row_tags || query_masks) ? "scan_topk_tagged" : (row_filter ? "scan_topk_filtered" : "scan_topk_typed"), c);
+extern "C" int nlsh_scan_topk_cells_phase_tagged(const void *corpus_sorted, int storage, NLSH_CELLS_PARAMS, const uint32_t *row_filter,
+                                                 const uint64_t *row_tags, const uint64_t *query_masks, int tag_match) {
+    return cells_topk_call((row_tags || query_masks) ? "scan_topk_tagged" : (row_filter ? "scan_topk_filtered" : "scan_topk_typed"), corpus_sorted,
+                           storage, NLSH_CELLS_ARGS, row_filter, row_tags, query_masks, tag_match);
 }
 
-extern "C" int nlsh_scan_topk_cells_phase_sq8_tagged(const uint8_t *corpus_sorted, const float *lo, const float *step, int64_t row_stride, int d,
-                              const int32_t *gid, const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order, int32_t n_buckets,
-                              const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
-                              const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q, const int32_t *qkeys, const int32_t *nkeys,
-                              int P, int k, int metric, int algo, int seg_rows, float *out_dist, int32_t *out_idx,
-                              uint64_t *out_keys, int32_t *out_ncand, int32_t *status, void *workspace, size_t workspace_bytes,
-                              int64_t max_tasks, void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
-                              const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks, int tag_match) {
-    NLSH_TOPK_CALL(c);
-    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
-    c.phases = phases; c.storage = NLSH_STORE_U8; c.row_filter = row_filter;
-    c.affine = true; c.quant_lo = lo; c.quant_step = step;
-    c.row_tags = row_tags; c.query_masks = query_masks; c.tag_match = tag_match;
-    return topk_call((row_tags || query_masks) ? "scan_topk_sq8_tagged" : "scan_topk_sq8", c);
+extern "C" int nlsh_scan_topk_cells_phase_sq8_tagged(const uint8_t *corpus_sorted, const float *lo, const float *step, NLSH_CELLS_PARAMS,
+                                                     const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks,
+                                                     int tag_match) {
+    return sq8_topk_call((row_tags || query_masks) ? "scan_topk_sq8_tagged" : "scan_topk_sq8", corpus_sorted, lo, step, NLSH_CELLS_ARGS, row_filter,
+                         row_tags, query_masks, tag_match);
 }
+#undef NLSH_CELLS_PARAMS
+#undef NLSH_CELLS_ARGS
 
 extern "C" int nlsh_merge_topk(const uint64_t *keys_in, int64_t row_stride, int G, int64_t Q, int k, const int32_t *ncand_in,
                                float *out_dist, int32_t *out_idx, int32_t *out_ncand, nlsh_stream_t stream) {

@@ -118,3 +118,31 @@ def test_compare_classes_two_builds_of_a_kernel():
     hot = old[:4] + [old[5], old[4]] + old[6:]
     assert isa_lint.compare(old, hot, res, dict(res)) == "d"
     assert isa_lint.compare(old, old + ["s_nop 0"], res, dict(res)) == "d"              # another instruction count
+
+
+def test_compare_pairs_kernels_by_template_when_their_parameters_changed():
+    """`--pair-by-template`: a kernel template whose PARAMETER types changed has another mangled name, and by full name counts as two
+    unmatched kernels; cut behind the template argument list the old and the new instantiation meet.  Two synthetic listings."""
+    def listing(kernels):
+        return "\n".join("%s:\n%s\n.Lfunc_end%d:\n" % (name, "\n".join("\t" + s for s in body), i) for i, (name, body) in enumerate(kernels))
+    body = ["s_load_dwordx2 s[2:3], s[0:1], 0x0", "s_waitcnt lgkmcnt(0)", "v_mov_b32 v0, s2", "s_endpgm"]
+    moved = [body[0].replace("0x0", "0x18")] + body[1:]                                   # the same program, the argument at another offset
+    old = listing([("_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb0EEEvNS_5BArgsEPKj", body), ("_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb1EEEvNS_5BArgsEPKj", body),
+                   ("_ZN4nlsh13bscan3_kernelILi0ELi4EEEvNS_5BArgsE", body), ("_Z5plainPKfi", body)])
+    new = listing([("_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb0EEEvNS_5BArgsENS_8SideArgsE", moved), ("_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb1EEEvNS_5BArgsENS_8SideArgsE", body),
+                   ("_ZN4nlsh13bscan3_kernelILi0ELi4EEEvNS_5BArgsE", body), ("_Z5plainPKfi", body)])
+    key = isa_lint.template_key
+    assert key("_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb1EEEvNS_5BArgsEPKj") == "_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb1EE"
+    assert key("_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb1EEEvNS_5BArgsENS_8SideArgsE") == "_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb1EE"
+    # nested template arguments, enum literals and substitutions are walked, not cut at their first E; a plain function is its own key
+    assert key("_ZN2ns6kernelINS_6configILj256ELNS_6methodE3ELS2_3EEEPfEEvT_T0_") == "_ZN2ns6kernelINS_6configILj256ELNS_6methodE3ELS2_3EEEPfE"
+    assert key("_Z3fooIiEvT_") == "_Z3fooIiE" and key("_Z5plainPKfi") == "_Z5plainPKfi" and key("main") == "main"
+    by_name = isa_lint.compare_builds(old, "", new, "")
+    assert sorted(by_name.values()) == ["a", "a", "d", "d", "d", "d"] and by_name["_Z5plainPKfi"] == "a"
+    by_key = isa_lint.compare_builds(old, "", new, "", key)
+    assert by_key == {"_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb0EEEvNS_5BArgsENS_8SideArgsE": "c",     # reported under the NEW name
+                      "_ZN4nlsh13bscanf_kernelILi0ELi4ELi0ELb1EEEvNS_5BArgsENS_8SideArgsE": "a",
+                      "_ZN4nlsh13bscan3_kernelILi0ELi4EEEvNS_5BArgsE": "a", "_Z5plainPKfi": "a"}
+    # two kernels of ONE build under one key (overloads of a template) pair nothing: they are held by name
+    twice = listing([("_Z3fooIiEvT_", body), ("_Z3fooIiEvT_i", body)])
+    assert isa_lint.compare_builds(twice, "", listing([("_Z3fooIiEvT_", body)]), "", key) == {"_Z3fooIiEvT_": "a", "_Z3fooIiEvT_i": "d"}

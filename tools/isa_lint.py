@@ -19,7 +19,9 @@ landing on one) is a violation.  Resource figures come from `-Rpass-analysis=ker
 
 `--compare OLD.s` classes every kernel of the source against an earlier build of it instead (a refactor's proof that the shipped code
 did not move): OLD.s is what `hipcc <BASE_FLAGS> -S --cuda-device-only -Rpass-analysis=kernel-resource-usage` wrote for the old
-source, OLD.remarks beside it that command's stderr.  See `compare`.
+source, OLD.remarks beside it that command's stderr.  See `compare`.  Kernels are paired by their full mangled names; `--pair-by-template`
+pairs them by the name cut behind the template argument list (`template_key`), so that a kernel whose parameter types changed meets its
+old build instead of counting as two unmatched kernels.
 """
 import collections
 import argparse
@@ -243,9 +245,69 @@ def compare(old, new, old_res=None, new_res=None):
     return "d"
 
 
-def compare_builds(old_asm, old_remarks, new_asm, new_remarks):
-    """{kernel: class} over the kernels of either build (one that exists in only one of them is "d")."""
+_SUBST = re.compile(r"S[0-9A-Z]*_|S[a-z]|T[0-9]*_|D[a-z]")
+
+
+def _ident(s, i):
+    """Index behind the <length><identifier> at s[i]."""
+    j = i
+    while s[j].isdigit():
+        j += 1
+    return j + int(s[i:j])
+
+
+def _item(s, i):
+    """Index behind one item of an Itanium-mangled name at s[i]: an identifier, a substitution, a builtin type or qualifier letter, a
+    literal (L <type> <value> E) or a group (N | I | J | F ... E).  Raises ValueError / IndexError on anything else."""
+    c = s[i]
+    if c.isdigit():
+        return _ident(s, i)
+    if c in "NIJF":
+        i += 1
+        while s[i] != "E":
+            i = _item(s, i)
+        return i + 1
+    if c == "L":
+        if s[i + 1] == "_":
+            raise ValueError(s)              # a literal that names a function or an object
+        return s.index("E", _item(s, i + 1)) + 1
+    m = _SUBST.match(s, i)
+    if m:
+        return m.end()
+    if c.isalpha() and c not in "AMXUu":     # array, member-pointer, expression and vendor types: not parsed here
+        return i + 1
+    raise ValueError(s)
+
+
+def template_key(name):
+    """The mangled name cut behind the template argument list of the function itself: `_ZN4nlsh6kernelILi0ELb1EEEvNS_1AEPKj` ->
+    `_ZN4nlsh6kernelILi0ELb1EE`.  What `--pair-by-template` pairs the kernels of two builds by: a kernel template whose PARAMETER types
+    changed keeps this key.  A name without template arguments, or one this small parser does not read, is its own key."""
+    try:
+        i = 3 if name.startswith("_ZN") else 2
+        if not name.startswith("_Z"):
+            return name
+        while name[i] != "I":
+            m = _SUBST.match(name, i)
+            if not (m or name[i].isdigit()):
+                return name
+            i = m.end() if m else _ident(name, i)
+        return name[:_item(name, i)]
+    except (ValueError, IndexError):
+        return name
+
+
+def compare_builds(old_asm, old_remarks, new_asm, new_remarks, key=None):
+    """{kernel: class} over the kernels of either build (one that exists in only one of them is "d").  `key` (template_key): kernels are
+    paired by key(name) instead of by name and reported under the new build's name; a key that two kernels of ONE build share pairs
+    nothing, and those kernels are held by name."""
     fo, fn, ro, rn = functions(old_asm), functions(new_asm), resources(old_remarks), resources(new_remarks)
+    if key:
+        count = collections.Counter([key(k) for k in fo] + [key(k) for k in fn])
+        alias = {key(k): k for k in fn if count[key(k)] == 2}
+        to_new = {k: alias[key(k)] for k in fo if key(k) in alias}
+        fo = {to_new.get(k, k): v for k, v in fo.items()}
+        ro = {to_new.get(k, k): v for k, v in ro.items()}
     return {k: compare(fo[k], fn[k], ro.get(k), rn.get(k)) if k in fo and k in fn else "d" for k in sorted(set(fo) | set(fn))}
 
 
@@ -270,11 +332,14 @@ def main():
     ap.add_argument("--match", default="bscan3_kernel")
     ap.add_argument("--extra", action="append", default=[])
     ap.add_argument("--compare", metavar="OLD.s", help="class every kernel of --src against this earlier build (see compare)")
+    ap.add_argument("--pair-by-template", action="store_true",
+                    help="with --compare: pair kernels by the mangled name cut behind the template argument list (a kernel whose parameter types changed still meets its old build)")
     args = ap.parse_args()
     if args.compare:
         remarks = os.path.splitext(args.compare)[0] + ".remarks"
         asm, new_remarks = compile_asm(args.src, tuple(args.extra))
-        rep = compare_builds(open(args.compare).read(), open(remarks).read() if os.path.exists(remarks) else "", asm, new_remarks)
+        rep = compare_builds(open(args.compare).read(), open(remarks).read() if os.path.exists(remarks) else "", asm, new_remarks,
+                             template_key if args.pair_by_template else None)
         res = resources(new_remarks)
         for name, cls in rep.items():
             print(cls, name, len(functions(asm).get(name, ())), "lines", res.get(name, {}))
