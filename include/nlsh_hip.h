@@ -71,6 +71,7 @@ enum { NLSH_SCAN_QUERY_MAJOR = 0, NLSH_SCAN_BUCKET_MAJOR = 1, NLSH_SCAN_BUCKET_T
 #define NLSH_MAX_DIM 1024   /* vector dimension of corpus / queries for the scan */
 #define NLSH_MAX_WIDTH 632  /* widest HIDDEN encoder layer the LDS-resident MLP supports (the input may be NLSH_MAX_DIM wide) */
 #define NLSH_MAX_STREAM_WIDTH 4096  /* widest HIDDEN encoder layer of the streamed form (nlsh_encode_hash_stream) */
+#define NLSH_MAX_BINS 4096  /* bins of a Categorical hash (nlsh_encode_logits, nlsh_probe_bins): = NLSH_MAX_STREAM_WIDTH, a width the layer GEMM takes */
 
 int nlsh_abi_version(void);
 const char *nlsh_last_error(void);
@@ -215,6 +216,69 @@ int nlsh_probe_ranked_budget(const float *z, int64_t z_stride, const uint32_t *c
                              const int32_t *uniq_keys, const int32_t *offsets, int32_t n_buckets, int32_t budget,
                              int32_t *keys_out, int32_t *nkeys_out, float *cost_out /* nullable */, int32_t *ncand_out /* nullable */,
                              nlsh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Categorical (softmax-bin) hashing.  Replaces the forward and `hash` of the reference's `Categorical` (nlsh/hashings.py:95-139):
+ * encoder -> Linear(hash_size = M bins) -> softmax, bucket = argmax bin; multi-probe = the next most probable bins.  Softmax is
+ * monotone in the logits, so the device works on logits alone: a forward that leaves [n, M] logits, and a kernel that ranks a row's bins.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The logits forward: nlsh_encode_hash_stream's layer stack (its blob layout, one fp32-MFMA GEMM launch per Linear layer, ReLU behind
+ * every layer but the last) with an output layer of dims[n_layers] = M bins, 1 <= M <= NLSH_MAX_BINS, and no epilogue.  A logit is one
+ * k-ascending chain from 0 over the last hidden activation, then the bias: the oracle's mlp_forward arithmetic, bit for bit.
+ * Limits: n_layers in [1, NLSH_MAX_LAYERS] (a single Linear layer is legal), dims[0] <= NLSH_MAX_DIM, hidden dims[l] <=
+ * NLSH_MAX_STREAM_WIDTH.  The hashing calls above keep refusing an output layer wider than NLSH_MAX_HASH_BITS. */
+
+/* Floats of the blob (-1 for a shape outside the limits) and the pack call: nlsh_encoder_stream_pack's arguments and layout. */
+int64_t nlsh_logits_packed_floats(int n_layers, const int *dims);
+int nlsh_logits_pack(int n_layers, const int *dims, const float *const *W, const float *const *b,
+                     float *packed, nlsh_stream_t stream);
+
+/* Workspace bytes of a pass of `rows_per_pass` rows (rounded up to the 128-row tile): the hidden activation images, plus a padded
+ * logits image when M is no multiple of 32.  At least 16 (a single layer of a 32-multiple width needs none); 0 for a shape outside
+ * the limits. */
+size_t nlsh_logits_workspace(int64_t rows_per_pass, int n_layers, const int *dims);
+
+/* x [dev] fp32 [n, d], row stride x_stride >= d (any alignment);  logits_out [dev] fp32 [n, M], row stride logits_stride >= M:
+ * columns >= M of the caller's rows are never written.  workspace [dev], 16-byte aligned: the rows are processed in passes of as many
+ * 128-row tiles as it holds (at least one: NLSH_E_WORKSPACE otherwise); the outputs do not depend on its size.
+ * Checked before anything touches the device: the limits (NLSH_E_INVALID / NLSH_E_UNSUPPORTED), n < 0, a stride below its width,
+ * NULL pointers with n > 0 (NLSH_E_INVALID).  n = 0 is NLSH_OK without a launch. */
+int nlsh_encode_logits(const float *x, int64_t n, int64_t x_stride, int n_layers, const int *dims, const float *packed,
+                       float *logits_out, int64_t logits_stride, void *workspace, size_t workspace_bytes, nlsh_stream_t stream);
+
+/* The n_probes best bins of every row, best first: a Categorical hash's keys (slot 0 = the bucket, the reference's probs.argmax(1);
+ * the rest = its multi-probe).  No reference counterpart for n_probes > 1 (its hash() is single-probe).
+ *   logits [dev] fp32 [n, M] with row stride logits_stride >= M (any alignment; 16-byte-aligned rows are loaded 16 bytes per lane)
+ *   keys_out [n, n_probes], nkeys_out [n] (required);  logit_out [n, n_probes] fp32 (nullable)
+ * A row's result is a pure function of its M logits, n_probes and whether its index is < n_multi_rows:
+ *   1. u(z) is the IEEE total-order map of z's bit pattern to uint32: a negative pattern (sign bit set) is complemented, a
+ *      non-negative one gets its sign bit set.  So -0 < +0, -inf is lowest and +inf highest.
+ *   2. Bins are ordered by (u(z[b]) descending, b ascending).
+ *   3. The first min(n_probes, M) bins are the row's keys, in that order; key = bin index as int32.
+ *   4. Rows >= n_multi_rows keep slot 0 alone (Indexer.hash's trailing-batch rule).
+ *   5. Unused slots are 0; nkeys = the number kept.
+ *   6. logit_out holds the kept bins' logits bit for bit, -inf past nkeys.
+ *   7. A NaN is a precondition violation: the order is then unspecified, but the kernel stays inside its buffers (it makes at most
+ *      min(n_probes, M) rounds and indexes its LDS image by bin index alone).
+ * Checked on the host before anything touches the device: NULL required pointers, n < 0, logits_stride < M (NLSH_E_INVALID); M outside
+ * [1, NLSH_MAX_BINS], n_probes outside [1, NLSH_MAX_ENCODE_PROBES] (NLSH_E_UNSUPPORTED).  n = 0 is NLSH_OK without a launch. */
+int nlsh_probe_bins(const float *logits, int64_t logits_stride, int64_t n, int M, int n_probes, int64_t n_multi_rows,
+                    int32_t *keys_out, int32_t *nkeys_out, float *logit_out /* nullable */, nlsh_stream_t stream);
+
+/* nlsh_probe_bins with nlsh_probe_ranked_budget's per-row CANDIDATE BUDGET, applied to this key order (uniq_keys, offsets, n_buckets,
+ * budget, ncand_out as there).  For one row let K[0..nk) be the keys nlsh_probe_bins writes; size(key) = offsets[b+1] - offsets[b] if
+ * uniq_keys[b] == key for some b, else 0; cum(m) = sum of size(K[i]) over i < m.  Then
+ *   nkeys_out = min{ m in [1, nk] : cum(m) >= budget }, or nk if there is none  (slot 0 is always kept; rows >= n_multi_rows keep it
+ *   alone);  keys_out = K[0..nkeys_out) then zeros;  logit_out = the kept logits then -inf;  ncand_out = cum(nkeys_out).
+ * The result is a prefix of the unbudgeted row; with budget = INT32_MAX it is nlsh_probe_bins' output in every word.  The selection
+ * loop itself ends at the stop (nothing is enumerated and then cut).
+ * Checked on the host first: budget < 1, n_buckets < 0, NULL uniq_keys or offsets with n_buckets > 0 (NLSH_E_INVALID), then every
+ * refusal of nlsh_probe_bins.  n_buckets == 0 is legal (every size is 0, no row stops early); n = 0 is NLSH_OK without a launch. */
+int nlsh_probe_bins_budget(const float *logits, int64_t logits_stride, int64_t n, int M, int n_probes, int64_t n_multi_rows,
+                           const int32_t *uniq_keys, const int32_t *offsets, int32_t n_buckets, int32_t budget,
+                           int32_t *keys_out, int32_t *nkeys_out, float *logit_out /* nullable */, int32_t *ncand_out /* nullable */,
+                           nlsh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Index build.  Replaces build_index (nlsh/indexer.py:6-24): key -> ascending row list, as CSR.

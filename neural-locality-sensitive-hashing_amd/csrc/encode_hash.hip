@@ -1277,3 +1277,135 @@ extern "C" int nlsh_encode_hash_stream(const float *x, int64_t n, int64_t x_stri
     }
     return NLSH_OK;
 }
+
+// ================================================================================================================================
+// The logits forward (nlsh_encode_logits): the streamed layer stack with an output layer of up to NLSH_MAX_BINS columns and no
+// epilogue -- the forward of a Categorical (softmax-bin) hash, whose bins nlsh_probe_bins ranks.  Every layer runs on
+// encode_layer_kernel in the hidden layers' geometry, the last one without ReLU: one k-ascending chain per logit, then the bias.
+// The kernel writes whole 32-column tiles, so logits of a width that is no multiple of 32 go through a padded image in the workspace
+// and are copied out M columns per row (columns >= M of the caller's rows are never written); other widths are written in place.
+namespace nlsh {
+
+#define NLSH_LAYER_LOGITS encode_layer_kernel<2, 2, 2, 2, false>
+constexpr long long SL_MAX_PASS = 1ll << 20;   // rows of a pass, whatever the workspace holds: bounds the grid of a layer launch
+
+__global__ void copy_logits_kernel(const float *__restrict__ src, int src_stride, long long n, int M, float *__restrict__ dst,
+                                   long long dst_stride) {
+    const long long total = n * M;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        const long long r = e / M;
+        const int c = (int)(e - r * M);
+        dst[r * dst_stride + c] = src[r * src_stride + c];
+    }
+}
+
+static int check_logits_dims(int n_layers, const int *dims) {
+    NLSH_REQUIRE(dims != nullptr && n_layers >= 1 && n_layers <= NLSH_MAX_LAYERS, NLSH_E_INVALID,
+                 "encoder (logits): n_layers=%d out of range [1,%d]", n_layers, NLSH_MAX_LAYERS);
+    for (int l = 0; l <= n_layers; ++l) NLSH_REQUIRE(dims[l] >= 1, NLSH_E_INVALID, "encoder (logits): dims[%d]=%d", l, dims[l]);
+    NLSH_REQUIRE(dims[0] <= NLSH_MAX_DIM, NLSH_E_UNSUPPORTED, "encoder (logits): input width %d > %d", dims[0], NLSH_MAX_DIM);
+    for (int l = 1; l < n_layers; ++l)
+        NLSH_REQUIRE(dims[l] <= NLSH_MAX_STREAM_WIDTH, NLSH_E_UNSUPPORTED, "encoder (logits): hidden width %d > %d", dims[l],
+                     NLSH_MAX_STREAM_WIDTH);
+    NLSH_REQUIRE(dims[n_layers] <= NLSH_MAX_BINS, NLSH_E_UNSUPPORTED, "encoder (logits): %d bins > NLSH_MAX_BINS=%d", dims[n_layers],
+                 NLSH_MAX_BINS);
+    return NLSH_OK;
+}
+
+// floats per row of a pass: the activation images of the streamed form, then the padded logits image where the width needs one
+static void logits_row_floats(int n_layers, const int *dims, int *WS, int *nbuf, int *Mp, long long *per_row) {
+    stream_row_floats(n_layers, dims, WS, nbuf, per_row);
+    const int M = dims[n_layers];
+    *Mp = M % 32 ? round_up(M, 32) : 0;
+    *per_row += *Mp - SL_ZS;
+}
+
+}  // namespace nlsh
+
+extern "C" int64_t nlsh_logits_packed_floats(int n_layers, const int *dims) {
+    if (check_logits_dims(n_layers, dims) != NLSH_OK) return -1;
+    LayerDesc L[NLSH_MAX_LAYERS];
+    return fill_stream_layers(n_layers, dims, L);
+}
+
+extern "C" int nlsh_logits_pack(int n_layers, const int *dims, const float *const *W, const float *const *b, float *packed,
+                                nlsh_stream_t stream) {
+    int rc = check_logits_dims(n_layers, dims);
+    if (rc != NLSH_OK) return rc;
+    NLSH_REQUIRE(W != nullptr && b != nullptr && packed != nullptr, NLSH_E_INVALID, "logits_pack: null pointer");
+    LayerDesc L[NLSH_MAX_LAYERS];
+    fill_stream_layers(n_layers, dims, L);
+    for (int l = 0; l < n_layers; ++l) {
+        NLSH_REQUIRE(W[l] != nullptr, NLSH_E_INVALID, "logits_pack: W[%d] is null", l);
+        const long long tot = (long long)L[l].Np * L[l].Kp;
+        const int grid = (int)std::min((tot + 255) / 256, 4096ll);
+        hipLaunchKernelGGL(pack_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W[l], b[l], L[l].K, L[l].N, L[l].Kp,
+                           L[l].Np, packed + L[l].w_off, packed + L[l].b_off);
+        NLSH_CHECK_HIP(hipGetLastError());
+    }
+    return NLSH_OK;
+}
+
+extern "C" size_t nlsh_logits_workspace(int64_t rows_per_pass, int n_layers, const int *dims) {
+    if (check_logits_dims(n_layers, dims) != NLSH_OK || rows_per_pass < 0) return 0;
+    int WS, nbuf, Mp;
+    long long per_row;
+    logits_row_floats(n_layers, dims, &WS, &nbuf, &Mp, &per_row);
+    const long long rows = ((rows_per_pass < 1 ? 1 : rows_per_pass) + SL_BM - 1) / SL_BM * SL_BM;
+    return (size_t)std::max(rows * per_row * 4, 16ll);   // a single Linear layer of a 32-multiple width needs nothing: 0 stays the refusal
+}
+
+extern "C" int nlsh_encode_logits(const float *x, int64_t n, int64_t x_stride, int n_layers, const int *dims, const float *packed,
+                                  float *logits_out, int64_t logits_stride, void *workspace, size_t workspace_bytes,
+                                  nlsh_stream_t stream) {
+    int rc = check_logits_dims(n_layers, dims);
+    if (rc != NLSH_OK) return rc;
+    const int M = dims[n_layers];
+    NLSH_REQUIRE(n >= 0, NLSH_E_INVALID, "encode_logits: n=%lld", (long long)n);
+    NLSH_REQUIRE(logits_stride >= M, NLSH_E_INVALID, "encode_logits: logits_stride %lld < M %d", (long long)logits_stride, M);
+    NLSH_REQUIRE(x_stride >= dims[0], NLSH_E_INVALID, "encode_logits: x_stride %lld < d %d", (long long)x_stride, dims[0]);
+    if (n == 0) return NLSH_OK;
+    NLSH_REQUIRE(x && packed && logits_out && workspace, NLSH_E_INVALID, "encode_logits: null pointer");
+    NLSH_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, NLSH_E_INVALID, "encode_logits: workspace not 16-byte aligned");
+    int WS, nbuf, Mp;
+    long long per_row;
+    logits_row_floats(n_layers, dims, &WS, &nbuf, &Mp, &per_row);
+    long long R = per_row ? (long long)(workspace_bytes / ((size_t)per_row * 4)) / SL_BM * SL_BM : SL_MAX_PASS;   // rows per pass
+    NLSH_REQUIRE(R >= SL_BM && workspace_bytes >= 16, NLSH_E_WORKSPACE, "encode_logits: workspace %zu B < one %d-row tile (%lld B)",
+                 workspace_bytes, SL_BM, std::max((long long)SL_BM * per_row * 4, 16ll));
+    R = std::min(R, SL_MAX_PASS);
+    LayerDesc L[NLSH_MAX_LAYERS];
+    fill_stream_layers(n_layers, dims, L);
+    float *ws = static_cast<float *>(workspace);
+    float *buf[2] = {ws, ws + (nbuf > 1 ? R * WS : 0)};
+    float *lb = ws + (long long)nbuf * R * WS;   // the padded logits image (Mp != 0)
+    hipStream_t s = (hipStream_t)stream;
+    for (long long p0 = 0; p0 < n; p0 += R) {
+        const long long np = std::min(R, (long long)n - p0), nrb = (np + SL_BM - 1) / SL_BM;
+        const float *src = x + p0 * x_stride;
+        long long src_stride = x_stride;
+        for (int l = 0; l < n_layers; ++l) {
+            const bool last = l + 1 == n_layers;
+            float *dst = !last ? buf[l & 1] : Mp ? lb : logits_out + p0 * logits_stride;
+            const long long dst_stride = !last ? WS : Mp ? Mp : (long long)logits_stride;
+            const int K = l == 0 ? L[l].K : L[l].Kp;   // as in nlsh_encode_hash_stream: later layers read whole padded rows
+            const float *Wl = packed + L[l].w_off, *bl = packed + L[l].b_off;
+            const long long grid = nrb * ((L[l].Np + SL_BN_HIDDEN - 1) / SL_BN_HIDDEN);
+            if (last)
+                hipLaunchKernelGGL(NLSH_LAYER_LOGITS, dim3((unsigned)grid), dim3(256), 0, s, src, src_stride, K, L[l].Kp, np, Wl, bl, L[l].Np,
+                                   dst, dst_stride);
+            else
+                hipLaunchKernelGGL(NLSH_LAYER_HIDDEN, dim3((unsigned)grid), dim3(256), 0, s, src, src_stride, K, L[l].Kp, np, Wl, bl, L[l].Np,
+                                   dst, dst_stride);
+            NLSH_CHECK_HIP(hipGetLastError());
+            src = dst; src_stride = dst_stride;
+        }
+        if (Mp) {
+            const long long tot = np * M;
+            hipLaunchKernelGGL(copy_logits_kernel, dim3((unsigned)std::min((tot + 255) / 256, 65536ll)), dim3(256), 0, s, lb, Mp, np, M,
+                               logits_out + p0 * logits_stride, (long long)logits_stride);
+            NLSH_CHECK_HIP(hipGetLastError());
+        }
+    }
+    return NLSH_OK;
+}

@@ -30,6 +30,7 @@ PROBE_RANKED_ROWS_PER_WORKGROUP = 4  # nlsh_probe_ranked: one wavefront per row,
 # NLSH_ENC_FORM_*: the kernel form nlsh_encode_hash takes for a shape (nlsh_encode_form reads the library's own choice back)
 ENC_FORM_H16, ENC_FORM_SINGLE, ENC_FORM_SINGLE_WIDE, ENC_FORM_BUILD128, ENC_FORM_PINGPONG, ENC_FORM_HET = 0, 1, 2, 3, 4, 5
 ENC_FORM_NAMES = ("H16", "SINGLE", "SINGLE_WIDE", "BUILD128", "PINGPONG", "HET")
+MAX_BINS = 4096  # bins of a Categorical hash (NLSH_MAX_BINS): the widest output layer of nlsh_encode_logits, the widest row of nlsh_probe_bins
 MAX_STREAM_WIDTH = 4096  # widest hidden layer of the streamed encoder form (nlsh_encode_hash_stream); MAX_WIDTH: the LDS-resident forms
 
 # every symbol include/nlsh_hip.h declares (tests/test_host_cpu.py::test_capi_library_exports_every_declared_symbol checks the header against this)
@@ -44,6 +45,7 @@ SYMBOLS = (
     "nlsh_query_batch_host",
     "nlsh_exact_workspace", "nlsh_exact_topk",
     "nlsh_probe_ranked", "nlsh_probe_ranked_budget",
+    "nlsh_logits_packed_floats", "nlsh_logits_pack", "nlsh_logits_workspace", "nlsh_encode_logits", "nlsh_probe_bins", "nlsh_probe_bins_budget",
     "nlsh_query_batch_ranked_scratch", "nlsh_query_batch_ranked",
     "nlsh_csr_update_workspace", "nlsh_csr_update",
     "nlsh_scan_topk_cells_phase_typed", "nlsh_gather_rows_typed", "nlsh_csr_update_typed",
@@ -222,6 +224,18 @@ def lib():
     L.nlsh_probe_ranked.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp]
     L.nlsh_probe_ranked_budget.restype = i32
     L.nlsh_probe_ranked_budget.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.nlsh_logits_packed_floats.restype = i64
+    L.nlsh_logits_packed_floats.argtypes = [i32, vp]
+    L.nlsh_logits_pack.restype = i32
+    L.nlsh_logits_pack.argtypes = [i32, vp, vp, vp, vp, vp]
+    L.nlsh_logits_workspace.restype = sz
+    L.nlsh_logits_workspace.argtypes = [i64, i32, vp]
+    L.nlsh_encode_logits.restype = i32          # x, n, x_stride | n_layers, dims, packed | logits_out, logits_stride | workspace, bytes, stream
+    L.nlsh_encode_logits.argtypes = [vp, i64, i64, i32, vp, vp, vp, i64, vp, sz, vp]
+    L.nlsh_probe_bins.restype = i32             # logits, stride, n, M, n_probes, n_multi_rows | keys_out, nkeys_out, logit_out, stream
+    L.nlsh_probe_bins.argtypes = [vp, i64, i64, i32, i32, i64, vp, vp, vp, vp]
+    L.nlsh_probe_bins_budget.restype = i32      # ... n_multi_rows | uniq_keys, offsets, n_buckets, budget | keys_out, nkeys_out, logit_out, ncand_out, stream
+    L.nlsh_probe_bins_budget.argtypes = [vp, i64, i64, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.nlsh_query_batch_ranked_scratch.restype = sz
     L.nlsh_query_batch_ranked_scratch.argtypes = [i64, i32]
     L.nlsh_query_batch_ranked.restype = i32     # desc, sizeof(desc), queries, q_stride, lookup_done, budget, scratch, bytes, host_out, words, scan events, stream

@@ -245,6 +245,9 @@ class ShardedIndexer:
         if kw.get("tags") is not None:
             raise NotImplementedError("ShardedIndexer takes no tags= / tag_mask: the row exchange moves rows, ids and keys, not row tags "
                                       "(DESIGN.md 7)")
+        if getattr(hashing, "hash_family", None) == "categorical":
+            raise NotImplementedError("ShardedIndexer takes no Categorical hasher: a sharded query runs pipelined batch slots, which launch "
+                                      "the Bernoulli encode only (DESIGN.md 7)")
         if shard not in ("buckets", "rows"):
             raise ValueError("shard must be 'buckets' or 'rows'")
         if kw.get("storage") not in (None, "float32"):

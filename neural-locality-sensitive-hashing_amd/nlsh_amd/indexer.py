@@ -925,6 +925,9 @@ class Indexer:
             raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"hash_times={hash_times} > {_capi.MAX_ENCODE_PROBES}")
         h = self._hashing
         q = self._as_queries(query_vectors)
+        if hasattr(h, "hash_budget_device"):    # a family that ranks its own keys (Categorical: bins, not bit codes)
+            return h.hash_budget_device(q, hash_times, self._n_multi_rows(q.shape[0], batch_size), self.uniq_keys, self.offsets,
+                                        self.n_buckets, budget, out=out)
         z, code = h.encode_device(q)
         B, H, dev = q.shape[0], z.shape[1], q.device
         if out is not None:

@@ -66,6 +66,9 @@ class QueryPipeline:
         if getattr(indexer, "storage", "float32") != "float32":
             raise NotImplementedError(f"pipelined batches (staged and graph slots) take float32 indexes only, not storage={indexer.storage!r}: "
                                       "the step descriptor has no storage field")
+        if getattr(indexer._hashing, "hash_family", None) == "categorical":
+            raise _capi.NlshHipError(_capi.E_UNSUPPORTED, "pipelined batches (staged and graph slots) take no Categorical hasher: its keys "
+                                                          "come from nlsh_encode_logits + nlsh_probe_bins, which no batch slot launches")
         streamed = getattr(indexer._hashing, "streamed", None)
         if streamed is not None and streamed():
             raise _capi.NlshHipError(_capi.E_UNSUPPORTED, f"pipelined batches take encoders with hidden layers <= {_capi.MAX_WIDTH} wide, "

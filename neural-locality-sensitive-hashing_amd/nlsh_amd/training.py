@@ -128,3 +128,72 @@ def load_weights(hashing, arrays) -> None:
             lin.weight.copy_(torch.as_tensor(arrays[f"W{i}"]))
             if lin.bias is not None and f"b{i}" in arrays:
                 lin.bias.copy_(torch.as_tensor(arrays[f"b{i}"]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Partition (Categorical) hashes: the Neural LSH recipe -- partition the training set, then fit a classifier to the partition.
+
+def kmeans_partition(x: torch.Tensor, n_bins: int, iters: int = 10, seed: int = 0) -> torch.Tensor:
+    """Lloyd's k-means labels int64 [n] in [0, n_bins) of the device rows `x`: centroids start at `n_bins` distinct random rows (`seed`),
+    every assignment is the exact nearest centroid (`exact_topk(..., k=1)`: (distance, centroid id) order, so ties are settled), an
+    empty bin keeps its centroid."""
+    from .exact import exact_topk
+    n = x.shape[0]
+    if not 1 <= n_bins <= n:
+        raise ValueError(f"n_bins must be in [1, {n}], got {n_bins}")
+    gen = torch.Generator(device=x.device)
+    gen.manual_seed(seed)
+    x = x.float()
+    centroids = x[torch.randperm(n, generator=gen, device=x.device)[:n_bins]].contiguous()
+    labels = None
+    for it in range(max(int(iters), 0) + 1):
+        labels = exact_topk(x, centroids, 1)[1][:, 0].long()
+        if it == iters:
+            break
+        sums = torch.zeros_like(centroids).index_add_(0, labels, x)
+        counts = torch.bincount(labels, minlength=n_bins)
+        live = counts > 0
+        centroids = torch.where(live[:, None], sums / counts.clamp_min(1)[:, None].float(), centroids).contiguous()
+    return labels
+
+
+def partition_targets(labels: torch.Tensor, n_bins: int, knn: Optional[torch.Tensor] = None, soft_k: int = 10) -> torch.Tensor:
+    """Training targets float32 [n, n_bins] of a partition: one-hot labels, or with `knn` (row ids [n, >= soft_k]) the Neural LSH soft
+    target -- the bin histogram of the row's first `soft_k` neighbours, normalised to sum 1."""
+    if knn is None:
+        return F.one_hot(labels, n_bins).float()
+    near = labels[knn[:, :soft_k]]                                  # [n, k'] bins of the neighbours
+    hist = torch.zeros((labels.shape[0], n_bins), dtype=torch.float32, device=labels.device)
+    hist.scatter_add_(1, near, torch.ones_like(near, dtype=torch.float32))
+    return hist / hist.sum(1, keepdim=True)
+
+
+def fit_partition(hashing, x: torch.Tensor, labels: torch.Tensor, knn: Optional[torch.Tensor] = None, soft_k: int = 10,
+                  n_steps: int = 1000, batch_size: int = 1024, learning_rate: float = 1e-3, seed: int = 0,
+                  log: Optional[Callable[[str], None]] = None, log_every: int = 0) -> List[float]:
+    """Fit a `Categorical` hash (anything with `parameters()`, `train_mode()` and a `predict()` that returns bin probabilities with
+    gradients in train mode) to a partition of the rows `x`: Adam on the cross-entropy between `predict(x)` and `partition_targets`.
+    Plain torch autograd, outside the hot path.  -> the loss of every step.  Leaves the hashing in eval mode."""
+    n, n_bins = x.shape[0], int(hashing.output_dim)
+    targets = partition_targets(labels, n_bins, knn, soft_k)
+    gen = torch.Generator(device=x.device)
+    gen.manual_seed(seed)
+    opt = torch.optim.Adam(list(hashing.parameters()), lr=learning_rate)
+    losses = []
+    hashing.train_mode(True)
+    while len(losses) < n_steps:
+        order = torch.randperm(n, generator=gen, device=x.device)
+        for s in range(0, n, batch_size):
+            rows = order[s:s + batch_size]
+            opt.zero_grad()
+            p = hashing.predict(x[rows])
+            loss = -(targets[rows] * torch.log(p.clamp_min(1e-30))).sum(1).mean()
+            loss.backward()
+            opt.step()
+            losses.append(float(loss.detach()))
+            if log is not None and log_every and len(losses) % log_every == 0:
+                log(f"[fit_partition] step {len(losses)} loss {losses[-1]:.4f}")
+            if len(losses) >= n_steps:
+                break
+    hashing.train_mode(False)
+    return losses
