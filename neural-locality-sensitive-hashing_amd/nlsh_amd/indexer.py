@@ -104,6 +104,19 @@ def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
+def _addr(t):
+    """Address of a tensor that may be absent."""
+    return None if t is None else t.data_ptr()
+
+
+def _event_handles(events):
+    """The (begin, end) handles of a call's `events=` pair, (None, None) without one."""
+    return (events[0].cuda_event, events[1].cuda_event) if events else (None, None)
+
+
+_no_pause = contextlib.nullcontext()    # `query()` with `pause_collector_for_call` off: one object for every call, it holds no state
+
+
 # `nlsh_scan_topk_cells_phase`'s arguments either side of (queries, q_stride), by their names in `Indexer._scan_fields`
 _SCAN_ARGS_BEFORE_QUERIES = operator.itemgetter("corpus_sorted", "row_stride", "d", "gid", "uniq_keys", "offsets", "bucket_order", "n_buckets",
                                                 "cell_of", "cell_offsets", "n_cells", "inv_norm")
@@ -1033,6 +1046,11 @@ class Indexer:
             got = self._cells[window_rows] = (cell_of, cell_offsets[:nc + 1], cell_order[:max(nc, 1)], nc)
         return got
 
+    def _cells_or_buckets(self, window):
+        """(cell_of, cell_offsets, order, n_cells) as a launch takes them: the cells of a row window, or -- window 0 -- none of them and
+        the buckets in `bucket_order`."""
+        return self.cells(window) if window else (None, None, self.bucket_order, 0)
+
     def choose_window(self, Q, P, algo):
         """Row window of the small-bucket packing for one batch shape (tiled schedule only): 64 rows unless forced.
         Measured (r04, tools/scan_bench.py --window 0,64,128,256 --rounds 4, same process and keys, scan kernel ms, one box):
@@ -1217,14 +1235,10 @@ class Indexer:
         field names of `_capi.StepDesc`: `_scan_launch` passes them to `nlsh_scan_topk_cells_phase_filtered`, `_step_desc` fills a descriptor
         from them.  Callers that launch many batches (the kept range plans, nlsh_amd/pipeline.py) build them once per buffer set; a
         call is then one ctypes transition."""
-        a = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (the tensors that may be absent)
-        metric = self._metric_code()
+        a, metric = _addr, self._metric_code()
         if window is None:
             window = self.choose_window(Q, keys.shape[1], algo)
-        if window and algo == _capi.SCAN_BUCKET_TILED:
-            cell_of, cell_offsets, order, n_cells = self.cells(window)
-        else:
-            cell_of, cell_offsets, order, n_cells = None, None, self.bucket_order, 0
+        cell_of, cell_offsets, order, n_cells = self._cells_or_buckets(window if algo == _capi.SCAN_BUCKET_TILED else 0)
         return {"corpus_sorted": self.corpus_sorted.data_ptr(), "row_stride": self.row_stride, "d": d, "gid": self.gid.data_ptr(),
                 "uniq_keys": self.uniq_keys.data_ptr(), "offsets": self.offsets.data_ptr(), "bucket_order": order.data_ptr(),
                 "n_buckets": self.n_buckets, "cell_of": a(cell_of), "cell_offsets": a(cell_offsets), "n_cells": n_cells,
@@ -1264,8 +1278,7 @@ class Indexer:
             filter = filter.row_filter
         _capi.check(call(
             before[0], *store, *before[1:], q.data_ptr(), q.stride(0) if Q else d, *_SCAN_ARGS_AFTER_QUERIES(f),
-            events[0].cuda_event if events else None, events[1].cuda_event if events else None,
-            _stream(q.device) if stream is None else stream, phases, None if filter is None else filter.words.data_ptr(), *tail))
+            *_event_handles(events), _stream(q.device) if stream is None else stream, phases, None if filter is None else filter.words.data_ptr(), *tail))
 
     def _scan_sliced(self, q, keys, nkeys, k, want_keys, check, filter=None):
         """hash_times > 64 (eval.py:148 sweeps n_samples up to 100): the key table is scanned in column slices of
@@ -1319,17 +1332,24 @@ class Indexer:
             raise NotImplementedError("radius (range) queries are not built for storage='sq8': the range kernels read float32, float16 "
                                       "and uint8 rows only (DESIGN.md 7)")
 
+    def _range_call_checks(self, what, filter, tag_mask):
+        """What every range call refuses before it does anything, in this order -> the checked filter."""
+        self._refuse_tags(what, tag_mask)
+        self._refuse_refine(what)
+        self._refuse_range_on_sq8()
+        filter = self._checked_filter(filter)
+        if self.metric not in ("l2", "cosine"):
+            raise NotImplementedError("range queries need metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
+        return filter
+
     def _metric_code(self):
         return (_capi.METRIC_L2_EPS_FOLDED if self.l2_form == "folded" else _capi.METRIC_L2_EPS) if self.metric == "l2" else _capi.METRIC_COSINE
 
     def _range_head(self, q, keys, nkeys, window, filter, rad):
         """The arguments `nlsh_range_count` and `nlsh_range_fill` share, in their order: index, queries, key table, metric, schedule,
         filter words (or None) and radii."""
-        a = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        if window:
-            cell_of, cell_offsets, order, n_cells = self.cells(window)
-        else:
-            cell_of, cell_offsets, order, n_cells = None, None, self.bucket_order, 0
+        a = _addr
+        cell_of, cell_offsets, order, n_cells = self._cells_or_buckets(window)
         return (self.corpus_sorted.data_ptr(), _STORAGES[self.storage][1], self.row_stride, q.shape[1], self.gid.data_ptr(),
                 self.uniq_keys.data_ptr(), self.offsets.data_ptr(), order.data_ptr(), self.n_buckets, a(cell_of), a(cell_offsets), n_cells,
                 a(self.inv_norm), q.data_ptr(), q.stride(0), q.shape[0], keys.data_ptr(), nkeys.data_ptr(), keys.shape[1],
@@ -1345,12 +1365,7 @@ class Indexer:
         limit (None = off): ValueError once the counts are known and before any output is allocated, if T > limit.
         Two scan launches with one host read between them (`nlsh_range_count`, `nlsh_range_fill`): the call synchronises.  Always the
         tiled schedule, as filtered and compressed calls; key tables wider than 64 probes are refused."""
-        self._refuse_tags("range_scan_tensors", tag_mask)
-        self._refuse_refine("range_scan_tensors")
-        self._refuse_range_on_sq8()
-        filter = self._checked_filter(filter)
-        if self.metric not in ("l2", "cosine"):
-            raise NotImplementedError("range queries need metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
+        filter = self._range_call_checks("range_scan_tensors", filter, tag_mask)
         q = self._as_queries(query_vectors)
         Q, d = q.shape
         if d != self.dim:
@@ -1366,7 +1381,6 @@ class Indexer:
         algo, stream, L = _capi.SCAN_BUCKET_TILED, _stream(dev), _capi.lib()
         pack = torch.empty((2 * Q + 2,), dtype=torch.int32, device=dev)     # one copy brings counts, candidate counts and status to the host
         count, ncand, status = pack.split((Q, Q, 2))
-        a = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         if Q == 0:
             return (torch.zeros((1,), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.int32, device=dev),
                     torch.empty((0,), dtype=torch.float32, device=dev), ncand, torch.empty((0,), dtype=torch.int64, device=dev) if want_keys else None)
@@ -1402,7 +1416,7 @@ class Indexer:
             sort_ws = torch.empty((sort_bytes,), dtype=torch.uint8, device=dev)
             cursor = torch.empty((Q,), dtype=torch.int32, device=dev)
             # the fill launch runs on the plan the count call left in `ws`: same table, same workspace, nothing in between
-            _capi.check(L.nlsh_range_fill(*head, offsets.data_ptr(), T, cursor.data_ptr(), a(keys64), dist.data_ptr(), idx.data_ptr(), *tail,
+            _capi.check(L.nlsh_range_fill(*head, offsets.data_ptr(), T, cursor.data_ptr(), _addr(keys64), dist.data_ptr(), idx.data_ptr(), *tail,
                                           sort_ws.data_ptr(), sort_bytes, None, None, stream))
         self._set_last(status, algo, window, pack, tkey, max_tasks)
         return offsets, idx, dist, ncand, keys64
@@ -1411,12 +1425,7 @@ class Indexer:
                       want_keys=False, tag_mask=None):
         """Device-resident radius query: the hash by the two-step route (`last_query_path == "two_step"`; probes / candidate_budget as in
         `query_tensors`), then `range_scan_tensors`.  hash_times <= 64."""
-        self._refuse_tags("range_tensors", tag_mask)
-        self._refuse_refine("range_tensors")
-        self._refuse_range_on_sq8()
-        filter = self._checked_filter(filter)
-        if self.metric not in ("l2", "cosine"):
-            raise NotImplementedError("range queries need metric 'l2' or 'cosine' (use SIFT.distance / Glove.distance)")
+        filter = self._range_call_checks("range_tensors", filter, tag_mask)
         if hash_times > _capi.MAX_PROBES:
             raise ValueError(f"range queries take hash_times <= {_capi.MAX_PROBES}, got {hash_times}")
         q = self._as_queries(query_vectors)
@@ -1439,29 +1448,16 @@ class Indexer:
         """Radius query in the shape `query()` returns: (List[List[int]], List[int]) -- per query the ids of every candidate within
         `radius`, in (distance, row id) order, and the candidate counts (before the radius and the filter); with return_distances=True
         also the lists of distances.  See `range_scan_tensors`."""
-        self._refuse_tags("range_query", tag_mask)
-        self._refuse_refine("range_query")
+        filter = self._range_call_checks("range_query", filter, tag_mask)
         out = self.range_tensors(query_vectors, radius, hash_times, seed, probes, candidate_budget, filter, limit)
         return self._range_lists(*out[:4], return_distances)
 
     def range_query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], radius, filter=None, return_distances=False,
                               tag_mask=None):
         """`range_query` on caller-supplied key lists, like `query_with_keys`."""
-        self._refuse_tags("range_query_with_keys", tag_mask)
-        self._refuse_refine("range_query_with_keys")
-        self._refuse_range_on_sq8()
-        filter = self._checked_filter(filter)
-        key_lists = [list(dict.fromkeys(int(key) for key in ks)) for ks in key_lists]
-        Q = len(key_lists)
-        P = max([len(ks) for ks in key_lists] + [1])
-        tab = np.zeros((Q, P), dtype=np.int64)
-        cnt = np.zeros((Q,), dtype=np.int32)
-        for i, ks in enumerate(key_lists):
-            cnt[i] = len(ks)
-            tab[i, :len(ks)] = list(ks)
-        tab = np.where(tab >= (1 << 31), tab - (1 << 32), tab).astype(np.int32)
-        dev = query_vectors.device
-        out = self.range_scan_tensors(query_vectors, torch.as_tensor(tab).to(dev), torch.as_tensor(cnt).to(dev), radius, filter=filter)
+        filter = self._range_call_checks("range_query_with_keys", filter, tag_mask)
+        _, keys, nkeys = self._pack_key_lists(key_lists, query_vectors.device)
+        out = self.range_scan_tensors(query_vectors, keys, nkeys, radius, filter=filter)
         return self._range_lists(*out[:4], return_distances)
 
     def query_tensors(self, query_vectors, k=10, hash_times=10, seed=None, want_keys=False, check=True, events=None, probes=None,
@@ -1529,15 +1525,19 @@ class Indexer:
         is a bucket-major one (the query-major stream's PLAN phase is a single kernel of its own).  A streamed encoder (hidden layer
         wider than `_capi.MAX_WIDTH`) has no fused encode launch: `hash_device` + `scan_tensors`, the same results by design.  Neither
         has a ranked hasher (`probes="ranked"`): its keys come from `nlsh_probe_ranked` behind the encode."""
+        return self._one_call_form(q, hash_times, algo, "encode_args") and getattr(self._hashing, "probes", "sampled") != "ranked"
+
+    def _one_call_form(self, q, hash_times, algo, encode_args):
+        """What `_fuses` and `_fuses_ranked` both need (`encode_args`: the hasher method that fills the form's descriptor).  The storage
+        test comes first: on a compressed index nothing else is looked at, the batch included."""
         if self.compressed:         # the step descriptor has no storage field: a compressed index hashes, then calls the typed scan
             return False
-        needs_train = getattr(self._hashing, "_needs_train_forward", None)
-        streamed = getattr(self._hashing, "streamed", None)
-        if getattr(self._hashing, "probes", "sampled") == "ranked":
-            return False
+        h = self._hashing
+        needs_train = getattr(h, "_needs_train_forward", None)
+        streamed = getattr(h, "streamed", None)
         return (self.metric in ("l2", "cosine") and 1 <= hash_times <= _capi.MAX_PROBES and algo != _capi.SCAN_QUERY_MAJOR
                 and self.n_buckets > 0 and q.shape[0] > 0 and not (needs_train is not None and needs_train())
-                and hasattr(self._hashing, "encode_args") and not (streamed is not None and streamed()))
+                and hasattr(h, encode_args) and not (streamed is not None and streamed()))
 
     # The ranked mode's one-call form (`nlsh_query_batch_ranked`: five launches, the keys looked up by the kernel that ranks them) against
     # its two-step form (`hash_device` / `_hash_budget` + `scan_tensors`: seven launches); same results, bit for bit.  OFF by default: on
@@ -1557,14 +1557,9 @@ class Indexer:
         batch, an LDS-resident encoder and no BatchNorm train-mode forward.  Everything else keeps the two-step path."""
         if self.compressed or not self.ranked_one_call:
             return False
-        h = self._hashing
         if ranked is None:
-            ranked = getattr(h, "probes", "sampled") == "ranked"
-        needs_train = getattr(h, "_needs_train_forward", None)
-        streamed = getattr(h, "streamed", None)
-        return (ranked and self.metric in ("l2", "cosine") and 1 <= hash_times <= _capi.MAX_PROBES and algo != _capi.SCAN_QUERY_MAJOR
-                and self.n_buckets > 0 and q.shape[0] > 0 and not (needs_train is not None and needs_train())
-                and hasattr(h, "ranked_encode_args") and not (streamed is not None and streamed()))
+            ranked = getattr(self._hashing, "probes", "sampled") == "ranked"
+        return bool(ranked) and self._one_call_form(q, hash_times, algo, "ranked_encode_args")
 
     def _ranked_scratch(self, m, dev):
         """Fresh scratch of one `nlsh_query_batch_ranked` call of m rows (z, hard codes, the one-probe encode's own key table)."""
@@ -1573,21 +1568,23 @@ class Indexer:
             _capi.check(_capi.E_UNSUPPORTED)
         return torch.empty((need,), dtype=torch.uint8, device=dev)
 
-    def _ranked_tensors(self, q, k, P, budget, want_keys, check, events, algo, n_multi, out=None):
-        """`_batch_tensors` of the ranked mode where `_fuses_ranked` holds: one `nlsh_query_batch_ranked` call with fresh outputs
-        (`budget` None = no budget); the retry after a task-table overflow repeats the scan part on the keys the first call left."""
+    def _one_call(self, q, k, P, want_keys, check, algo, n_multi, out, start):
+        """The launch loop of the two one-call forms (`_batch_tensors` where `_fuses` holds, `_ranked_tensors`): fresh outputs, the key
+        table `out` or a fresh one, then the call -- repeated on the keys the first one left, scan part only (`lookup_done`), while the
+        task table overflows -> (dist, idx, ncand, keys64 | None, keys, nkeys).  `start(keys, nkeys)`, called once behind the dim check
+        and the allocations, gives what is the form's own: the hasher's encode arguments for the descriptor and
+        call(desc, lookup_done, stream), which makes the C call and returns its status."""
         Q, d = q.shape
         if d != self.dim:
             raise ValueError(f"query dim {d} != corpus dim {self.dim}")
-        L, h, dev = _capi.lib(), self._hashing, q.device
+        L, dev = _capi.lib(), q.device
         if out is not None:
             keys, nkeys = out
         else:
             keys = torch.empty((Q, P), dtype=torch.int32, device=dev)
             nkeys = torch.empty((Q,), dtype=torch.int32, device=dev)
         out_dist, pack, out_idx, ncand, status, out_keys = self._outputs(Q, k, dev, want_keys)
-        enc = h.ranked_encode_args(P)               # (held to the end of the call: the descriptor names its dims array)
-        scratch = self._ranked_scratch(Q, dev)
+        enc, call = start(keys, nkeys)              # (`enc` held to the end of the call: the descriptor names its dims array)
         stream = _stream(dev)
         lookup_done = 0
         while True:
@@ -1596,9 +1593,7 @@ class Indexer:
             desc = self._step_desc(self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws,
                                                      window), enc, n_multi)
             try:
-                _capi.check(L.nlsh_query_batch_ranked(ctypes.byref(desc), ctypes.sizeof(desc), q.data_ptr(), q.stride(0), lookup_done, budget or 0,
-                                                      scratch.data_ptr(), scratch.numel(), None, 0,
-                                                      events[0].cuda_event if events else None, events[1].cuda_event if events else None, stream))
+                _capi.check(call(desc, lookup_done, stream))
             except _capi.NlshHipError:
                 self._ws.pop(wkey, None)    # a call that failed part-way may have left the counters at the head non-zero
                 raise
@@ -1609,8 +1604,20 @@ class Indexer:
                 break
             lookup_done = 1                 # task table too small, grown: repeat the scan part on the same keys
         self._set_last(status, algo, window, pack, tkey, max_tasks)
-        self.last_query_path = "ranked_one_call"
         return out_dist, out_idx, ncand, out_keys, keys, nkeys
+
+    def _ranked_tensors(self, q, k, P, budget, want_keys, check, events, algo, n_multi, out=None):
+        """`_batch_tensors` of the ranked mode where `_fuses_ranked` holds: one `nlsh_query_batch_ranked` call with fresh outputs
+        (`budget` None = no budget)."""
+        def start(keys, nkeys):
+            enc = self._hashing.ranked_encode_args(P)
+            scratch = self._ranked_scratch(q.shape[0], q.device)
+            return enc, lambda desc, lookup_done, stream: _capi.lib().nlsh_query_batch_ranked(
+                ctypes.byref(desc), ctypes.sizeof(desc), q.data_ptr(), q.stride(0), lookup_done, budget or 0, scratch.data_ptr(), scratch.numel(),
+                None, 0, *_event_handles(events), stream)
+        got = self._one_call(q, k, P, want_keys, check, algo, n_multi, out, start)
+        self.last_query_path = "ranked_one_call"
+        return got
 
     def _batch_tensors(self, query_vectors, k, hash_times, seed, want_keys=False, check=True, events=None, algo=None, row0=0,
                        n_multi=None, out=None):
@@ -1620,7 +1627,7 @@ class Indexer:
         if hash_times < 1:
             raise ValueError(f"`n` should be positive integer, but got {hash_times}")
         q = self._as_queries(query_vectors)
-        Q, d = q.shape
+        Q = q.shape[0]
         if algo is None:
             algo = self.choose_algo(Q, hash_times)
         if n_multi is None:
@@ -1635,39 +1642,12 @@ class Indexer:
             else:
                 keys, nkeys = self.hash_device(q, hash_times=hash_times, seed=seed)
             return self.scan_tensors(q, keys, nkeys, k=k, want_keys=want_keys, check=check, events=events, algo=algo, refine_k=0) + (keys, nkeys)
-        if d != self.dim:
-            raise ValueError(f"query dim {d} != corpus dim {self.dim}")
-        L, h, dev, P = _capi.lib(), self._hashing, q.device, hash_times
-        if out is not None:
-            keys, nkeys = out
-        else:
-            keys = torch.empty((Q, P), dtype=torch.int32, device=dev)
-            nkeys = torch.empty((Q,), dtype=torch.int32, device=dev)
-        out_dist, pack, out_idx, ncand, status, out_keys = self._outputs(Q, k, dev, want_keys)
-        if seed is None:
-            seed = h.next_seed()
-        enc, _ = h.encode_args(P, keys, nkeys)      # (held to the end of the call: the descriptor names its dims array)
-        stream = _stream(dev)
-        lookup_done = 0
-        while True:
-            tkey, window, max_tasks = self._task_table(algo, Q, P)
-            wkey, ws = self._workspace(dev, stream, True, L.nlsh_scan_workspace(Q, P, k, max_tasks, self.n_buckets, d))
-            desc = self._step_desc(self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws,
-                                                     window), enc, n_multi)
-            try:
-                _capi.check(L.nlsh_query_batch(ctypes.byref(desc), ctypes.sizeof(desc), q.data_ptr(), q.stride(0), seed, int(row0), lookup_done,
-                                               events[0].cuda_event if events else None, events[1].cuda_event if events else None, stream))
-            except _capi.NlshHipError:
-                self._ws.pop(wkey, None)    # a call that failed part-way may have left the counters at the head non-zero
-                raise
-            if not check:
-                break
-            needed, overflow = status.cpu().tolist()
-            if self._settle(tkey, needed, overflow, max_tasks):
-                break
-            lookup_done = 1                 # task table too small, grown: repeat the scan part on the same keys
-        self._set_last(status, algo, window, pack, tkey, max_tasks)
-        return out_dist, out_idx, ncand, out_keys, keys, nkeys
+
+        def start(keys, nkeys):     # the seed is drawn behind the dim check: a call refused there takes none
+            s = self._hashing.next_seed() if seed is None else seed
+            return self._hashing.encode_args(hash_times, keys, nkeys)[0], lambda desc, lookup_done, stream: _capi.lib().nlsh_query_batch(
+                ctypes.byref(desc), ctypes.sizeof(desc), q.data_ptr(), q.stride(0), s, int(row0), lookup_done, *_event_handles(events), stream)
+        return self._one_call(q, k, hash_times, want_keys, check, algo, n_multi, out, start)
 
     def _rows_of_key(self, key):
         """Ascending global row ids of one bucket (host list) or [] for an unknown key.  Called once per query with fewer than k
@@ -1784,6 +1764,20 @@ class Indexer:
             return ids, counts, rows[:, 1:], rows[:, 0]
         return ids, counts, a[n:n + m * P].reshape(m, P), a[n + m * P:n + m * P + m]
 
+    def _range_copied(self, q, keys, nkeys, k, lo, hi, algo, fused, block):
+        """The copy form of one row range: `_range_tensors` with the results left on the device, then device->host copies on the stream
+        into the head of the range's `block` of the pinned buffer -- ids | counts | status, and under `compat` the key table and its
+        counts.  A range that is the whole batch slices nothing: every tensor view made here is host time of the call."""
+        m, P = hi - lo, keys.shape[1]
+        self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused)
+        n = m * k + m + 2
+        to_ids, to_keys, to_nkeys, _ = block.split((n, m * P, m, block.numel() - n - m * P - m))
+        to_ids.copy_(self._last_pack, non_blocking=True)
+        if self.compat:
+            whole = m == keys.shape[0]
+            to_keys.view(m, P).copy_(keys if whole else keys[lo:hi], non_blocking=True)
+            to_nkeys.copy_(nkeys if whole else nkeys[lo:hi], non_blocking=True)
+
     def _host_results(self, q, keys, nkeys, k, fused=None, queued=None):
         """One range = the whole batch: scan, results into the pinned block, ONE stream synchronisation (the only sync of a `query()`
         call).  `queued`: called once, between the launch and that synchronisation (`_Shells.alloc`: host work that needs no result).
@@ -1802,12 +1796,7 @@ class Indexer:
             if host_form:           # the merge kernel stores into the pinned block itself: nothing to copy
                 self._range_tensors(q, keys, nkeys, k, 0, Q, algo, fused, pin[:words])
             else:
-                self._range_tensors(q, keys, nkeys, k, 0, Q, algo, fused)
-                to_ids, to_keys, to_nkeys, _ = pin.split((n, Q * P, Q, pin.numel() - words))
-                to_ids.copy_(self._last_pack, non_blocking=True)
-                if self.compat:
-                    to_keys.view(Q, P).copy_(keys, non_blocking=True)
-                    to_nkeys.copy_(nkeys, non_blocking=True)
+                self._range_copied(q, keys, nkeys, k, 0, Q, algo, fused, pin)
             self._release_held()                                    # the device is busy now: free what an earlier call left with us
             if queued is not None:
                 queued()
@@ -1854,12 +1843,7 @@ class Indexer:
             if host_form and m:     # the merge kernel stores into the range's slice of the pinned block itself: nothing to copy
                 self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused, block)
             else:
-                self._range_tensors(q, keys, nkeys, k, lo, hi, algo, fused)
-                to_ids, to_keys, to_nkeys = block.split((n, m * P, m))
-                to_ids.copy_(self._last_pack, non_blocking=True)
-                if self.compat:
-                    to_keys.view(m, P).copy_(keys[lo:hi], non_blocking=True)
-                    to_nkeys.copy_(nkeys[lo:hi], non_blocking=True)
+                self._range_copied(q, keys, nkeys, k, lo, hi, algo, fused, block)
             ev = torch.cuda.Event()
             ev.record(stream)
             return ev, self._last_tkey, self._last_max_tasks
@@ -2011,14 +1995,12 @@ class Indexer:
     # of two threads and the nested pause of `_plain_lists` leave the collector as the FIRST of them found it (r06).
     pause_collector_for_call = True
 
-    def _query_refined(self, query_vectors, k, k1, hash_times, seed, probes, candidate_budget, filter):
-        """`query()` of an index with refine=: the two-step route's key table, stage one at k1, the re-rank, one copy to the host.  The
+    def _query_two_step(self, query_vectors, k, k1, hash_times, seed, probes, candidate_budget, filter):
+        """`query()` of a filtered call (k1 = 0) and of an index with refine= (k1: stage one's k): the two-step route's key table, the
+        scan -- with the re-rank behind it, `last_query_path == "two_step+refine"` -- and one copy to the host.  Unfiltered, the
         short-query rule (F7) is applied from stage one's candidate counts, as on an unrefined index."""
-        if hash_times < 1:
-            raise ValueError(f"`n` should be positive integer, but got {hash_times}")
         keys, nkeys = self._filtered_keys(query_vectors, hash_times, seed, probes, candidate_budget)
         _, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter, refine_k=k1)
-        self.last_query_path = "two_step+refine"
         if filter is not None:
             return self._filtered_lists(idx, ncand, keys64)
         idx_h, nc_h = np.ascontiguousarray(idx.cpu().numpy()), ncand.cpu().numpy()
@@ -2040,25 +2022,17 @@ class Indexer:
         lists and counts follow the rules of a filtered call."""
         filter = self._checked_filter(filter, None, tag_mask, tag_match, query_vectors)
         k1 = self._refine_k1(k, refine_k)
-        if k1:
-            with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
-                return self._keep(self._query_refined(query_vectors, k, k1, hash_times, seed, probes, candidate_budget, filter))
-        if filter is not None:
-            with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
-                keys, nkeys = self._filtered_keys(query_vectors, hash_times, seed, probes, candidate_budget)
-                _, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter, refine_k=0)
-                return self._keep(self._filtered_lists(idx, ncand, keys64))
-        if candidate_budget is not None:
-            budget = self._candidate_budget(candidate_budget, probes)
-            with _collector_pause if self.pause_collector_for_call else contextlib.nullcontext():
-                return self._keep(self._query(query_vectors, k, hash_times, seed, budget))
-        if probes is not None:
-            with self._probe_mode(probes):
-                return self.query(query_vectors, k, hash_times, seed)
-        if not self.pause_collector_for_call:
-            return self._keep(self._query(query_vectors, k, hash_times, seed))
-        with _collector_pause:
-            return self._keep(self._query(query_vectors, k, hash_times, seed))
+        with _collector_pause if self.pause_collector_for_call else _no_pause:
+            if k1 or filter is not None:
+                result = self._query_two_step(query_vectors, k, k1, hash_times, seed, probes, candidate_budget, filter)
+            elif candidate_budget is not None:
+                result = self._query(query_vectors, k, hash_times, seed, self._candidate_budget(candidate_budget, probes))
+            elif probes is not None:        # the call again with the mode on the hasher: it keeps its own result
+                with self._probe_mode(probes):
+                    return self.query(query_vectors, k, hash_times, seed)
+            else:
+                result = self._query(query_vectors, k, hash_times, seed)
+            return self._keep(result)
 
     def _query(self, query_vectors, k, hash_times, seed, budget=None):
         self.last_query_path = "two_step"
@@ -2072,13 +2046,7 @@ class Indexer:
         if self._fuses_ranked(q, hash_times, self.choose_algo(Q, hash_times), ranked=True if budget is not None else None):
             # every row range is ranked, looked up and scanned by ONE call (five launches) into its rows of the batch's key table, which is
             # kept per (stream, batch shape): two streams never share one
-            tab = self.__dict__.setdefault("_ranked_key_tables", {})
-            tkey_ = (_stream(q.device), q.device, Q, hash_times)
-            if tkey_ not in tab:
-                if len(tab) > 8:
-                    tab.clear()
-                tab[tkey_] = (torch.empty((Q, hash_times), dtype=torch.int32, device=q.device), torch.empty((Q,), dtype=torch.int32, device=q.device))
-            keys, nkeys = tab[tkey_]
+            keys, nkeys = self._kept_key_table("_ranked_key_tables", (_stream(q.device), q.device, Q, hash_times))
             fused = ("ranked", budget or 0, self._n_multi_rows(Q))
             self.last_query_path = "ranked_one_call"
         elif budget is not None:            # ranked keys cut at the candidate budget, two steps
@@ -2087,13 +2055,7 @@ class Indexer:
             self.last_query_path = "fused"
             # every row range is hashed and scanned by ONE call (five launches); the ranges share the batch's key table, seed and the
             # Philox counters of its rows, so the split changes no key
-            tab = self.__dict__.setdefault("_key_tables", {})
-            tkey_ = (q.device, Q, hash_times)
-            if tkey_ not in tab:          # the batch's key table is consumed inside the call (pinned copy for the F7 rule): kept per batch shape
-                if len(tab) > 8:
-                    tab.clear()
-                tab[tkey_] = (torch.empty((Q, hash_times), dtype=torch.int32, device=q.device), torch.empty((Q,), dtype=torch.int32, device=q.device))
-            keys, nkeys = tab[tkey_]
+            keys, nkeys = self._kept_key_table("_key_tables", (q.device, Q, hash_times))
             fused = (hash_times, self._hashing.next_seed() if seed is None else seed, self._n_multi_rows(Q))
         else:
             keys, nkeys = self.hash_device(q, hash_times=hash_times, seed=seed)
@@ -2101,26 +2063,41 @@ class Indexer:
             _, idx, ncand, _ = self.scan_tensors(q, keys, nkeys, k=k, refine_k=0)
             idx_h, nc_h = idx.cpu().numpy(), ncand.cpu().numpy()
             keys_h, nkeys_h = (keys.cpu().numpy(), nkeys.cpu().numpy()) if self.compat else (None, None)
-        elif self._n_chunks() > 1 and q.shape[0] >= self._n_chunks() * self._CHUNK_MIN_ROWS:
-            shells = self._shells(Q, k)
-            if shells is not None:      # containers while range 1 scans, every range's ids into its rows as its event completes
-                for lo, hi, idx_h, nc_h, keys_h, nkeys_h in self._chunked_results(q, keys, nkeys, k, self._n_chunks(), fused, shells.alloc):
-                    self._fill_range(shells, lo, hi, idx_h, nc_h, keys_h, nkeys_h, k)
-                return shells.rows, shells.counts
-            results, counts = [], []
-            for lo, hi, idx_h, nc_h, keys_h, nkeys_h in self._chunked_results(q, keys, nkeys, k, self._n_chunks(), fused):
-                r, c = self._to_lists(self._short_key_sets(nc_h, keys_h, nkeys_h, k), idx_h, nc_h, k)
+            return self._to_lists(self._short_key_sets(nc_h, keys_h, nkeys_h, k), idx_h, nc_h, k)
+        # the containers (`shells`, where the two-phase construction runs) are built while the device scans: between the launch and the
+        # stream synchronisation of a single range, while range 1 scans of several -- whose ids then land as each range's event completes
+        shells, chunks = self._shells(Q, k), self._n_chunks()
+        queued = None if shells is None else shells.alloc
+        if chunks > 1 and Q >= chunks * self._CHUNK_MIN_ROWS:
+            ranges = self._chunked_results(q, keys, nkeys, k, chunks, fused, queued)
+        else:                           # one range in the shape of several: a tuple, no generator on the default path
+            ranges = ((0, Q) + self._host_results(q, keys, nkeys, k, fused, queued),)
+        if shells is not None:
+            for lo, hi, idx_h, nc_h, keys_h, nkeys_h in ranges:
+                self._fill_range(shells, lo, hi, idx_h, nc_h, keys_h, nkeys_h, k)
+            return shells.rows, shells.counts
+        results = counts = None
+        for _, _, idx_h, nc_h, keys_h, nkeys_h in ranges:
+            r, c = self._to_lists(self._short_key_sets(nc_h, keys_h, nkeys_h, k), idx_h, nc_h, k)
+            if results is None:         # the first range's lists are the result's: a single range is handed on as it was built
+                results, counts = r, c
+            else:
                 results += r
                 counts += c
-            return results, counts
-        else:
-            shells = self._shells(Q, k)
-            if shells is not None:      # containers between the launch and the stream synchronisation, one fill behind it
-                idx_h, nc_h, keys_h, nkeys_h = self._host_results(q, keys, nkeys, k, fused, shells.alloc)
-                self._fill_range(shells, 0, Q, idx_h, nc_h, keys_h, nkeys_h, k)
-                return shells.rows, shells.counts
-            idx_h, nc_h, keys_h, nkeys_h = self._host_results(q, keys, nkeys, k, fused)
-        return self._to_lists(self._short_key_sets(nc_h, keys_h, nkeys_h, k), idx_h, nc_h, k)
+        return results, counts
+
+    def _kept_key_table(self, cache, ckey):
+        """The (keys [Q, P], nkeys [Q]) table `query()` keeps per batch shape in the dictionary named `cache` (`_key_tables`: the fused
+        form, `_ranked_key_tables`: the ranked one-call form, per stream as well -- the two never share a table); `ckey` ends in
+        (device, Q, P).  The table is consumed inside the call (pinned copy for the F7 rule); a caller sweeping shapes keeps at most nine."""
+        tab = self.__dict__.setdefault(cache, {})
+        got = tab.get(ckey)
+        if got is None:
+            if len(tab) > 8:
+                tab.clear()
+            dev, Q, P = ckey[-3:]
+            got = tab[ckey] = (torch.empty((Q, P), dtype=torch.int32, device=dev), torch.empty((Q,), dtype=torch.int32, device=dev))
+        return got
 
     def _short_key_sets(self, nc_h, keys_h, nkeys_h, k):
         """{query: its key set} for the queries with < k candidates: F7 (compat) needs their key SETS (Python iteration order) only."""
@@ -2136,14 +2113,11 @@ class Indexer:
             q = q.float().contiguous()
         return q
 
-    def query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], k=10, filter=None, refine_k=None, tag_mask=None,
-                        tag_match="any"):
-        """Scan stage on caller-supplied key lists (each in the iteration order the caller saw):
-        parity on identical candidate sets, independent of hashing (SURVEY F8).  `filter`: as in `query` (allowed ids only, list lengths
-        from the sort keys, no F7 rule, candidate counts before the filter).  `tag_mask` / `tag_match`: as in `query`."""
-        filter = self._checked_filter(filter, None, tag_mask, tag_match, query_vectors)
-        self._refine_k1(k, refine_k)        # refused before anything is copied to the device
-        # a query's keys are a set (nlsh/utils.pyx:27-31): a repeated key probes its bucket once; first-occurrence order kept
+    @staticmethod
+    def _pack_key_lists(key_lists, dev):
+        """Caller-supplied key lists -> (the lists de-duplicated, keys int32 [Q, P] and nkeys int32 [Q] on `dev`).  A query's keys are a
+        set (nlsh/utils.pyx:27-31): a repeated key probes its bucket once, first-occurrence order kept; the table is padded to the
+        longest list (P >= 1) and holds keys >= 2^31 as the same 32 bits, signed."""
         key_lists = [list(dict.fromkeys(int(key) for key in ks)) for ks in key_lists]
         Q = len(key_lists)
         P = max([len(ks) for ks in key_lists] + [1])
@@ -2151,11 +2125,18 @@ class Indexer:
         cnt = np.zeros((Q,), dtype=np.int32)
         for i, ks in enumerate(key_lists):
             cnt[i] = len(ks)
-            tab[i, :len(ks)] = list(ks)
+            tab[i, :len(ks)] = ks
         tab = np.where(tab >= (1 << 31), tab - (1 << 32), tab).astype(np.int32)
-        dev = query_vectors.device
-        keys = torch.as_tensor(tab).to(dev)
-        nkeys = torch.as_tensor(cnt).to(dev)
+        return key_lists, torch.as_tensor(tab).to(dev), torch.as_tensor(cnt).to(dev)
+
+    def query_with_keys(self, query_vectors, key_lists: Sequence[Sequence[int]], k=10, filter=None, refine_k=None, tag_mask=None,
+                        tag_match="any"):
+        """Scan stage on caller-supplied key lists (each in the iteration order the caller saw):
+        parity on identical candidate sets, independent of hashing (SURVEY F8).  `filter`: as in `query` (allowed ids only, list lengths
+        from the sort keys, no F7 rule, candidate counts before the filter).  `tag_mask` / `tag_match`: as in `query`."""
+        filter = self._checked_filter(filter, None, tag_mask, tag_match, query_vectors)
+        self._refine_k1(k, refine_k)        # refused before anything is copied to the device
+        key_lists, keys, nkeys = self._pack_key_lists(key_lists, query_vectors.device)
         if filter is not None:
             dist, idx, ncand, keys64 = self.scan_tensors(query_vectors, keys, nkeys, k=k, want_keys=True, filter=filter, refine_k=refine_k)
             return self._filtered_lists(idx, ncand, keys64) + (dist, idx)
