@@ -693,6 +693,54 @@ int nlsh_scan_topk_cells_phase_sq8_tagged(const uint8_t *corpus_sorted, const fl
                                           const uint32_t *row_filter, const uint64_t *row_tags, const uint64_t *query_masks, int tag_match);
 
 /* ---------------------------------------------------------------------------------------------
+ * pq corpus storage: product quantisation, M = ceil(d / dsub) bytes per row.  The reference names it (nlsh/hashings.py ends in an empty
+ * ProductQuantization class) and has nothing to compare with.
+ *
+ * THE RULE.
+ *   quantiser  a codebook C, float32 [M, 256, dsub], finite, dsub in {4, 8, 16}, M = ceil(d / dsub), 16-byte aligned.  Columns of the last
+ *              sub-vector at or beyond d are held as +0 (the Python facade zeroes them on intake; these calls read what they are given).
+ *   decode     row element j is C[j / dsub][code[j / dsub]][j % dsub]: a copy, no arithmetic.
+ *   encode     per sub-vector m, code[m] is the centroid c with the smallest s(c): acc = 0.0f; for j ascending over the sub-vector's
+ *              columns below d: t = x_j - C[m][c][j]; acc = acc + t * t -- a separate IEEE float32 subtract, multiply and add (the
+ *              library is built with -ffp-contract=off).  Ties go to the lowest c.  A row holding a NaN or an infinity is refused by its
+ *              number (first_bad, as in the sq8 calls: the smallest such row, -1 for none; the codes are then to be dropped).  Nothing
+ *              saturates, so nothing is counted as clamped.
+ *   cosine     inv_norm of a stored row is the float32 path's rule (nlsh_gather_rows) applied to the decoded row: the same operations
+ *              in the same order.
+ *   keys       the bucket keys of a pq corpus are the hasher's keys of the DECODED rows, unless the caller gives keys.
+ * A pq index is, by definition, the float32 index over the decoded rows: every array and every result bit of the scan call below equals
+ * what the float32 calls give on those rows.  The sorted copy is a uint8 row store of width M (pitch a multiple of 16 bytes, bytes behind
+ * M stored as 0): nlsh_gather_rows_typed with a NLSH_STORE_U8 source and destination builds it, nlsh_csr_update_typed mutates it (codes
+ * encoded first), and nlsh_pq_inv_norm computes the cosine norms of the result afterwards.  The typed calls keep refusing every storage
+ * code past NLSH_STORE_U8.
+ *
+ * nlsh_pq_encode: rows [dev] of `storage` (NLSH_STORE_F32 | NLSH_STORE_F16) elements, [n, d] with row stride row_stride elements (any
+ *   alignment of the element size) -> codes [dev] uint8 [n, M] in the rows' order, code_pitch >= M bytes between rows (only the M code
+ *   bytes of a row are written).  first_bad [dev] int32 [1].
+ * nlsh_pq_decode_rows: codes [n, M] -> out [dev] float32 [n, d], out_stride >= d floats between rows (columns below d are written).
+ * nlsh_pq_inv_norm: inv_norm [dev] float [n] of n code rows.
+ * nlsh_scan_topk_cells_phase_pq: nlsh_scan_topk_cells_phase_sq8 over a pq index, with the codebook, dsub and the code pitch (bytes,
+ *   a multiple of 16) where that call has lo and step; row_stride is the decoded row's width M * dsub; row_filter NULL = no filter.
+ *   Tiled schedule only (NLSH_E_UNSUPPORTED otherwise), every metric, k <= NLSH_MAX_K_TILED.  Refused: dsub outside {4, 8, 16}, a null
+ *   or misaligned codebook (NLSH_E_INVALID).  The code bytes are decoded as they are staged.  The radius, tagged, step, graph-slot and
+ *   one-call batch entry points take no pq index. */
+int nlsh_pq_encode(const void *rows, int storage, int64_t row_stride, int d, int64_t n, const float *codebook, int dsub,
+                   uint8_t *codes, int64_t code_pitch, int32_t *first_bad, nlsh_stream_t stream);
+int nlsh_pq_decode_rows(const uint8_t *codes, int64_t code_pitch, int64_t n, const float *codebook, int dsub, int d, float *out,
+                        int64_t out_stride, nlsh_stream_t stream);
+int nlsh_pq_inv_norm(const uint8_t *codes, int64_t code_pitch, int64_t n, const float *codebook, int dsub, int d, float *inv_norm,
+                     nlsh_stream_t stream);
+int nlsh_scan_topk_cells_phase_pq(const uint8_t *corpus_sorted, const float *codebook, int dsub, int64_t code_pitch, int64_t row_stride, int d,
+                                  const int32_t *gid, const int32_t *uniq_keys, const int32_t *offsets, const int32_t *bucket_order,
+                                  int32_t n_buckets, const int32_t *cell_of, const int32_t *cell_offsets, int32_t n_cells,
+                                  const float *inv_norm, const float *queries, int64_t q_stride, int64_t Q,
+                                  const int32_t *qkeys, const int32_t *nkeys, int P, int k, int metric, int algo, int seg_rows,
+                                  float *out_dist, int32_t *out_idx, uint64_t *out_keys, int32_t *out_ncand,
+                                  int32_t *status, void *workspace, size_t workspace_bytes, int64_t max_tasks,
+                                  void *ev_scan_begin, void *ev_scan_end, nlsh_stream_t stream, int phases,
+                                  const uint32_t *row_filter);
+
+/* ---------------------------------------------------------------------------------------------
  * One pipelined query batch per call.  Replaces, for a caller that streams batches, the whole body of Indexer.query
  * (nlsh/indexer.py:56-96: hashing.hash on the batch :59 via Indexer.hash :40-54, then the per-query loop :62-95) by ONE
  * enqueue: nlsh_encode_hash + the PLAN, SCAN and MERGE phases of nlsh_scan_topk_cells_phase (five launches since r06: the bucket

@@ -100,17 +100,21 @@ static const void *bscan2_of(int d4) {
 struct ScanLaunch {
     const void *fn;
     dim3 grid, block;
-    void *argv[2];   // the kernel's BArgs and, read by the filtered, affine and tagged kernels alone, `side` as their second parameter
+    void *argv[3];   // the kernel's BArgs and, read by the filtered, affine, tagged and PQ kernels alone, `side` as their second parameter;
+                     // `pqa` is the PQ kernels' third
     SideArgs side;   // the call's filter, quantiser, tags, masks and mode: what it does not carry is null
+    PqArgs pqa;      // the call's codebook, code pitch and chunks per sub-vector (a pq call's alone)
 };
 static int scan_launch_of(const BucketScanCall &c, int metric, const BArgs *a, ScanLaunch *l) {
     l->side = SideArgs{c.row_tags, c.query_masks, c.tag_match, c.row_filter, c.affine ? (const float4 *)c.quant_lo : nullptr,
                        c.affine ? (const float4 *)c.quant_step : nullptr};
     l->argv[0] = (void *)a;
     l->argv[1] = (void *)&l->side;
+    l->pqa = PqArgs{(const float4 *)c.pq_codebook, c.pq_pitch, c.pq_dsub / 4};
+    l->argv[2] = (void *)&l->pqa;
     const bool wide = c.k > NLSH_MAX_K;   // wide k: the same task body, its epilogue selecting up to 64 * TPS keys per list
     if (!c.tiled()) {
-        NLSH_REQUIRE(!c.row_filter && c.storage == NLSH_STORE_F32 && !c.affine && !c.row_tags, NLSH_E_UNSUPPORTED,
+        NLSH_REQUIRE(!c.row_filter && c.storage == NLSH_STORE_F32 && !c.affine && !c.row_tags && !c.pq, NLSH_E_UNSUPPORTED,
                      "scan_topk(bucket-major): row_filter, row_tags and a float16 / uint8 corpus are read by the tiled schedule only");
         l->grid = dim3((unsigned)((c.max_tasks + 3) / 4));  // one wavefront per task
         l->block = dim3(256);
@@ -120,7 +124,8 @@ static int scan_launch_of(const BucketScanCall &c, int metric, const BArgs *a, S
     }
     // (the float32 tiled kernels are named before the wave-level ones: a code object keeps its kernels in the order the host code first
     // names them, and scan_bucket.hip's is compared byte for byte across changes of this file)
-    if (c.tiled() && c.row_tags) l->fn = tagged_scan_kernel_of(c.affine ? NLSH_STORE_SQ8 : c.storage, metric, wide);   // scan_bucket_tagged.hip
+    if (c.tiled() && c.pq) l->fn = pq_scan_kernel_of(metric, wide);                                                    // scan_bucket_pq.hip
+    else if (c.tiled() && c.row_tags) l->fn = tagged_scan_kernel_of(c.affine ? NLSH_STORE_SQ8 : c.storage, metric, wide);   // scan_bucket_tagged.hip
     else if (c.tiled() && c.affine) l->fn = affine_scan_kernel_of(metric, wide);                                      // scan_bucket_affine.hip
     else if (c.tiled() && c.row_filter) l->fn = filtered_scan_kernel_of(c.storage, metric, wide);                    // scan_bucket_filtered.hip
     else if (c.tiled() && c.storage != NLSH_STORE_F32) l->fn = typed_scan_kernel_of(c.storage, metric, wide);   // scan_bucket_typed.hip
@@ -181,6 +186,7 @@ int bucket_scan_node(const BucketScanCall &c, ScanNode *out) {
     NLSH_REQUIRE(c.row_filter == nullptr, NLSH_E_UNSUPPORTED, "scan node: a call with a row_filter cannot be replayed from a graph node");
     NLSH_REQUIRE(!c.affine, NLSH_E_UNSUPPORTED, "scan node: a call over an sq8 corpus cannot be replayed from a graph node");
     NLSH_REQUIRE(c.row_tags == nullptr, NLSH_E_UNSUPPORTED, "scan node: a call with row_tags cannot be replayed from a graph node");
+    NLSH_REQUIRE(!c.pq, NLSH_E_UNSUPPORTED, "scan node: a call over a pq corpus cannot be replayed from a graph node");
     BucketScanPrep p;
     int rc = bucket_scan_args(c, &p);
     if (rc != NLSH_OK) return rc;

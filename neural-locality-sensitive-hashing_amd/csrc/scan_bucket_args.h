@@ -103,6 +103,17 @@ struct SideArgs {
     const float4 *step4;           // NLSH_STORE_SQ8: [row_stride / 4] its steps, padded with 1: a padded column (code 0) decodes to +0
 };
 
+// The corpus storage of the PQ kernels (bscanq_kernel, scan_bucket_pq.hip; nlsh_scan_topk_cells_phase_pq): M code bytes per row, a staged
+// 16-byte slot gathered from the codebook as the tile is written (l2_task*, scan_bucket_tiled.h).  Internal, like NLSH_STORE_SQ8: a pq
+// call is a uint8 call that carries a codebook (BucketScanCall::pq).
+#define NLSH_STORE_PQ 4
+// THIRD parameter of the PQ kernels, theirs alone: SideArgs and BArgs keep their layout and field order (see SideArgs above).
+struct PqArgs {
+    const float4 *cb4;             // the codebook [M, 256, dsub] float32 as float4s: entry (m, code) is cps consecutive ones
+    long long pitch;               // bytes between the code rows (a multiple of 16, >= M)
+    int cps;                       // 16-byte chunks per sub-vector: dsub / 4 = 1 | 2 | 4
+};
+
 // A call's prepared launch (scan_bucket.hip): the workspace held against the schedule's layout (NLSH_E_WORKSPACE), then what the scan kernels
 // take (bucket_scan_run; the radius calls for their own kernel), what the lookup takes (step.hip, probe_ranked.hip: the launch that does it),
 // the metric the schedule really computes and whether the tiled schedule needs its padded / pre-normalised query copy

@@ -3,7 +3,8 @@
 // the hand-scheduled k-blocks, the task bodies built from them (l2_task*), one task start to finish (tiled_task_body) and the kernels
 // bscan3_kernel (k <= 64) and bscanw_kernel (k up to NLSH_MAX_K_TILED) over a float32 corpus, bscant_kernel over a float16 / uint8 one,
 // bscanf_kernel behind a row filter (scan_bucket_filtered.hip instantiates it), bscanr_kernel for radius queries (scan_bucket_range.hip),
-// bscana_kernel over an sq8 corpus (scan_bucket_affine.hip), bscang_kernel behind per-query tag filters (scan_bucket_tagged.hip).
+// bscana_kernel over an sq8 corpus (scan_bucket_affine.hip), bscang_kernel behind per-query tag filters (scan_bucket_tagged.hip),
+// bscanq_kernel over a product-quantised corpus (scan_bucket_pq.hip).
 #pragma once
 
 // Diagnostic build only (make EXTRA=-DNLSH_SCAN_TRACE, tools/scan_trace.py): wave 0 of every bscan3 workgroup
@@ -316,6 +317,14 @@ template <> struct Stored<NLSH_STORE_SQ8> {
     }
     static __device__ __forceinline__ uint32_t zero() { return 0u; }
 };
+// The product-quantised form (storage="pq"; bscanq_kernel): a row is M code bytes, and what is staged is the DECODED chunk -- the float4 of
+// the codebook entry its code byte names, a copy without arithmetic.  The staging registers hold float4s like the
+// float32 form's, `widen` is the identity, and the staging code of l2_task / l2_task_single does the two dependent loads.
+template <> struct Stored<NLSH_STORE_PQ> {
+    typedef float4 word;
+    static __device__ __forceinline__ float4 widen(float4 w) { return w; }
+    static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+};
 
 // All k-blocks of one L2 task for a wave that holds NQ (0..4) of its queries, NTL = tiles of the task (1..4): staging
 // (global -> registers -> LDS, next k-block's loads in flight during the current one) + the hand-scheduled k-blocks.
@@ -330,7 +339,8 @@ template <int NW, int NQ, int NTL, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK =
 __device__ __forceinline__ void l2_task(float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
                                         const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4],
                                         [[maybe_unused]] unsigned long long (&tr)[3],
-                                        [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr) {
+                                        [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr,
+                                        [[maybe_unused]] const PqArgs *pq = nullptr) {
     constexpr int NTH = 64 * NW, KB = NLSH_TILED_KB;
     // A task costs ~15 us before it does any work (r01 trace: 16 us for 1 query x <= 64 rows, 55 us for 16 x 256): one
     // exposed global-load round trip + two barriers per k-block.  Short segments therefore take FATTER k-blocks --
@@ -352,12 +362,40 @@ __device__ __forceinline__ void l2_task(float4 *tile, const typename Stored<STOR
     const typename Stored<STORE>::word *rowp[SPT];
 #pragma unroll
     for (int i = 0; i < SPT; ++i) rowp[i] = corpus4 + (long long)(row0 + min(sr + RPPt * i, nrows - 1)) * stride4;
+    // (NLSH_STORE_PQ: a staged slot is two DEPENDENT loads -- the code byte of (row, gc / cps), then the float4 that byte names in the
+    // codebook.  The code bytes run ONE STAGE AHEAD of the gathers: stage_load(kb) gathers with the bytes it holds and requests those of
+    // stage kb + 1 behind them, so a gather's address is a whole k-block old when it is needed and only the task's first byte load is
+    // an exposed round trip.  Four registers per thread; a thread's bytes of the whole task would be M per row, up to 256.  A clamped
+    // slot (row nrows - 1, chunk d4 - 1) names a real code byte, and any byte a real entry: (d4 - 1) / cps < M.)
+    [[maybe_unused]] const uint8_t *crow[SPT];
+    [[maybe_unused]] uint32_t pcode[SPT];
+    [[maybe_unused]] const float4 *pcb = nullptr;
+    [[maybe_unused]] int psh = 0, pmask = 0;
+    if constexpr (STORE == NLSH_STORE_PQ) {
+        pcb = pq->cb4; psh = pq->cps >> 1; pmask = pq->cps - 1;   // cps 1 / 2 / 4 -> shift 0 / 1 / 2
+#pragma unroll
+        for (int i = 0; i < SPT; ++i)
+            crow[i] = reinterpret_cast<const uint8_t *>(corpus4) + (long long)(row0 + min(sr + RPPt * i, nrows - 1)) * pq->pitch;
+    }
+    [[maybe_unused]] auto code_load = [&](int kb) {
+        const int m = min(kb * KBt + sc, d4 - 1) >> psh;
+#pragma unroll
+        for (int i = 0; i < SPT; ++i) pcode[i] = crow[i][m];
+    };
     auto stage_load = [&](int kb) {
         const int gc = min(kb * KBt + sc, d4 - 1);
+        if constexpr (STORE == NLSH_STORE_PQ) {
+            const float4 *e = pcb + (((gc >> psh) * 256) << psh) + (gc & pmask);
 #pragma unroll
-        for (int i = 0; i < SPT; ++i) stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? rowp[i][gc] : Stored<STORE>::zero();
-        if constexpr (STORE == NLSH_STORE_SQ8) { lo_c = qlo[gc]; step_c = qstep[gc]; }
+            for (int i = 0; i < SPT; ++i) stg[i] = e[pcode[i] << psh];
+            if (kb + 1 < nkb) code_load(kb + 1);
+        } else {
+#pragma unroll
+            for (int i = 0; i < SPT; ++i) stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? rowp[i][gc] : Stored<STORE>::zero();
+            if constexpr (STORE == NLSH_STORE_SQ8) { lo_c = qlo[gc]; step_c = qstep[gc]; }
+        }
     };
+    if constexpr (STORE == NLSH_STORE_PQ) code_load(0);
     stage_load(0);
     float qsink = 0.0f;
     asm volatile("" : "+s"(qsink));
@@ -409,7 +447,8 @@ constexpr int SINGLE_STAGE_SLOTS = 1024;   // float4 slots one pass of the 256 t
 template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS, int STORE = NLSH_STORE_F32>
 __device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
                                                const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4],
-                                               [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr) {
+                                               [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr,
+                                               [[maybe_unused]] const PqArgs *pq = nullptr) {
     constexpr int NTH = 64 * NW, SPT = SINGLE_STAGE_SLOTS / NTH;
     const int RS = d4 | 1;                   // odd LDS row stride (16-byte slots): conflict-free column reads
     const int total = nrows * d4;
@@ -426,6 +465,11 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stor
         r -= (r * d4 > idx) ? 1 : 0;
         r += ((r + 1) * d4 <= idx) ? 1 : 0;
         const int c = idx - r * d4;
+        if constexpr (STORE == NLSH_STORE_PQ) {   // the slot's code byte, then the float4 it names: both loads exposed, once per task
+            const int psh = pq->cps >> 1, m = c >> psh;
+            const uint32_t code = reinterpret_cast<const uint8_t *>(corpus4)[(long long)(row0 + r) * pq->pitch + m];
+            stg[i] = pq->cb4[((m * 256 + (int)code) << psh) + (c & (pq->cps - 1))];
+        } else
         stg[i] = (NLSH_ABLATE != 2 && NLSH_ABLATE != 12 && NLSH_ABLATE != 13) ? corpus4[(long long)(row0 + r) * stride4 + c] : Stored<STORE>::zero();
         dst[i] = r * RS + c;
         if constexpr (STORE == NLSH_STORE_SQ8) col[i] = c;
@@ -456,14 +500,15 @@ __device__ __forceinline__ void l2_task_single(float4 *tile, const typename Stor
 template <int NW, int NQ, int METRIC = NLSH_METRIC_L2_EPS, bool WIDEK = false, int STORE = NLSH_STORE_F32>
 __device__ __forceinline__ void l2_task_nt(int ntile, float4 *tile, const typename Stored<STORE>::word *corpus4, long long stride4, int d4, int row0, int nrows,
                                            const const_f32p (&qs)[4], int tid, int lane, float (&acc)[4][4], unsigned long long (&tr)[3],
-                                           [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr) {
-    if constexpr (STORE == NLSH_STORE_SQ8) {   // the same switch, the quantiser handed on
+                                           [[maybe_unused]] const float4 *qlo = nullptr, [[maybe_unused]] const float4 *qstep = nullptr,
+                                           [[maybe_unused]] const PqArgs *pq = nullptr) {
+    if constexpr (STORE == NLSH_STORE_SQ8 || STORE == NLSH_STORE_PQ) {   // the same switch, the quantiser / the codebook handed on
         switch (ntile) {
-            case 0: l2_task_single<NW, NQ, METRIC, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, qlo, qstep); break;
-            case 1: l2_task<NW, NQ, 1, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep); break;
-            case 2: l2_task<NW, NQ, 2, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep); break;
-            case 3: l2_task<NW, NQ, 3, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep); break;
-            default: l2_task<NW, NQ, 4, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep); break;
+            case 0: l2_task_single<NW, NQ, METRIC, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, qlo, qstep, pq); break;
+            case 1: l2_task<NW, NQ, 1, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep, pq); break;
+            case 2: l2_task<NW, NQ, 2, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep, pq); break;
+            case 3: l2_task<NW, NQ, 3, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep, pq); break;
+            default: l2_task<NW, NQ, 4, METRIC, WIDEK, STORE>(tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, tr, qlo, qstep, pq); break;
         }
         return;
     }
@@ -510,7 +555,8 @@ template <int METRIC, int QW, int NW, int TPS, bool WIDEK = false, int STORE = N
 __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, long long t, const int4 desc, const int2 qr_all, int tid, int lane,
                                                 int wave, [[maybe_unused]] unsigned long long ts_entry,
                                                 [[maybe_unused]] const SideArgs *side = nullptr,
-                                                [[maybe_unused]] const RangeArgs *range = nullptr) {
+                                                [[maybe_unused]] const RangeArgs *range = nullptr,
+                                                [[maybe_unused]] const PqArgs *pq = nullptr) {
     static_assert(!(RANGE && (FILT || WIDEK)), "the range epilogue takes its filter as a nullable run-time operand and selects nothing");
     static_assert(!(TAGS && (FILT || RANGE)), "the tagged kernels take their filter as a nullable run-time operand and have no range epilogue");
     // AFFINE (STORE == NLSH_STORE_SQ8; nlsh_scan_topk_cells_phase_sq8, bscana_kernel): the staging code decodes with side->lo4 / step4,
@@ -518,7 +564,11 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
     constexpr bool AFFINE = STORE == NLSH_STORE_SQ8;
     static_assert(!(AFFINE && (FILT || RANGE)), "the affine kernels take their filter as a nullable run-time operand and have no range epilogue");
     // SIDE: the forms that read `side` at all; in the others neither the parameter nor the filter words exist in the code
-    constexpr bool SIDE = FILT || RANGE || AFFINE || TAGS;
+    // PQ (STORE == NLSH_STORE_PQ; nlsh_scan_topk_cells_phase_pq, bscanq_kernel): the staging code gathers from pq->cb4 by the rows' code
+    // bytes, and the filter is a nullable run-time operand as in the affine kernels.  Off, none of it exists in the code.
+    constexpr bool PQ = STORE == NLSH_STORE_PQ;
+    static_assert(!(PQ && (FILT || RANGE || TAGS)), "the PQ kernels take their filter as a nullable run-time operand and have neither tags nor a range epilogue");
+    constexpr bool SIDE = FILT || RANGE || AFFINE || TAGS || PQ;
     static_assert(QW == 4 && TPS == 4 && NW == 4, "the hand-scheduled task bodies (l2_task_nt) are written for 4 waves x 4 queries x 4 row tiles");
 #ifdef NLSH_SCAN_TRACE_CLOCK
     const unsigned long long ts0 = SCAN_NOW();
@@ -608,11 +658,11 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
     const int nt_sel = (nrows * d4 <= SINGLE_STAGE_SLOTS && nrows <= 64) ? 0 : ntile;   // wave-uniform (task shape)
     // the hand-scheduled form, specialised per (queries of this wave, tiles of the task); same barrier count on every path
     switch (nqw) {
-        case 0: l2_task_nt<NW, 0, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
-        case 1: l2_task_nt<NW, 1, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
-        case 2: l2_task_nt<NW, 2, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
-        case 3: l2_task_nt<NW, 3, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
-        default: l2_task_nt<NW, 4, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep); break;
+        case 0: l2_task_nt<NW, 0, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep, pq); break;
+        case 1: l2_task_nt<NW, 1, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep, pq); break;
+        case 2: l2_task_nt<NW, 2, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep, pq); break;
+        case 3: l2_task_nt<NW, 3, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep, pq); break;
+        default: l2_task_nt<NW, 4, METRIC, WIDEK, STORE>(nt_sel, tile, corpus4, stride4, d4, row0, nrows, qs, tid, lane, acc, trl, qlo, qstep, pq); break;
     }
     if (nqw == 0) return;
     if (NLSH_ABLATE == 5 || NLSH_ABLATE == 6 || NLSH_ABLATE == 12 || NLSH_ABLATE == 13) {   // diagnostic: no epilogue at all (the accumulators are kept alive)
@@ -786,7 +836,7 @@ __device__ __forceinline__ void tiled_task_body(const BArgs &a, float4 *tile, lo
     const int2 qr_all = (a).task_qr[tc * (QW * NW) + (lane & (QW * NW - 1))];                \
     if (t >= ntasks) return
 
-// The seven kernels below are shells: the LDS stage, the pick, one call of tiled_task_body.  The stage is declared in each __global__:
+// The eight kernels below are shells: the LDS stage, the pick, one call of tiled_task_body.  The stage is declared in each __global__:
 // handed to a shared function, or declared in one, its address stops being a compile-time constant of the staging code and the float32
 // kernels' instructions change.  Each is a kernel of its own name with task bodies of its own instantiation, in a translation unit of
 // its own where it says so, so that the kernels in front of it keep their code and their register / occupancy budget; BArgs keeps its
@@ -870,6 +920,20 @@ __global__ __launch_bounds__(64 * NW, 1) void bscana_kernel(BArgs a, SideArgs s)
     [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
     NLSH_TILED_PICK(a);
     tiled_task_body<METRIC, QW, NW, TPS, WIDEK, NLSH_STORE_SQ8>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, &s);
+}
+
+// A product-quantised corpus (STORE == NLSH_STORE_PQ; nlsh_scan_topk_cells_phase_pq): M code bytes per row, the staged chunk gathered from
+// the codebook as the tile is written, both k classes.  One kernel per (metric, k class) serves both filter states -- s.row_filter is a
+// wave-uniform run-time operand.  The codebook, the code pitch and cps are a THIRD parameter of these kernels alone (PqArgs).
+// Instantiated in scan_bucket_pq.hip (profiles/pq_storage.txt).
+template <int METRIC, int QW, int NW, int TPS, bool WIDEK>
+__global__ __launch_bounds__(64 * NW, 1) void bscanq_kernel(BArgs a, SideArgs s, PqArgs p) {
+    constexpr int RS = NLSH_TILED_KB + 1;
+    __shared__ float4 tile[64 * TPS * RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    [[maybe_unused]] const unsigned long long ts_entry = SCAN_NOW();
+    NLSH_TILED_PICK(a);
+    tiled_task_body<METRIC, QW, NW, TPS, WIDEK, NLSH_STORE_PQ>(a, tile, t, desc, qr_all, tid, lane, wave, ts_entry, &s, nullptr, &p);
 }
 
 // Behind per-query tag filters (TAGS of tiled_task_body; nlsh_scan_topk_cells_phase_tagged / _sq8_tagged), every storage -- NLSH_STORE_SQ8

@@ -446,6 +446,12 @@ struct BucketScanCall {
                                   // the tags, the masks, the mode, the filter and -- affine -- the quantiser
     const uint64_t *query_masks;  // [Q] mask of every query; given iff row_tags is
     int tag_match;                // NLSH_TAG_ANY | NLSH_TAG_ALL | NLSH_TAG_EQ; looked at only with row_tags
+    bool pq;                      // nlsh_scan_topk_cells_phase_pq: `corpus` holds product-quantiser codes, M = ceil(d / pq_dsub) bytes per row
+                                  // (storage = NLSH_STORE_U8, row_stride = M * pq_dsub: the decoded row's width), and the SCAN phase launches a
+                                  // PQ kernel, which reads the three fields below from a third parameter of its own (PqArgs)
+    const float *pq_codebook;     // pq: [M, 256, pq_dsub] float32 (device, 16-byte aligned), columns at or beyond d held as +0
+    int pq_dsub;                  // pq: 4 | 8 | 16
+    long long pq_pitch;           // pq: bytes between the code rows, a multiple of 16 and >= M
     bool tiled() const { return algo == NLSH_SCAN_BUCKET_TILED; }
 };
 // internal phase bit (not part of the C ABI's phase mask): the PLAN phase WITHOUT the bucket lookup, which the batch's encode_hash
@@ -483,5 +489,7 @@ const void *affine_scan_kernel_of(int metric, bool wide);
 // the tiled scan kernel behind per-query tag filters (scan_bucket_tagged.hip): any storage, NLSH_STORE_SQ8 (scan_bucket_args.h) for an
 // affine call; tags, masks, mode, the filter and the quantiser inside the second parameter
 const void *tagged_scan_kernel_of(int storage, int metric, bool wide);
+// the tiled scan kernel over a product-quantised corpus (scan_bucket_pq.hip): its parameters are (BArgs, SideArgs, PqArgs)
+const void *pq_scan_kernel_of(int metric, bool wide);
 
 }  // namespace nlsh

@@ -361,6 +361,15 @@ int query_major_run(const BucketScanCall &c) {
 
 // the pitch of the corpus rows: a multiple of 16 bytes -- 4 float32 / 8 float16 / 16 uint8 elements -- from a 16-byte aligned base
 static int corpus_pitch_check(const char *who, const BucketScanCall &c) {
+    if (c.pq) {   // code rows: M bytes at a pitch of 16-byte units; row_stride is the decoded row's width and must say the same M
+        const long long M = c.pq_dsub > 0 ? (c.d + c.pq_dsub - 1) / c.pq_dsub : 0;
+        NLSH_REQUIRE(c.pq_pitch >= M && c.pq_pitch % 16 == 0, NLSH_E_INVALID, "%s: code_pitch=%lld must be >= M=%lld and a multiple of 16 bytes", who,
+                     c.pq_pitch, M);
+        NLSH_REQUIRE(c.row_stride == M * c.pq_dsub, NLSH_E_INVALID, "%s: row_stride=%lld is not M * dsub = %lld (the decoded row's width)", who,
+                     c.row_stride, M * c.pq_dsub);
+        NLSH_REQUIRE(((uintptr_t)c.corpus & 15) == 0, NLSH_E_INVALID, "%s: corpus_sorted must be 16-byte aligned", who);
+        return NLSH_OK;
+    }
     const int per16 = c.storage == NLSH_STORE_F32 ? 4 : (c.storage == NLSH_STORE_F16 ? 8 : 16);
     NLSH_REQUIRE(c.row_stride >= c.d && c.row_stride % per16 == 0, NLSH_E_INVALID, "%s: row_stride=%lld must be >= d=%d and a multiple of %d elements "
                  "(a pitch of 16-byte units) for storage=%d", who, c.row_stride, c.d, per16, c.storage);
@@ -386,6 +395,14 @@ int scan_call_check(const char *who, const BucketScanCall &c, unsigned needs) {
     NLSH_REQUIRE(c.storage == NLSH_STORE_F32 || c.tiled(), NLSH_E_UNSUPPORTED, "%s: a %s corpus (storage=%d) is read by %s, not by algo=%d", who,
                  c.storage == NLSH_STORE_F16 ? "float16" : "uint8", c.storage, tiled_only, c.algo);
     NLSH_REQUIRE(!c.affine || c.storage == NLSH_STORE_U8, NLSH_E_INVALID, "%s: an sq8 corpus is held in the uint8 layout, not storage=%d", who, c.storage);
+    // a product-quantised corpus: the tiled schedule's direct top-k calls alone, one of three sub-vector widths, no tags
+    NLSH_REQUIRE(!c.pq || c.tiled(), NLSH_E_UNSUPPORTED, "%s: a pq corpus is read by %s, not by algo=%d", who, tiled_only, c.algo);
+    NLSH_REQUIRE(!c.pq || (topk && !(needs & SCAN_ALLOWS_PLAN_REST) && !(c.phases & NLSH_PHASE_PLAN_REST)), NLSH_E_UNSUPPORTED,
+                 "%s: a pq corpus is read by the direct top-k calls only, not by a radius call, a step or a graph slot", who);
+    NLSH_REQUIRE(!c.pq || !(c.row_tags || c.query_masks), NLSH_E_UNSUPPORTED, "%s: a pq corpus takes no row_tags", who);
+    NLSH_REQUIRE(!c.pq || (c.storage == NLSH_STORE_U8 && !c.affine), NLSH_E_INVALID, "%s: a pq corpus is code bytes, not storage=%d", who, c.storage);
+    NLSH_REQUIRE(!c.pq || c.pq_dsub == 4 || c.pq_dsub == 8 || c.pq_dsub == 16, NLSH_E_INVALID, "%s: dsub=%d is none of 4, 8, 16", who, c.pq_dsub);
+    NLSH_REQUIRE(!c.pq || (c.pq_codebook && ((uintptr_t)c.pq_codebook & 15) == 0), NLSH_E_INVALID, "%s: the codebook is null or not 16-byte aligned", who);
     NLSH_REQUIRE(((uintptr_t)c.row_filter & 3) == 0, NLSH_E_INVALID, "%s: row_filter must be 4-byte aligned", who);
     // per-query tag filters (the schedule is held above): both arrays or neither, read with 8-byte loads, by the top-k kernels of a direct call alone
     NLSH_REQUIRE(c.row_tags || !c.query_masks, NLSH_E_INVALID, "%s: query_masks without row_tags", who);
@@ -525,6 +542,17 @@ extern "C" int nlsh_scan_topk_cells_phase_filtered(const void *corpus_sorted, in
 extern "C" int nlsh_scan_topk_cells_phase_sq8(const uint8_t *corpus_sorted, const float *lo, const float *step, NLSH_CELLS_PARAMS,
                                               const uint32_t *row_filter) {
     return sq8_topk_call("scan_topk_sq8", corpus_sorted, lo, step, NLSH_CELLS_ARGS, row_filter, nullptr, nullptr, 0);
+}
+
+// The filtered call over a product-quantised corpus: code rows, the codebook, dsub and the code pitch where the sq8 call has lo / step.
+// row_stride is the decoded row's width, M * dsub.
+extern "C" int nlsh_scan_topk_cells_phase_pq(const uint8_t *corpus_sorted, const float *codebook, int dsub, int64_t code_pitch, NLSH_CELLS_PARAMS,
+                                             const uint32_t *row_filter) {
+    NLSH_TOPK_CALL(c);
+    c.cell_of = cell_of; c.cell_offsets = cell_offsets; c.n_cells = n_cells;
+    c.phases = phases; c.storage = NLSH_STORE_U8; c.row_filter = row_filter;
+    c.pq = true; c.pq_codebook = codebook; c.pq_dsub = dsub; c.pq_pitch = code_pitch;
+    return topk_call("scan_topk_pq", c);
 }
 
 // The filtered call behind per-query tag filters: without row_tags it IS the filtered call, and says so in its refusals.

@@ -55,6 +55,7 @@ SYMBOLS = (
     "nlsh_sq8_train_workspace", "nlsh_sq8_train", "nlsh_gather_rows_sq8", "nlsh_csr_update_sq8", "nlsh_scan_topk_cells_phase_sq8",
     "nlsh_rerank_topk",
     "nlsh_scan_topk_cells_phase_tagged", "nlsh_scan_topk_cells_phase_sq8_tagged",
+    "nlsh_pq_encode", "nlsh_pq_decode_rows", "nlsh_pq_inv_norm", "nlsh_scan_topk_cells_phase_pq",
 )
 
 
@@ -191,6 +192,16 @@ def lib():
         tagged = getattr(L, base.replace("_filtered", "") + "_tagged")
         tagged.restype = i32
         tagged.argtypes = list(getattr(L, base).argtypes) + [vp, vp, i32]
+    # storage="pq": code rows plus a codebook; the sorted copy moves through the typed uint8 calls, the scan has an entry of its own
+    L.nlsh_pq_encode.restype = i32             # rows, storage, row_stride, d, n | codebook, dsub | codes, code_pitch | first_bad, stream
+    L.nlsh_pq_encode.argtypes = [vp, i32, i64, i32, i64, vp, i32, vp, i64, vp, vp]
+    L.nlsh_pq_decode_rows.restype = i32        # codes, code_pitch, n | codebook, dsub, d | out, out_stride, stream
+    L.nlsh_pq_decode_rows.argtypes = [vp, i64, i64, vp, i32, i32, vp, i64, vp]
+    L.nlsh_pq_inv_norm.restype = i32           # codes, code_pitch, n | codebook, dsub, d | inv_norm, stream
+    L.nlsh_pq_inv_norm.argtypes = [vp, i64, i64, vp, i32, i32, vp, vp]
+    L.nlsh_scan_topk_cells_phase_pq.restype = i32      # the filtered call with (codebook, dsub, code_pitch) in place of the storage code
+    L.nlsh_scan_topk_cells_phase_pq.argtypes = (L.nlsh_scan_topk_cells_phase_filtered.argtypes[:1] + [vp, i32, i64]
+                                                + L.nlsh_scan_topk_cells_phase_filtered.argtypes[2:])
     L.nlsh_row_filter_words.restype = sz
     L.nlsh_row_filter_words.argtypes = [i64]
     L.nlsh_row_filter_build.restype = i32      # gid, n_rows | ids, n_ids | dense, n_dense, id_base | invert | row_filter, n_allowed, stream

@@ -183,8 +183,32 @@ def build_index(indexes, cuda=True) -> Dict[int, torch.Tensor]:
 #   "sq8" holds uint8 CODES in the uint8 layout and decodes them with the index's per-dimension quantiser: its calls
 #   are the *_sq8 entry points, the typed ones never see it
 _STORAGES = {"float32": (torch.float32, _capi.STORE_F32, 4), "float16": (torch.float16, _capi.STORE_F16, 8), "uint8": (torch.uint8, _capi.STORE_U8, 16),
-             "sq8": (torch.uint8, _capi.STORE_U8, 16)}
+             "sq8": (torch.uint8, _capi.STORE_U8, 16), "pq": (torch.uint8, _capi.STORE_U8, 16)}
+#   "pq" holds product-quantiser CODES, M = ceil(d / dsub) bytes per row, decoded through the index's codebook: the
+#   sorted copy moves through the typed uint8 calls at width M, the scan has the *_pq entry point
+PQ_DSUBS = (4, 8, 16)
 _STORE_CODE_OF_DTYPE = {dt: code for dt, code, _ in _STORAGES.values()}
+
+
+def checked_codebook(codebook, d, dsub):
+    """`quantiser=` of a pq index, checked on the host before anything touches a device -> the codebook, float32 [M, 256, dsub]
+    contiguous (on whatever device it came from), the columns of the last sub-vector at or beyond d zeroed (a copy if any had to be)."""
+    M = (d + dsub - 1) // dsub
+    if isinstance(codebook, (tuple, list)):
+        raise ValueError(f"quantiser of storage='pq' must be a codebook, a float32 [{M}, 256, {dsub}] array, not a {type(codebook).__name__}")
+    t = codebook if isinstance(codebook, torch.Tensor) else torch.as_tensor(np.asarray(codebook))
+    if t.dtype != torch.float32:
+        raise ValueError(f"codebook must be float32, got {t.dtype}")
+    if tuple(t.shape) != (M, 256, dsub):
+        raise ValueError(f"codebook must have shape ({M}, 256, {dsub}) for d={d}, pq_dsub={dsub}, got {tuple(t.shape)}")
+    if t.device.type == "cpu" and not bool(torch.isfinite(t).all()):       # (a device codebook is held against this where the index is built)
+        raise ValueError("codebook must be finite")
+    tail = M * dsub - d
+    t = t.contiguous()
+    if tail and bool((t[M - 1, :, dsub - tail:] != 0).any() if t.device.type == "cpu" else True):
+        t = t.clone()
+        t[M - 1, :, dsub - tail:] = 0.0
+    return t
 
 
 def checked_quantiser(quantiser, d):
@@ -263,6 +287,37 @@ def pack_row_filter(allowed) -> np.ndarray:
     return np.packbits(bits.reshape(n_words, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
 
 
+def pq_encode(rows, codebook, d, what="rows", row_base=0):
+    """Float rows [n, d] (device; float32 or float16, anything else is converted with `.float()`) -> their product-quantiser codes, uint8
+    [n, M], by `nlsh_pq_encode` -- the one statement of the encoding rule on the device (include/nlsh_hip.h).  `codebook`: float32
+    [M, 256, dsub] on the rows' device.  A row holding a NaN or an infinity raises ValueError naming `what` row `row_base` + its number."""
+    if rows.dtype not in (torch.float32, torch.float16):
+        rows = rows.float()
+    if rows.dim() != 2 or rows.stride(1) != 1:
+        rows = rows.contiguous()
+    n, dev, M, dsub = int(rows.shape[0]), rows.device, int(codebook.shape[0]), int(codebook.shape[2])
+    codes = torch.empty((n, M), dtype=torch.uint8, device=dev)
+    first_bad = torch.empty((1,), dtype=torch.int32, device=dev)
+    _capi.check(_capi.lib().nlsh_pq_encode(_capi.ptr(rows), _STORE_CODE_OF_DTYPE[rows.dtype], rows.stride(0) if n else d, d, n, _capi.ptr(codebook),
+                                           dsub, _capi.ptr(codes), M, _capi.ptr(first_bad), _stream(dev)))
+    bad = int(first_bad.item())
+    if bad >= 0:
+        Indexer._raise_unrepresentable(row_base + bad, "pq", what)
+    return codes
+
+
+def pq_decode(codes, codebook, d):
+    """Codes uint8 [n, >= M] (device, unit column stride, any pitch) -> the decoded rows, float32 [n, d], by `nlsh_pq_decode_rows`: element j
+    of a row is codebook[j // dsub][code[j // dsub]][j % dsub], a copy."""
+    if codes.stride(1) != 1:
+        codes = codes.contiguous()
+    n, dev, dsub = int(codes.shape[0]), codes.device, int(codebook.shape[2])
+    out = torch.empty((n, d), dtype=torch.float32, device=dev)
+    _capi.check(_capi.lib().nlsh_pq_decode_rows(_capi.ptr(codes), codes.stride(0) if n else int(codebook.shape[0]), n, _capi.ptr(codebook), dsub, d,
+                                                _capi.ptr(out), d, _stream(dev)))
+    return out
+
+
 class Indexer:
 
     # "float32" | "float16" | "uint8": what `corpus_sorted` holds (DESIGN.md 4.9).  A compressed index (the last two) is, by definition,
@@ -279,7 +334,7 @@ class Indexer:
                  row_ids: Optional[torch.Tensor] = None, schedule_stats: Optional[Tuple[float, float]] = None,
                  corpus_keys: Optional[torch.Tensor] = None, l2_form: str = "exact", window_rows: Optional[int] = None,
                  row_align: int = 4, storage: Optional[str] = None, quantiser=None, refine: Optional[str] = None, refine_factor: int = 4,
-                 tags: Optional[torch.Tensor] = None):
+                 tags: Optional[torch.Tensor] = None, pq_dsub: Optional[int] = None, pq_dim: Optional[int] = None):
         # tags: None | int64 [N] in the caller's row order = one 64-bit tag word per row for per-query tag filters (`tag_mask=` of the
         # query calls).  The index keeps them beside `gid` in sorted order (`tags_sorted`, 8 bytes per row) and carries
         # them through add / remove / update; an index built without tags has none and refuses `tag_mask=` and `add(tags=)`.
@@ -303,9 +358,33 @@ class Indexer:
                              "(algo=None or 'tiled')")
         # quantiser (storage="sq8" only): None = train on the (float) corpus; (lo, step), float32 [d] = use it.  A uint8 corpus is codes
         # and has nothing to train on.
-        if quantiser is not None and self.storage != "sq8":
-            raise ValueError(f"quantiser= belongs to storage='sq8', not storage={self.storage!r}")
+        if quantiser is not None and self.storage not in ("sq8", "pq"):
+            raise ValueError(f"quantiser= belongs to storage='sq8' (lo, step) or storage='pq' (a codebook), not storage={self.storage!r}")
         self._quantiser_given = None
+        # storage="pq" (DESIGN.md 4.18): pq_dsub = width of a sub-vector (4 | 8 | 16, default 8); quantiser = None (train a codebook on
+        # the float corpus) or the codebook, float32 [M, 256, pq_dsub].  A uint8 [N, M] corpus IS codes and needs the codebook; its row
+        # width is then M * pq_dsub unless pq_dim names a d with a partial last sub-vector.
+        if (pq_dsub is not None or pq_dim is not None) and self.storage != "pq":
+            raise ValueError(f"pq_dsub= / pq_dim= belong to storage='pq', not storage={self.storage!r}")
+        self.pq_dsub = None
+        if self.storage == "pq":
+            self.pq_dsub = 8 if pq_dsub is None else pq_dsub
+            if isinstance(self.pq_dsub, bool) or self.pq_dsub not in PQ_DSUBS:
+                raise ValueError(f"pq_dsub must be one of {PQ_DSUBS}, got {pq_dsub!r}")
+            if tags is not None:
+                raise NotImplementedError("tags= is not built for storage='pq': the tagged kernels read no codebook (DESIGN.md 7)")
+            is_codes = candidate_vectors_gpu.dtype == torch.uint8
+            if is_codes and quantiser is None:
+                raise ValueError("a uint8 corpus is pq codes: storage='pq' needs quantiser=codebook to decode them")
+            width = int(candidate_vectors_gpu.shape[1])
+            d_pq = (width * self.pq_dsub if is_codes else width) if pq_dim is None else int(pq_dim)
+            if is_codes and (d_pq + self.pq_dsub - 1) // self.pq_dsub != width:
+                raise ValueError(f"pq_dim={d_pq} at pq_dsub={self.pq_dsub} is {(d_pq + self.pq_dsub - 1) // self.pq_dsub} code bytes per row, the corpus has {width}")
+            if not is_codes and d_pq != width:
+                raise ValueError(f"pq_dim={d_pq} != the corpus width {width}")
+            self._pq_dim = d_pq
+            if quantiser is not None:
+                self._quantiser_given = checked_codebook(quantiser, d_pq, self.pq_dsub)
         if self.storage == "sq8":
             if quantiser is not None:
                 self._quantiser_given = checked_quantiser(quantiser, int(candidate_vectors_gpu.shape[1]))
@@ -364,7 +443,7 @@ class Indexer:
                 raise NotImplementedError("refine= needs metric 'l2' or 'cosine': the re-rank kernel computes the distance")
             # the caller's rows BEFORE they are compressed (sq8 codes have no other original than what they decode to)
             originals = candidate_vectors_gpu
-            if self.storage == "sq8" and originals.dtype == torch.uint8:
+            if self.storage in ("sq8", "pq") and originals.dtype == torch.uint8:
                 originals = self._dequantised(originals)
             self.refine_store = RefineStore(originals, self.metric, id_base=self.id_base, where=self.refine, row_align=self.row_align)
 
@@ -374,6 +453,10 @@ class Indexer:
 
     def _dequantised(self, rows, row_base=0):
         """Rows as the index holds them, in float32: `rows.to(storage).float()` (both steps exact on representable values)."""
+        if self.storage == "pq":
+            # codes decode as they are; anything else is encoded first (`nlsh_pq_encode`), then `nlsh_pq_decode_rows`: a copy out of the codebook
+            codes = rows if rows.dtype == torch.uint8 else self._pq_encode(rows, "corpus", row_base)
+            return self._pq_decode(codes)
         if self.storage == "sq8":
             # codes decode as they are; anything else is encoded first (the library's kernel: the one statement of the rule on the
             # device) -- deq(c, j) = float(c) * step[j] + lo[j] as two separately rounded torch operations
@@ -388,6 +471,46 @@ class Indexer:
         if self.storage != "sq8":
             raise AttributeError(f"storage={self.storage!r} has no quantiser")
         return self._qlo[:self.dim], self._qstep[:self.dim]
+
+    # ---- storage="pq": the codebook, the encoder and the decoder (csrc/pq_rows.hip) ----
+    @property
+    def codebook(self):
+        """The codebook of a pq index: float32 [M, 256, pq_dsub] on the device (what the kernels read)."""
+        if self.storage != "pq":
+            raise AttributeError(f"storage={self.storage!r} has no codebook")
+        return self._codebook
+
+    def _pq_set_codebook(self, corpus, dev):
+        """The device codebook: the given one (held against NaN / inf here if it came on a device), or trained on the float `corpus`."""
+        if self._quantiser_given is not None:
+            cb = self._quantiser_given.to(dev)
+            if not bool(torch.isfinite(cb).all()):
+                raise ValueError("codebook must be finite")
+        else:
+            from .training import pq_train
+            if not bool(torch.isfinite(corpus).all()):      # the trainer samples: a refusal must not depend on the sample
+                bad = int(torch.nonzero(~torch.isfinite(corpus.float()).all(dim=1)).reshape(-1)[0])
+                self._raise_unrepresentable(bad, self.storage, "corpus")
+            cb = pq_train(corpus, self.pq_dsub)
+        self._codebook = cb.contiguous()
+        self._quantiser_given = None
+
+    def _pq_encode(self, rows, what, row_base=0):
+        """Float rows [n, d] (float32 / float16, unit column stride) -> their codes, uint8 [n, M], by `nlsh_pq_encode`; a row holding a
+        NaN or an infinity raises ValueError naming it (`what` row `row_base` + its number)."""
+        return pq_encode(rows, self._codebook, self.dim, what, row_base)
+
+    def _pq_decode(self, codes):
+        """Codes [n, >= M] (any pitch) -> the decoded rows, float32 [n, d], by `nlsh_pq_decode_rows`."""
+        return pq_decode(codes, self._codebook, self.dim)
+
+    def _pq_inv_norm(self, codes_sorted):
+        """inv_norm of the sorted code rows by the float32 path's rule on the decoded rows (`nlsh_pq_inv_norm`)."""
+        n, dev = int(codes_sorted.shape[0]), codes_sorted.device
+        out = torch.empty((n,), dtype=torch.float32, device=dev)
+        _capi.check(_capi.lib().nlsh_pq_inv_norm(_capi.ptr(codes_sorted), codes_sorted.stride(0) if n else self.row_stride, n,
+                                                 _capi.ptr(self._codebook), self.pq_dsub, self.dim, _capi.ptr(out), _stream(dev)))
+        return out
 
     def _sq8_set_quantiser(self, corpus, d, stride, dev):
         """The pitch-padded quantiser arrays (lo = 0, step = 1 behind d): the given one, or trained on `corpus` by `nlsh_sq8_train`."""
@@ -424,7 +547,7 @@ class Indexer:
         """Rows [*, d] (unit column stride, a dtype the library reads) picked by `perm` [M] -> `out` [M, row_stride] as the storage holds
         them, by the storage's C entry.  A compressed storage reads one pair of flags back: a row it cannot hold raises ValueError
         naming it (`what` row `row_base` + its number), the saturated rows of sq8 are counted in `last_clamped_rows`."""
-        L, dev, M, d = _capi.lib(), out.device, int(perm.shape[0]), self.dim
+        L, dev, M, d = _capi.lib(), out.device, int(perm.shape[0]), self._store_dim
         src = (_capi.ptr(rows), _STORE_CODE_OF_DTYPE[rows.dtype], rows.stride(0) if M else d, d, _capi.ptr(perm), M, _capi.ptr(out))
         tail = (_capi.ptr(inv_norm), _capi.ptr(gid), id_base)
         if not self.compressed:
@@ -457,7 +580,7 @@ class Indexer:
     @staticmethod
     def _raise_unrepresentable(bad_row, storage, what):
         rule = ("a finite value that float16 rounds to an infinity" if storage == "float16"
-                else "a NaN or an infinity" if storage == "sq8"
+                else "a NaN or an infinity" if storage in ("sq8", "pq")
                 else "a value that is not an integer in [0, 255]")
         raise ValueError(f"{what} row {bad_row} holds {rule}: it cannot be stored as storage={storage!r} (nothing was changed)")
 
@@ -499,7 +622,18 @@ class Indexer:
         if corpus.stride(1) != 1:
             corpus = corpus.contiguous()
         dev = corpus.device
-        self.dim, self.row_stride = d, self._pitch(d)
+        # `_store_dim`: elements of a stored row -- d, or the M code bytes of a pq row; `row_stride`: its pitch in elements
+        self._store_dim = d
+        if self.storage == "pq":
+            d = self._pq_dim
+            self._store_dim = (d + self.pq_dsub - 1) // self.pq_dsub
+        self.dim, self.row_stride = d, self._pitch(self._store_dim)
+        if self.storage == "pq":
+            # the codebook comes first, then the codes in the caller's order: the keys are those of the DECODED rows, and the sorted copy
+            # is a uint8 row store of the codes (gathered as bytes below)
+            self._pq_set_codebook(corpus, dev)
+            if corpus.dtype != torch.uint8:
+                corpus = self._pq_encode(corpus, "corpus")
         if self.storage == "sq8":
             # the quantiser comes first: the keys are those of the DECODED rows (one read of the corpus trains it)
             self._sq8_set_quantiser(corpus, d, self.row_stride, dev)
@@ -510,6 +644,8 @@ class Indexer:
         self.gid = torch.empty((N,), dtype=torch.int32, device=dev)
         self.inv_norm = torch.empty((N,), dtype=torch.float32, device=dev) if self.metric == "cosine" else None
         self._gather(corpus, self.perm, self.corpus_sorted, "corpus", inv_norm=self.inv_norm, gid=self.gid, id_base=self.id_base)
+        if self.storage == "pq" and self.inv_norm is not None:      # the u8 gather took norms of the code bytes: the decoded rows' instead
+            self.inv_norm = self._pq_inv_norm(self.corpus_sorted)
         if self.row_ids is not None:
             if self.row_ids.shape[0] != N or self.row_ids.dtype != torch.int32:
                 raise ValueError("row_ids must be int32 [N]")
@@ -617,12 +753,14 @@ class Indexer:
         else:
             entry, head, new, flags = L.nlsh_csr_update_typed, (code,), (_STORE_CODE_OF_DTYPE[vectors.dtype] if M else code,), (None,)
         _capi.check(entry(
-            _capi.ptr(self.corpus_sorted), *head, stride, self.dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
+            _capi.ptr(self.corpus_sorted), *head, stride, self._store_dim, _capi.ptr(self.gid), _capi.ptr(self.inv_norm), _capi.ptr(self.uniq_keys),
             _capi.ptr(self.offsets), N, self.n_buckets, _capi.ptr(keep_u8), n_kept,
-            _capi.ptr(vectors), *new, vectors.stride(0) if M else self.dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
+            _capi.ptr(vectors), *new, vectors.stride(0) if M else self._store_dim, _capi.ptr(new_keys), _capi.ptr(new_ids), M,
             _capi.ptr(sorted_out), stride, _capi.ptr(gid_out), _capi.ptr(inv_out), _capi.ptr(src_out), _capi.ptr(uniq_out), _capi.ptr(offs_out),
             _capi.ptr(nb_out), *flags, _capi.ptr(ws), ws_bytes, _stream(dev)))
         n_buckets = int(nb_out.item())
+        if self.storage == "pq" and inv_out is not None and n_out:      # as in the build: the norms of the decoded rows
+            inv_out = self._pq_inv_norm(sorted_out)
         # the int32 side arrays in LOCAL order, from where every sorted row came from (`src_out`): torch plumbing, 4 bytes per row
         src = src_out.long()
         if N:
@@ -663,7 +801,7 @@ class Indexer:
             # the caller's rows as they came, under the ids they were given (default ids: next_id .. = id_base + rows of the store);
             # `remove` leaves the store alone -- stage one can no longer return a removed id
             originals = add
-            if self.storage == "sq8" and add.dtype == torch.uint8:
+            if self.storage in ("sq8", "pq") and add.dtype == torch.uint8:
                 originals = self._dequantised(vectors)
             assert int(new_ids[0].item()) == self.id_base + self.refine_store.n_rows
             self.refine_store.append(originals)
@@ -681,10 +819,11 @@ class Indexer:
             raise _capi.NlshHipError(_capi.E_INVALID, "added rows must be a device-resident tensor; there is no CPU path")
         if add.device != dev:
             raise ValueError(f"added rows are on {add.device}, the index on {dev}")
-        if add.dim() != 2 or add.shape[1] != self.dim:
-            raise ValueError(f"added rows must be [M, {self.dim}], got {tuple(add.shape)}")
+        width = self._store_dim if (self.storage == "pq" and isinstance(add, torch.Tensor) and add.dtype == torch.uint8) else self.dim
+        if add.dim() != 2 or add.shape[1] != width:
+            raise ValueError(f"added rows must be [M, {width}], got {tuple(add.shape)}")
         if add.dtype != torch.float32 and not (self.compressed and add.dtype == _STORAGES[self.storage][0]):
-            own = "uint8 (codes)" if self.storage == "sq8" else self.storage
+            own = "uint8 (codes)" if self.storage in ("sq8", "pq") else self.storage
             raise ValueError(f"added rows must be float32{' or ' + own if self.compressed else ''}, got {add.dtype}")
         M = int(add.shape[0])
         if M == 0:
@@ -697,7 +836,7 @@ class Indexer:
             if self.storage == "sq8":
                 self.last_clamped_rows = 0
             if vectors.dtype == torch.float32:
-                vectors = self._held_rows(vectors, "added")[:, :self.dim]
+                vectors = self._pq_encode(vectors, "added") if self.storage == "pq" else self._held_rows(vectors, "added")[:, :self.dim]
         if add_keys is not None:
             keys = add_keys
             if not isinstance(keys, torch.Tensor) or keys.shape != (M,) or keys.dtype != torch.int32 or keys.device != dev:
@@ -836,6 +975,8 @@ class Indexer:
         if tag_match not in TAG_MATCH:
             raise ValueError(f"tag_match must be one of {tuple(TAG_MATCH)}, got {tag_match!r}")
         if tag_mask is not None:
+            if self.storage == "pq":
+                raise NotImplementedError("tag_mask= is not built for storage='pq': the tagged kernels read no codebook (DESIGN.md 7)")
             if self.tags_sorted is None:
                 raise ValueError("tag_mask= on an index built without tags: pass tags= to the constructor")
             if isinstance(tag_mask, torch.Tensor):
@@ -1267,8 +1408,11 @@ class Indexer:
         Q, d = q.shape
         f = self._scan_fields(Q, d, keys, nkeys, k, algo, max_tasks, out_dist, out_idx, out_keys, ncand, status, ws, window)
         before = _SCAN_ARGS_BEFORE_QUERIES(f)
+        if self.storage == "pq":      # the entry of its own: codebook, dsub and the code pitch where the storage code stands; row_stride = M * dsub
+            before = (before[0], self._store_dim * self.pq_dsub) + tuple(before[2:])
         # an sq8 index has the call of its own: the quantiser's two arrays stand where the storage code does
         call, store = ((_capi.lib().nlsh_scan_topk_cells_phase_sq8, (self._qlo.data_ptr(), self._qstep.data_ptr())) if self.storage == "sq8"
+                       else (_capi.lib().nlsh_scan_topk_cells_phase_pq, (self._codebook.data_ptr(), self.pq_dsub, self.row_stride)) if self.storage == "pq"
                        else (_capi.lib().nlsh_scan_topk_cells_phase_filtered, (_STORAGES[self.storage][1],)))
         tail = ()
         if isinstance(filter, TagFilter):       # the tagged twin of either entry: tags, masks and mode behind the filter words
@@ -1328,9 +1472,9 @@ class Indexer:
         return torch.as_tensor(r32).to(dev)
 
     def _refuse_range_on_sq8(self):
-        if self.storage == "sq8":
-            raise NotImplementedError("radius (range) queries are not built for storage='sq8': the range kernels read float32, float16 "
-                                      "and uint8 rows only (DESIGN.md 7)")
+        if self.storage in ("sq8", "pq"):
+            raise NotImplementedError(f"radius (range) queries are not built for storage={self.storage!r}: the range kernels read float32, "
+                                      "float16 and uint8 rows only (DESIGN.md 7)")
 
     def _range_call_checks(self, what, filter, tag_mask):
         """What every range call refuses before it does anything, in this order -> the checked filter."""

@@ -61,7 +61,7 @@ class MultiTableIndexer:
     def __init__(self, hashings, candidate_vectors_gpu, distance_func, metric: Optional[str] = None, storage: Optional[str] = None,
                  l2_form: str = "exact", row_align: int = 4, window_rows: Optional[int] = None, corpus_keys=None,
                  row_ids: Optional[torch.Tensor] = None, id_base: int = 0, quantiser=None, refine: Optional[str] = None,
-                 refine_factor: int = 4, tags: Optional[torch.Tensor] = None):
+                 refine_factor: int = 4, tags: Optional[torch.Tensor] = None, pq_dsub: Optional[int] = None, pq_dim: Optional[int] = None):
         # tags: None | int64 [N] = `Indexer`'s `tags=`, handed to every table (each keeps them in its own sorted order: 8 bytes per row
         # and table); the queries then take `tag_mask=` / `tag_match=`
         # refine: None | "device" | "host" = ONE store of the caller's float32 rows behind the de-duplicating merge:
@@ -71,8 +71,10 @@ class MultiTableIndexer:
         if self.refine is not None and row_ids is not None:
             raise ValueError("refine= needs the default row ids (id_base + row): the refine store addresses a row by id - id_base, "
                              "row_ids= names rows freely")
-        if quantiser is not None and storage != "sq8":
-            raise ValueError(f"quantiser= belongs to storage='sq8', not storage={storage!r}")
+        if quantiser is not None and storage not in ("sq8", "pq"):
+            raise ValueError(f"quantiser= belongs to storage='sq8' (lo, step) or storage='pq' (a codebook), not storage={storage!r}")
+        if (pq_dsub is not None or pq_dim is not None) and storage != "pq":
+            raise ValueError(f"pq_dsub= / pq_dim= belong to storage='pq', not storage={storage!r}")
         hashings = list(hashings)
         if not hashings:
             raise ValueError("hashings is empty: a multi-table index needs at least one hasher")
@@ -93,17 +95,20 @@ class MultiTableIndexer:
         if self.metric not in ("l2", "cosine"):
             raise NotImplementedError("a multi-table index needs metric 'l2' or 'cosine': its merge rests on the tiled schedule's distance bits")
         # storage="sq8": ONE quantiser for all tables -- the given one, or the one the first table trains on the corpus -- so that every
-        # table holds the same decoded rows and a row's distance has one value whichever table finds it (the merge rests on that)
+        # table holds the same decoded rows and a row's distance has one value whichever table finds it (the merge rests on that).
+        # storage="pq": ONE codebook for all tables in the same way, trained (by the first table) or given once.
         self.tables: List[Indexer] = []
         for t, h in enumerate(hashings):
             kw = {} if storage != "sq8" else {"quantiser": quantiser if t == 0 else self.tables[0].quantiser}
+            if storage == "pq":
+                kw = {"quantiser": quantiser if t == 0 else self.tables[0].codebook, "pq_dsub": pq_dsub, "pq_dim": pq_dim}
             self.tables.append(Indexer(h, candidate_vectors_gpu, distance_func, compat=False, metric=self.metric, algo="tiled", storage=storage,
                                        l2_form=l2_form, row_align=row_align, window_rows=window_rows, row_ids=row_ids, id_base=id_base,
                                        corpus_keys=None if corpus_keys is None else corpus_keys[t], tags=tags, **kw))
         self.storage = self.tables[0].storage
         if self.refine is not None:
             originals = candidate_vectors_gpu
-            if self.storage == "sq8" and originals.dtype == torch.uint8:
+            if self.storage in ("sq8", "pq") and originals.dtype == torch.uint8:
                 originals = self.tables[0]._dequantised(originals)
             self.refine_store = RefineStore(originals, self.metric, id_base=id_base, where=self.refine, row_align=row_align)
         self.generation = 0         # +1 per effective add / remove / update: a MultiRowFilter of an older one is stale
@@ -244,7 +249,7 @@ class MultiTableIndexer:
             self.generation += 1
         if self.refine_store is not None and result is not None and int(result[0].shape[0]):
             originals = add
-            if self.storage == "sq8" and add.dtype == torch.uint8:
+            if self.storage in ("sq8", "pq") and add.dtype == torch.uint8:
                 originals = first._dequantised(add)
             assert int(result[0][0].item()) == self.refine_store.id_base + self.refine_store.n_rows
             self.refine_store.append(originals)      # once: the tables share the store

@@ -197,3 +197,44 @@ def fit_partition(hashing, x: torch.Tensor, labels: torch.Tensor, knn: Optional[
                 break
     hashing.train_mode(False)
     return losses
+
+
+def pq_train(x: torch.Tensor, dsub: int, iters: int = 10, seed: int = 0, sample: int = 65536) -> torch.Tensor:
+    """A product-quantiser codebook for `Indexer(storage="pq")`: float32 [M, 256, dsub] on x's device, M = ceil(d / dsub),
+    from `iters` Lloyd iterations per sub-space on a seeded sample of at most `sample` rows of x [n, d] (device).
+    The assignment step IS `nlsh_pq_encode` (the index's own encoder); the update is an `index_add_` mean per (sub-space, centroid), taken on
+    the host so that its summation order -- and with it the codebook -- is the same on every run of the same seed; an empty centroid keeps
+    its previous value.  The centroids start as sample rows; with fewer than 256 of them the rows repeat.  Rows holding a NaN or an infinity
+    are left out of the sample (the index refuses them by number when it encodes).  Columns of the last sub-vector at or beyond d are +0.
+    Seeded, not bit-defined across devices or library versions: the codebook is an input of the storage's rule, not part of it."""
+    from .indexer import PQ_DSUBS, pq_encode
+    if isinstance(dsub, bool) or dsub not in PQ_DSUBS:
+        raise ValueError(f"dsub must be one of {PQ_DSUBS}, got {dsub!r}")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be a [n, d] tensor")
+    if iters < 0 or sample < 1:
+        raise ValueError("iters must be >= 0 and sample >= 1")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    M, dev = (d + dsub - 1) // dsub, x.device
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    rows = x if n <= sample else x[torch.randint(n, (sample,), generator=g).to(dev)]
+    rows = rows.float()
+    rows = rows[torch.isfinite(rows).all(dim=1)].contiguous()
+    S = int(rows.shape[0])
+    if S == 0:
+        return torch.zeros((M, 256, dsub), dtype=torch.float32, device=dev)
+    padded = torch.zeros((S, M * dsub), dtype=torch.float32)
+    padded[:, :d] = rows.cpu()
+    sub = padded.view(S * M, dsub)      # row s * M + m: sub-vector m of sample row s
+    start = torch.arange(256) % S if S < 256 else torch.randperm(S, generator=g)[:256]
+    cb = padded[start].view(256, M, dsub).permute(1, 0, 2).contiguous()
+    offs = (torch.arange(M) * 256)[None, :]
+    for _ in range(iters):
+        codes = pq_encode(rows, cb.to(dev), d, "sample").cpu().long()       # [S, M]
+        flat = (codes + offs).view(-1)
+        sums = torch.zeros((M * 256, dsub), dtype=torch.float32).index_add_(0, flat, sub)
+        counts = torch.zeros((M * 256,), dtype=torch.float32).index_add_(0, flat, torch.ones((S * M,), dtype=torch.float32))
+        mean = sums / counts.clamp(min=1.0)[:, None]
+        cb = torch.where((counts > 0)[:, None], mean, cb.view(M * 256, dsub)).view(M, 256, dsub).contiguous()
+    return cb.to(dev)

@@ -13,9 +13,11 @@ Workloads (the generators bench.py uses, the learned hashes of checkpoints/):
 Every storage of a workload gets the same `corpus_keys=` and the same query key table, so the task tables are identical and the results
 are compared bit for bit before anything is timed.  `--sq8` adds an sq8 index of the same rows to every workload (same keys, same task
 table, its own distances): recall@10 against the float32 lists and the training pass beside a device copy are reported with the times
-(profiles/sq8_storage.txt is made from it).
+(profiles/sq8_storage.txt is made from it).  `--pq 4,8,16` adds a product-quantised index per sub-vector width in the same way (DESIGN.md
+4.18; profiles/pq_storage.txt): codebook training time, encoder rows/s, bytes per row, recall@10 against the float32 lists without and
+with an exact re-rank of 2 / 4 / 8 x k stage-one candidates.
 
-    python tools/storage_bench.py [--workloads sift1m,clusters,glove,deep] [--sq8] [--rounds 7] [--iters 10] [--steps 20] [--out FILE]
+    python tools/storage_bench.py [--workloads sift1m,clusters,glove,deep] [--sq8] [--pq 4,8,16] [--rounds 7] [--iters 10] [--steps 20] [--out FILE]
 
 Prints one JSON line per workload and a table; `--out` also writes the table to a file (profiles/corpus_storage.txt is made from it).
 """
@@ -84,8 +86,30 @@ def recall_at_k(got_idx, ref_idx):
     return hits / max(int((r >= 0).sum()), 1)
 
 
-def build(tag, n_rows, Q, dev, sq8=False):
-    """-> ({storage: Indexer}, query batch, key table, (distinct candidate rows, candidates) of the batch, sq8 extras or None)."""
+def pq_index(hashing, stored, dist, w, dsub, keys_of_rows):
+    """-> (pq Indexer at this sub-vector width over `stored`, {training seconds, encoder ms (median of 3, HIP events)})."""
+    from nlsh_amd.indexer import pq_encode
+    from nlsh_amd.training import pq_train
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    cb = pq_train(stored, dsub)
+    torch.cuda.synchronize()
+    train_s = time.perf_counter() - t0
+    ix = Indexer(hashing, stored, dist, compat=w["compat"], storage="pq", pq_dsub=dsub, quantiser=cb, corpus_keys=keys_of_rows)
+    enc = []
+    for _ in range(4):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        codes = pq_encode(stored, ix.codebook, ix.dim)
+        b.record()
+        torch.cuda.synchronize()
+        enc.append(a.elapsed_time(b))
+    del codes
+    return ix, {"train_s": train_s, "encode_ms": float(np.median(enc[1:])), "code_bytes_per_row": int(ix._store_dim), "pitch_bytes": int(ix.row_stride)}
+
+
+def build(tag, n_rows, Q, dev, sq8=False, pq=()):
+    """-> ({storage: Indexer}, query batch, key table, (distinct candidate rows, candidates) of the batch, sq8 extras or None, pq extras)."""
     w = WORKLOADS[tag]
     N, d = n_rows or w["N"], w["d"]
     gen = getattr(synth, w["gen"])
@@ -117,13 +141,26 @@ def build(tag, n_rows, Q, dev, sq8=False):
         keys_of_rows = ix.corpus_keys
         ixs[storage] = ix
         del src
+    pq_extras = {}
+    for dsub in pq:
+        ixs[f"pq{dsub}"], pq_extras[f"pq{dsub}"] = pq_index(hashing, stored, dist, w, dsub, keys_of_rows)
+    store = None
+    if pq:      # the exact second stage over the rows every storage was built from (nlsh_amd/refine.py), driven by hand on stage-one lists
+        from nlsh_amd.refine import RefineStore
+        store = RefineStore(stored, w["metric"], id_base=0, where="device")
     keys, nkeys = ixs["float32"].hash_device(q, hash_times=P, seed=7)
     ref, extras = None, None
     for storage, ix in ixs.items():                 # sizes the task tables (checked calls) and holds every storage to the float32 bits
         out = ix.scan_tensors(q, keys, nkeys, k=K)
         if ref is None:
             ref = out
-        if storage == "sq8":                        # other rows, by design: the same candidates, its own distances
+        if storage.startswith("pq"):                # other rows, by design: the same candidates, its own distances
+            assert torch.equal(out[2], ref[2]), storage
+            pq_extras[storage]["recall"] = recall_at_k(out[1], ref[1])
+            for f in (2, 4, 8):
+                one = ix.scan_tensors(q, keys, nkeys, k=f * K)
+                pq_extras[storage][f"recall_refine_{f}"] = recall_at_k(store.rerank(q, one[1], K)[1], ref[1])
+        elif storage == "sq8":                      # other rows, by design: the same candidates, its own distances
             assert torch.equal(out[2], ref[2]), storage
             t_train, t_copy = train_vs_copy(stored, ix.row_stride)
             extras = {"recall_at_k_vs_float32": recall_at_k(out[1], ref[1]), "clamped_rows": ix.last_clamped_rows,
@@ -135,7 +172,8 @@ def build(tag, n_rows, Q, dev, sq8=False):
     pos = torch.searchsorted(ix.uniq_keys, keys.clamp(min=int(ix.uniq_keys[0]), max=int(ix.uniq_keys[-1]))).clamp(max=ix.n_buckets - 1)
     hit = (ix.uniq_keys[pos] == keys) & (torch.arange(keys.shape[1], device=dev)[None, :] < nkeys[:, None])
     rows = (ix.offsets[1:] - ix.offsets[:-1]).long()
-    return ixs, q, keys, nkeys, (int(rows[torch.unique(pos[hit])].sum().item()), int(ref[2].long().sum().item())), extras
+    del store
+    return ixs, q, keys, nkeys, (int(rows[torch.unique(pos[hit])].sum().item()), int(ref[2].long().sum().item())), extras, pq_extras
 
 
 def time_round(ix, q, keys, nkeys, iters, steps):
@@ -170,6 +208,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10, help="scan launches per storage and round")
     ap.add_argument("--steps", type=int, default=20, help="device-resident batches per storage and round")
     ap.add_argument("--sq8", action="store_true", help="also build and time an sq8 index of every workload (recall and training time reported)")
+    ap.add_argument("--pq", default="", help="comma-separated sub-vector widths (4, 8, 16): also build and time a pq index per width")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -177,7 +216,8 @@ def main():
     dev = torch.device("cuda", 0)
     lines = []
     for tag in args.workloads.split(","):
-        ixs, q, keys, nkeys, (uniq_rows, sum_c), extras = build(tag, args.rows, args.queries, dev, sq8=args.sq8)
+        ixs, q, keys, nkeys, (uniq_rows, sum_c), extras, pq_extras = build(tag, args.rows, args.queries, dev, sq8=args.sq8,
+                                                                           pq=tuple(int(v) for v in args.pq.split(",") if v))
         d = ixs["float32"].dim
         for ix in ixs.values():     # warm-up round, untimed
             time_round(ix, q, keys, nkeys, 3, 3)
@@ -191,13 +231,15 @@ def main():
         for s, ix in ixs.items():
             scan, batch = spread([r[0] for r in rounds[s]]), spread([r[1] for r in rounds[s]])
             elem = ix.corpus_sorted.element_size()
-            row_bytes = d * elem                    # the bytes of a row the scan needs (the pitch may pad)
+            row_bytes = (ix._store_dim if s.startswith("pq") else d) * elem    # the bytes of a row the scan needs (the pitch may pad)
             base = base or scan["median"]
             res["storages"][s] = {"index_bytes": int(ix.corpus_sorted.numel() * elem), "row_pitch_bytes": int(ix.row_stride * elem), "scan_ms": scan,
                                   "batch_ms": batch, "route": ix.last_query_path, "scan_vs_float32": scan["median"] / base,
                                   "hbm_frac_of_distinct_candidate_rows": uniq_rows * row_bytes / (scan["median"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
         if extras:
             res["sq8"] = extras
+        if pq_extras:
+            res["pq"] = pq_extras
         print(json.dumps(res), flush=True)
         lines.append(f"{tag}: N={res['N']} d={d} Q={args.queries} k={K} hash_times={P}, {res['n_buckets']} buckets, {uniq_rows} distinct candidate rows, "
                      f"{sum_c} candidates per batch; {args.rounds} interleaved rounds x ({args.iters} scans, {args.steps} batches)")
@@ -213,6 +255,11 @@ def main():
                          f"{extras['clamped_rows']} rows saturated; training pass {extras['train_ms']:.3f} ms ({gbps(extras['train_ms'], 1):.0f} GB/s read) "
                          f"beside a device copy of the same {extras['train_bytes'] / 2 ** 20:.0f} MiB {extras['copy_ms']:.3f} ms "
                          f"({gbps(extras['copy_ms'], 2):.0f} GB/s read + written)")
+        for s, e in pq_extras.items():
+            lines.append(f"  {s}: {e['code_bytes_per_row']} code bytes per row (pitch {e['pitch_bytes']}); pq_train {e['train_s']:.2f} s; nlsh_pq_encode "
+                         f"{e['encode_ms']:.2f} ms = {res['N'] / (e['encode_ms'] * 1e-3) / 1e6:.1f} M rows/s; recall@{K} against the float32 lists "
+                         f"{e['recall']:.4f}, re-ranked from 2k / 4k / 8k stage-one candidates {e['recall_refine_2']:.4f} / {e['recall_refine_4']:.4f} / "
+                         f"{e['recall_refine_8']:.4f}")
         del ixs, q, keys, nkeys
         torch.cuda.empty_cache()
     table = "\n".join(lines)
